@@ -119,6 +119,36 @@ def cpu_baseline(dims, Lp, threads):
                        f"{times[4]:.2f}s -> {per_layer:.2f}s per extra layer; 32-layer time extrapolated linearly = {total:.1f}s")}
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: every file together stays below this
+
+
+def dump_outputs(out_dir, model, opt, loss):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy — `loss` (float64), and for every trainable tensor
+    `grad.<param>` (the gradient AdamW read) and `param.<param>` (its fp32 master weight after the update), float32.  A tensor larger than its
+    share of DUMP_BYTES is written as a 1-D sample at flat indices drawn from np.random.default_rng(0) (sorted, unique): the same positions
+    for a tensor's gradient and master and in every run with the same arguments, so two builds compare output for output."""
+    model.engine.wait_param_updates()
+    names = list(opt.state)
+    numels = [opt.state[n]["master"].numel() for n in names]
+    budget = (DUMP_BYTES - (2 * len(names) + 1) * 4096) // 8          # float32 elements per kind (grad, param); 4 KB per file for headers
+    lo, hi = 0, max(numels)
+    while lo < hi:                                                       # the largest per-tensor sample length that fits the budget
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if sum(min(n, mid) for n in numels) <= budget else (lo, mid - 1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array(float(loss), dtype=np.float64))
+    for n, numel in zip(names, numels):
+        p = opt.state[n]["p"]
+        idx = None
+        if numel > lo:
+            idx = torch.from_numpy(np.unique(np.random.default_rng(0).integers(0, numel, lo))).to(p.device)
+        for kind, t in (("grad", getattr(p, "main_grad", None)), ("param", opt.state[n]["master"])):
+            if t is None:
+                continue
+            t = t.detach().reshape(-1)[idx] if idx is not None else t.detach()
+            np.save(os.path.join(out_dir, f"{kind}.{n}.npy"), t.float().cpu().numpy())
+
+
 class SmiSampler:
     """Engine clock and socket power while the timed region runs (rocm-smi as a child process every ~0.4 s): the dominant
     kernel is power-limited, so a box-to-box difference in ms/step shows up here."""
@@ -219,11 +249,16 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="N=1 only: create a one-rank RCCL group and run the gradient exchange through it anyway "
                                                               "(every collective of the N>1 step on the real backend; the line is marked rehearsal)")
     ap.add_argument("--dry-launch", action="store_true", help="launcher self-test: ranks rendezvous (gloo, host tensors), check the world size and exit without touching the GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps (rank 0): what the last timed step computed — loss, gradients and updated fp32 master weights of the "
+                         "trainable tensors — as DIR/<name>.npy, 64 MB at most (large tensors as a fixed seeded sample; see dump_outputs)")
     a = ap.parse_args()
 
     if a.workload == "decode":
         if a.gpus != 1:
             raise SystemExit("--workload decode is a single-GPU configuration (BASELINE.json configs[4])")
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs covers the training step (--workload train)")
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_decode
         print(json.dumps(bench_decode.run(batch=256, steps=32)), flush=True)
@@ -317,6 +352,7 @@ def main():
         model.engine.grad_sync = sync
         return model, opt, sync
 
+    torch.manual_seed(0)                                         # torch's default generators (DropPath draws in --mode pc): the same inputs in every run
     # ---- synthetic batch, resident in HBM before the timed region (rank r gets samples r*B .. r*B+B-1)
     clips = [synth.synth_clip(rank * B + i, T, H, W) for i in range(B)]
     rgb = torch.from_numpy(np.stack([c[0] for c in clips])).to(dev)
@@ -338,8 +374,9 @@ def main():
         if world > 1:
             dist.barrier()
 
-    def measure(model, opt, sync, steps, warmup, gemm_event_steps, smi):
-        """`warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides (the bench contract)."""
+    def measure(model, opt, sync, steps, warmup, gemm_event_steps, smi, dump_dir=None):
+        """`warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides (the bench contract).
+        dump_dir: after the timed region, rank 0 writes what the last step computed (dump_outputs)."""
         OVERLAP_OPT = (OVERLAP_ENV != "0") if OVERLAP_ENV is not None else model.engine.any_layer_trainable
         EARLY_OPT = OVERLAP_OPT and EARLY_ENV
 
@@ -389,11 +426,14 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, model, opt, loss)
         return float(tmax), per_step, float(loss), prof, ev_steps
 
     model, opt, sync = build(a.mode)
     smi = SmiSampler(local) if rank == 0 else None
-    dt, per_step, loss, prof, ev_steps = measure(model, opt, sync, a.steps, a.warmup, None if a.no_gemm_events else a.gemm_event_steps, smi)
+    dt, per_step, loss, prof, ev_steps = measure(model, opt, sync, a.steps, a.warmup, None if a.no_gemm_events else a.gemm_event_steps, smi,
+                                                 dump_dir=a.dump_outputs)
     ms_median = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     clips_total = a.steps * B * world
     value = clips_total / dt / world            # clips/sec/GPU ... see `value` note below

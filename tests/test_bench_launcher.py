@@ -45,3 +45,45 @@ def test_bench_fails_fast_when_one_rank_dies_at_startup():
     assert dt < 30, dt
     assert "rank 1 exited with code 3" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]                 # no result line from a broken job
+
+
+def test_dump_outputs_within_budget_and_repeatable(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs) on host tensors, with the budget shrunk to 1 MB: float64 loss, float32 gradients
+    and masters (a bf16 gradient included), small tensors whole, large ones sampled at the same positions for a gradient and its master,
+    the directory within the budget, and a second dump byte-identical to the first."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    shapes = {"small.weight": (64, 32), "big.weight": (512, 512), "wide.weight": (256, 1024)}
+    state = {}
+    for i, (n, shp) in enumerate(shapes.items()):
+        master = torch.arange(shp[0] * shp[1], dtype=torch.float32).view(shp)          # value == flat index
+        grad = (2 * master).to(torch.bfloat16 if i == 1 else torch.float32)             # big.weight: a bf16 gradient, as GradSync's wire buffers hold
+        state[n] = {"p": types.SimpleNamespace(main_grad=grad, device=torch.device("cpu")), "master": master}
+    model = types.SimpleNamespace(engine=types.SimpleNamespace(wait_param_updates=lambda: None))
+    opt = types.SimpleNamespace(state=state)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), model, opt, torch.tensor(1.25))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(["loss.npy"] + [f"{k}.{n}.npy" for n in shapes for k in ("grad", "param")])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 1 << 20
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes(), f
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float64 and float(loss) == 1.25
+    small = np.load(tmp_path / "a" / "param.small.weight.npy")
+    assert small.dtype == np.float32 and np.array_equal(small, state["small.weight"]["master"].numpy())
+    for n in ("big.weight", "wide.weight"):
+        p = np.load(tmp_path / "a" / f"param.{n}.npy")
+        g = np.load(tmp_path / "a" / f"grad.{n}.npy")
+        numel = shapes[n][0] * shapes[n][1]
+        assert p.dtype == g.dtype == np.float32 and p.ndim == 1 and 1000 < p.size < numel
+        assert np.all(np.diff(p) > 0) and p[0] >= 0 and p[-1] < numel                 # sorted, unique flat indices of the tensor
+        if n == "wide.weight":
+            assert np.array_equal(g, 2 * p)                                           # the gradient sampled at the master's positions
+        else:
+            assert np.allclose(g, 2 * p, rtol=2 ** -7)                                # (bf16 gradient: values rounded to 8 bits)

@@ -72,12 +72,12 @@ def test_train_validate_checkpoint_resume_evaluate(tmp_path):
     assert ms["n"] == 4 and np.isfinite(ms["FDE"])
 
 
-def test_backward_overwrites_unless_accumulating():
+def test_backward_overwrites_unless_accumulating(tmp_path):
     """from step 2 on the fp32 driver loop summed gradients over steps.  loss_and_backward overwrites unless
     `accumulate_grads` is set, in both dtypes; two micro-batches accumulated == one batch of twice the size."""
     from egoscaler_amd.driver import SyntheticTrajData
     for dtype in (torch.float32, torch.bfloat16):
-        dims, args, m = _setup("/tmp", dtype=dtype)
+        dims, args, m = _setup(tmp_path, dtype=dtype)
         m.train()
         data = SyntheticTrajData(dims, 8, frames=2, size=32, text_len=8, num_steps=5)
         dev = torch.device("cuda")
