@@ -42,9 +42,36 @@ def sample_rows(logits, scores, seq, pos, rep_from, ids, done, repetition_penalt
          c_i64(0 if pad is None else int(pad)), c_i(dt(logits.dtype)), S())
 
 
+def beam_rows(logits, lg_div, R, nb, scores, seq, pos, repetition_penalty, temperature, top_k, top_p, min_keep, do_sample, rng, draw, run_score,
+              cand_key, cand_score, cand_tok, ctl):
+    """One beam step's row pass (include/egomi.h egomi_beam_rows): processed log-probs (HF's `.scores`) + each row's K best candidates."""
+    V = logits.shape[1]
+    call("egomi_beam_rows", P(logits), c_i64(logits.stride(0)), c_i(lg_div), c_i(R), c_i(V), c_i(nb), P(scores), c_i64(scores.stride(0)), P(seq),
+         c_i64(seq.stride(0) if seq is not None else 0), c_i(pos), c_f(repetition_penalty), c_f(temperature), c_i(int(top_k or 0)), c_f(top_p),
+         c_i(min_keep), c_i(int(bool(do_sample))), P(rng), c_i(draw), P(run_score), c_i(cand_key.shape[1]), P(cand_key), P(cand_score), P(cand_tok),
+         P(ctl), c_i(dt(logits.dtype)), S())
+
+
+def beam_update(B, nb, V, cand_key, cand_score, cand_tok, S0, cur_len, max_len, eos, length_penalty, early_stopping, seq, fin_seq, bidx, fin_bidx,
+                kv_row, run_score, fin_score, fin_flag, heur, tok, ctl):
+    """One beam step's per-item update (include/egomi.h egomi_beam_update).  early_stopping: False / True / "never"."""
+    es = 2 if early_stopping == "never" else int(bool(early_stopping))
+    call("egomi_beam_update", c_i(B), c_i(nb), c_i(cand_key.shape[1]), c_i(V), P(cand_key), P(cand_score), P(cand_tok), c_i(S0), c_i(cur_len),
+         c_i(max_len), c_i64(-1 if eos is None else int(eos)), c_f(length_penalty), c_i(es), P(seq), P(fin_seq), c_i64(seq.stride(0)), P(bidx),
+         P(fin_bidx), c_i64(bidx.stride(0)), P(kv_row), c_i64(kv_row.stride(0)), P(run_score), P(fin_score), P(fin_flag), P(heur), P(tok), P(ctl), S())
+
+
+def attn_decode_rows(q, ld_q, kc, vc, kv_row, n_phys, key_mask, out, B, nb, H, hd, Smax, T_len, scale):
+    """attn_decode with key t of logical row r read from physical cache row kv_row[r, t] (include/egomi.h egomi_attn_decode_rows)."""
+    call("egomi_attn_decode_rows", P(q), c_i64(ld_q), P(kc), P(vc), P(kv_row), c_i64(kv_row.stride(0)), c_i(n_phys), P(key_mask),
+         c_i64(key_mask.stride(0) if key_mask is not None else 0), P(out), c_i64(out.stride(0)), c_i(B), c_i(nb), c_i(H), c_i(hd), c_i(Smax),
+         c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+
+
 class Decoder:
-    def __init__(self, engine, B, max_len):
-        self.eng, self.B, self.Smax = engine, B, max_len
+    def __init__(self, engine, B, max_len, num_beams=1):
+        """B = rows of the cache and of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...))."""
+        self.eng, self.B, self.Smax, self.nb = engine, B, max_len, int(num_beams)
         lm = engine.dims.lm
         L, H, hd, d, Fd, V = lm.num_hidden_layers, lm.num_attention_heads, lm.head_dim, lm.hidden_size, lm.intermediate_size, lm.vocab_size
         T, dev = engine.dtype, engine.device
@@ -62,6 +89,9 @@ class Decoder:
         self.rng = z(2, dtype=torch.int64)
         self.done_buf = z(B, dtype=torch.int32)
         self._graphs, self._scores = {}, {}
+        self.kv_row = None                                  # beam mode: [B, Smax] int32, physical cache row of every key of every logical row
+        if self.nb > 1:
+            self._beam_buffers()
         self.seq = None
         self.mask = None
         self.pos = 0
@@ -86,11 +116,16 @@ class Decoder:
             self.fused["down"] = ops.mm_slabs(self.act, w["model.layers.0.mlp.down_proj.weight"], self.x, self.gws, count_only=True)
 
     # -- prefill -------------------------------------------------------------------------------------
-    def _set_inputs(self, input_ids, mask, total_new):
-        """Prompt ids and key mask into the static buffers (`seq` is a [B, S0 + total_new] view of rows that are Smax long)."""
+    def _set_inputs(self, input_ids, mask, total_new, nb=1):
+        """Prompt ids and key mask into the static buffers (`seq` is a [B, S0 + total_new] view of rows that are Smax long); nb > 1: every
+        prompt row serves the nb logical beams of its item."""
         B, S0 = input_ids.shape
         if S0 + total_new > self.Smax:
             raise ValueError("prompt + new tokens exceed the decoder's cache length")
+        if B * nb != self.B:
+            raise ValueError(f"{B} prompts x {nb} beams do not fill the decoder's {self.B} rows")
+        if nb > 1:
+            input_ids, mask = input_ids.repeat_interleave(nb, 0), mask.repeat_interleave(nb, 0)
         self.mask_buf.fill_(1)
         self.mask_buf[:, :S0] = mask.to(torch.uint8)
         self.mask = self.mask_buf
@@ -103,18 +138,20 @@ class Decoder:
         H, hd, d = lm.num_attention_heads, lm.head_dim, lm.hidden_size
         kv_append(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), self.kc[l], self.vc[l], B, Sq, H, hd, self.Smax, 0)
 
-    def prefill(self, input_ids, attention_mask, point_clouds, fps_start, total_new):
+    def prefill(self, input_ids, attention_mask, point_clouds, fps_start, total_new, nb=1):
+        """nb > 1 (beam mode): the B prompts run ONCE each; their K/V land in physical cache rows 0..B-1 and their logits in rows 0..B-1 of
+        self.lg, which every beam of the item reads at step 0 (HF expands to B * nb identical rows and prefills them all)."""
         B, S0 = input_ids.shape
         dev = self.eng.device
         mask = torch.ones(B, S0, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
-        self._set_inputs(input_ids, mask, total_new)
+        self._set_inputs(input_ids, mask, total_new, nb)
         hn = self.eng.forward_hidden(input_ids, mask, point_clouds, fps_start, save=False, kv_sink=self._sink)
         self.pos = S0
         last = hn.view(B, S0, -1)[:, -1].contiguous()
-        ops.mm(last, self.eng.w["lm_head.weight"], out=self.lg)
-        return self.lg
+        ops.mm(last, self.eng.w["lm_head.weight"], out=self.lg[:B])
+        return self.lg[:B]
 
-    def prefill_chunked(self, input_ids, attention_mask, point_clouds, fps_start, total_new, chunk=16):
+    def prefill_chunked(self, input_ids, attention_mask, point_clouds, fps_start, total_new, chunk=16, nb=1):
         """prefill() for large batches (config 5: bs=256): the prompt pass runs `chunk` samples at a time (its activations are
         what limits the batch, not the cache) and every chunk appends its K/V rows to its own slice of the static cache."""
         B, S0 = input_ids.shape
@@ -122,7 +159,7 @@ class Decoder:
         lm = eng.dims.lm
         H, hd, d = lm.num_attention_heads, lm.head_dim, lm.hidden_size
         mask = torch.ones(B, S0, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
-        self._set_inputs(input_ids, mask, total_new)
+        self._set_inputs(input_ids, mask, total_new, nb)
         for b0 in range(0, B, chunk):
             b1 = min(B, b0 + chunk)
 
@@ -136,7 +173,7 @@ class Decoder:
             last = hn.view(b1 - b0, S0, -1)[:, -1].contiguous()
             ops.mm(last, eng.w["lm_head.weight"], out=self.lg[b0:b1])
         self.pos = S0
-        return self.lg
+        return self.lg[:B]
 
     # -- one decode step on static buffers: consumes self.tok, leaves logits in self.lg ---------------------
     def step(self, pos):
@@ -159,7 +196,10 @@ class Decoder:
                 ops.mm(self.h, self.wqkv[l], out=self.qkv, workspace=self.gws)
                 ops.rope_(self.qkv, eng.cos, eng.sin, B, 1, pos, 2 * H, hd, 3 * d)
                 kv_append(self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, self.kc[l], self.vc[l], B, 1, H, hd, self.Smax, pos)
-            attn_decode(self.qkv, 3 * d, self.kc[l], self.vc[l], self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
+            if self.kv_row is None:
+                attn_decode(self.qkv, 3 * d, self.kc[l], self.vc[l], self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
+            else:
+                attn_decode_rows(self.qkv, 3 * d, self.kc[l], self.vc[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd, self.Smax, pos + 1, scale)
             if fo:
                 n = ops.mm_slabs(self.ao, w[p + "self_attn.o_proj.weight"], self.x_mid, self.gws)
                 ops.slabs_rmsnorm(self.gws, n, x, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, self.x_mid, self.h2)
@@ -259,3 +299,91 @@ class Decoder:
         self.graph = g
         self.pos = S0 + T_new
         return self.seq, ([sc_buf[t] for t in range(T_new)] if keep_scores else None)
+
+    # -- beam search / beam sampling ---------------------------------------------------------------
+    def _beam_buffers(self):
+        R, Smax, dev = self.B, self.Smax, self.eng.device
+        z = lambda *s, dtype: torch.zeros(*s, dtype=dtype, device=dev)
+        self.kv_row = z(R, Smax, dtype=torch.int32)
+        self.fin_seq = z(R, Smax, dtype=torch.int64)
+        self.bidx = z(R, Smax, dtype=torch.int32)             # HF's running_beam_indices / beam_indices (columns 0 .. new tokens - 1)
+        self.fin_bidx = z(R, Smax, dtype=torch.int32)
+        self.run_score, self.fin_score = z(R, dtype=torch.float32), z(R, dtype=torch.float32)
+        self.fin_flag, self.heur = z(R, dtype=torch.int32), z(R // self.nb, dtype=torch.int32)
+        self.ctl = z(8, dtype=torch.int32)                    # [0] loop open, [1] iterations run, [2..5] per-step tallies (egomi_beam_update)
+        self._cands = {}
+
+    def beam(self, T_new, num_return_sequences=1, length_penalty=1.0, early_stopping=False, do_sample=False, temperature=1.0, top_k=50,
+             top_p=1.0, repetition_penalty=1.0, eos=None, pad=None, seed=None, use_graph=True):
+        """After prefill(nb=self.nb): HF _beam_search (generation/utils.py:3208-3560) for T_new steps, every step one egomi_beam_rows + one
+        egomi_beam_update launch + one cached decode step over the B * nb logical beams, all captured into ONE hipGraph (no host sync per
+        step: the loop-open flag lives in device memory and closes the remaining steps when HF would have left its loop).
+        Returns (sequences [B*nrs, S0 + Lgen], sequences_scores [B*nrs], scores [iterations, B*nb, V] fp32, beam_indices [B*nrs, Lgen])."""
+        nb, R, S0, dev = self.nb, self.B, self.pos, self.eng.device
+        Bi, V = R // nb, self.lg.shape[1]
+        n_eos = 0 if eos is None else 1
+        K = max(2, 1 + n_eos) * nb                                            # beams_to_keep
+        max_len = S0 + T_new
+        fill = (pad or eos) if eos is not None else -1                         # HF's output_fill_value
+        sc_buf = self._scores.get(T_new)
+        if sc_buf is None:
+            sc_buf = self._scores[T_new] = torch.empty(T_new, R, V, dtype=torch.float32, device=dev)
+        cands = self._cands.get(K)
+        if cands is None:
+            cands = self._cands[K] = (torch.empty(R, K, dtype=torch.float32, device=dev), torch.empty(R, K, dtype=torch.float32, device=dev),
+                                      torch.empty(R, K, dtype=torch.int32, device=dev))
+        # initial state (:3290-3320): running scores [0, -1e9, ...] per item, finished scores -1e9, beam indices -1, sequences filled
+        self.seq_buf[:, S0:] = fill
+        self.fin_seq.copy_(self.seq_buf)
+        self.bidx.fill_(-1)
+        self.fin_bidx.fill_(-1)
+        self.run_score.view(Bi, nb).fill_(-1e9)
+        self.run_score.view(Bi, nb)[:, 0] = 0
+        self.fin_score.fill_(-1e9)
+        self.fin_flag.zero_()
+        self.heur.fill_(1)
+        self.ctl.zero_()
+        self.ctl[0] = 1
+        self.kv_row.zero_()
+        self.kv_row[:, :S0] = (torch.arange(R, device=dev, dtype=torch.int32) // nb)[:, None]     # every beam reads its item's prompt row
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self.rng.copy_(torch.tensor([int(seed), 0], dtype=torch.int64))
+        if not do_sample:                                                      # HF applies the warpers in sampling mode only
+            temperature, top_k, top_p = 1.0, 0, 1.0
+        kw = dict(repetition_penalty=float(repetition_penalty or 1.0), temperature=float(temperature or 1.0), top_k=int(top_k or 0),
+                  top_p=float(1.0 if top_p is None else top_p), min_keep=max(2, n_eos + 1), do_sample=bool(do_sample))  # :1299-1305
+        es = early_stopping if early_stopping == "never" else bool(early_stopping)
+
+        def steps():
+            for t in range(T_new):
+                beam_rows(self.lg, nb if t == 0 else 1, R, nb, sc_buf[t], self.seq_buf, S0 + t, rng=self.rng, draw=t, run_score=self.run_score,
+                          cand_key=cands[0], cand_score=cands[1], cand_tok=cands[2], ctl=self.ctl, **kw)
+                beam_update(Bi, nb, V, cands[0], cands[1], cands[2], S0, S0 + t, max_len, eos, float(length_penalty), es, self.seq_buf,
+                            self.fin_seq, self.bidx, self.fin_bidx, self.kv_row, self.run_score, self.fin_score, self.fin_flag, self.heur,
+                            self.tok.view(-1), self.ctl)
+                if t + 1 < T_new:
+                    self.step(S0 + t)
+        if not use_graph:
+            steps()
+        else:
+            key = ("beam", S0, T_new, nb, float(length_penalty), es, eos, pad, tuple(sorted(kw.items())))
+            g = self._graphs.get(key)
+            if g is None:
+                g = torch.cuda.CUDAGraph()
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    with torch.cuda.graph(g, stream=side):
+                        steps()
+                torch.cuda.current_stream().wait_stream(side)
+                self._graphs[key] = g
+            g.replay()
+            self.graph = g
+        self.pos = S0 + T_new
+        n_iter = int(self.ctl[1])
+        nrs = int(num_return_sequences)
+        rows = (torch.arange(Bi, device=dev)[:, None] * nb + torch.arange(nrs, device=dev)[None, :]).reshape(-1)
+        bidx = self.fin_bidx[rows, :T_new]
+        lgen = int((bidx >= 0).sum(1).max()) if T_new > 0 else 0              # :3520, the longest returned hypothesis
+        return (self.fin_seq[rows, :S0 + lgen].clone(), self.fin_score[rows].clone(), sc_buf[:n_iter].clone(), bidx[:, :lgen].long())

@@ -141,7 +141,7 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
 
 
 @torch.no_grad()
-def run_validation(model, data, args, device, max_batches=None):
+def run_validation(model, data, args, device, max_batches=None, num_beams=1):
     """Generation + metrics on the rank's shard (train.py:207-264, evaluate.py:104-154): prompts up to the first <tsep>,
     `generate` of the remaining positions (sampling with the reference's defaults top_k 50 / top_p 0.95 / T 1.0 unless
     args.val_sample is False -> greedy), cut at eos, de-tokenise, de-normalise (dataset.denorm), pad with the last step,
@@ -149,7 +149,9 @@ def run_validation(model, data, args, device, max_batches=None):
 
     Metrics: 'ADE'/'FDE' use the documented [T,D] form of metrics.py:38-55,7-27; 'ADE_as_called' is what the reference's
     drivers log (they pass [1,T,6], so the norm runs over TIME: SURVEY.md §0.1); 'GD' is metrics.py:61-87 on the rotation
-    vectors [T,3] (the reference's own call passes [1,T,6] and raises inside scipy)."""
+    vectors [T,3] (the reference's own call passes [1,T,6] and raises inside scipy).
+
+    num_beams > 1 (eval only): beam search (or beam sampling with the sampling flags) with one returned hypothesis per sample, the best."""
     dims = model.dims
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
@@ -172,8 +174,9 @@ def run_validation(model, data, args, device, max_batches=None):
         batch = data.batch(idx, device, args.max_traj_token)
         prompts, tokens = batch["prompts"], batch["tokens"]
         max_new = tokens.shape[1] - prompts.shape[1]
+        beam = {} if num_beams == 1 else {"num_beams": num_beams}
         out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"], max_length=max_new,
-                             do_sample=sample, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device))
+                             do_sample=sample, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device), **beam)
         gen_ids = out.sequences[:, prompts.shape[1]:]
         # the prompt holds the first step; prepend its six tokens + <tsep> so step 0 is parsed like the rest
         vals, n = T.detokenize_batch(torch.cat([prompts[:, -7:], gen_ids], 1), dims.tok, args.num_steps + 4)
@@ -319,7 +322,7 @@ def evaluate(args, model, data, split="test", device="cuda"):
     norm = getattr(data, "norm", None)
     if norm is not None and norm.mode == "standard" and norm.mean is None:
         norm.load(args.checkpoint_dir)
-    metrics, dump = run_validation(model, data, args, device)
+    metrics, dump = run_validation(model, data, args, device, num_beams=int(getattr(args, "num_beams", 1)))
     rank, world = _rank_world()
     if world > 1:
         parts = [None] * world
@@ -357,6 +360,8 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--val_greedy", dest="val_sample", action="store_false",
                     help="validate with greedy decoding instead of the reference's sampling defaults (model_arch.py:82-88)")
+    ap.add_argument("--num_beams", type=int, default=1,
+                    help="eval mode: beam search with N beams (beam sampling unless --val_greedy); the dump keeps the best hypothesis per image")
     ap.add_argument("--root_dir", default=None, help="EgoScaler data root (pcrgbs/, trajs/ ...: dataset.py:36, dataset_base.py:68-103)")
     ap.add_argument("--data_dir", default=None, help="directory of the split files {train,val,test}.json (dataset.py:37)")
     ap.add_argument("--smooth_traj", action="store_true", help="smoothing_traj on the resampled tracks (dataset.py:39 reads this attribute)")

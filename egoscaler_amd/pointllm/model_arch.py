@@ -144,6 +144,15 @@ class GenerateOutput:
     scores: Tuple[torch.Tensor, ...]
 
 
+@dataclass
+class GenerateBeamOutput:
+    """HF GenerateBeamDecoderOnlyOutput's fields as generate(num_beams > 1, output_scores=True) fills them."""
+    sequences: torch.Tensor
+    sequences_scores: torch.Tensor
+    scores: Tuple[torch.Tensor, ...]
+    beam_indices: torch.Tensor
+
+
 def _install(root: nn.Module, dotted: str, tensor: torch.Tensor, buffer: bool):
     parts = dotted.split(".")
     m = root
@@ -234,6 +243,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         dtype = self.model.embed_tokens.weight.dtype
         dev = self.model.embed_tokens.weight.device
         old = self.engine
+        self.__dict__.pop("_decoders", None)                # decoders hold stacked copies of the old engine's weights
         self.engine = Engine(self.dims, {k: v.data for k, v in tensors.items()}, dev, dtype)
         self.engine.param_ref = dict(self.named_parameters())
         if old is not None:
@@ -460,7 +470,7 @@ class TrajPointLLMForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, point_clouds=None, max_length=20, temperature=1.0, top_k=50,
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
-                 eos_token_id="config", pad_token_id=None, seed=None, **kwargs):
+                 eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -470,8 +480,13 @@ class TrajPointLLMForCausalLM(nn.Module):
         reference model's logits), a draw from the softmax (Gumbel-max on a counter-based generator seeded from torch's CPU generator —
         torch.multinomial's stream cannot be reproduced, so parity is on `.scores` and, with do_sample=False, on the ids), and HF's
         eos rule: `eos_token_id` defaults to the config's (GenerationConfig.from_model_config), finished rows emit `pad_token_id`, and
-        the outputs are cut after the step at which every row has finished.  eos_token_id=None: fixed length, never stops."""
-        from ..decode import Decoder
+        the outputs are cut after the step at which every row has finished.  eos_token_id=None: fixed length, never stops.
+
+        num_beams > 1: HF's beam search (do_sample=False) or beam sampling (do_sample=True), generation/utils.py _beam_search, on the
+        device under one hipGraph (decode.Decoder.beam -> egomi_beam_rows / egomi_beam_update / egomi_attn_decode_rows; each prompt is
+        prefilled once and shared by its beams).  Returns GenerateBeamOutput(sequences [B*nrs, S0+Lgen], sequences_scores [B*nrs], scores
+        (one [B*num_beams, V] per iteration HF runs: processed log-probs), beam_indices [B*nrs, Lgen]).  Golden: tests/golden/beam_search.npz,
+        recorded from HF's own generate."""
         eng = self.engine
         eng.wait_param_updates()                           # the decoder reads the weights outside the engine's forward pass
         dev = eng.device
@@ -479,6 +494,19 @@ class TrajPointLLMForCausalLM(nn.Module):
         if fps_start is None and point_clouds is not None:
             fps_start = torch.randint(0, point_clouds.shape[1], (ids.shape[0],), dtype=torch.long)
         n_ret = int(num_return_sequences)
+        nb = int(num_beams)
+        if nb < 1:
+            raise ValueError(f"`num_beams` has to be a strictly positive integer, but is {num_beams}")
+        if early_stopping not in (True, False, "never"):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {early_stopping}.")
+        if nb > 1:
+            if n_ret > nb:                                 # configuration_utils.py:802
+                raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`.")
+            if isinstance(point_clouds, (list, tuple)):
+                raise NotImplementedError("num_beams > 1 with a list of ragged clouds is not built")
+            return self._generate_beam(ids, attention_mask, point_clouds, fps_start, int(max_length), nb, n_ret, float(length_penalty),
+                                       early_stopping, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id,
+                                       seed, kwargs.get("use_graph", True))
         if n_ret > 1:                                      # HF expands every input n times (generation/utils.py _expand_inputs_for_generation)
             if isinstance(point_clouds, (list, tuple)):
                 raise NotImplementedError("num_return_sequences > 1 with a list of ragged clouds is not built")
@@ -500,16 +528,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         # one Decoder (static KV cache + captured token loops) per geometry, kept while the decoder layers it holds stacked copies of cannot
         # change: frozen-LLM mode, same prepared weights.  run_validation / evaluate (train.py:207-264, evaluate.py:104-154) call generate()
         # once per batch: without this every batch re-allocated the cache and re-captured a graph of (new tokens x ~300) kernels
-        key = (B, S0 + T, eng.prepare_epoch)
-        cache = self.__dict__.setdefault("_decoders", {})
-        reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
-        dec = cache.get(key) if reuse else None
-        if dec is None:
-            dec = Decoder(eng, B, S0 + T)
-            if reuse:
-                while len(cache) >= 2:                     # the full batch and the split's short last one; a cache is 2 * L * B * H * Smax * hd elements
-                    cache.pop(next(iter(cache)))
-                cache[key] = dec
+        dec = self._decoder(B, S0 + T)
         dec.prefill(ids, attention_mask, point_clouds, fps_start, T)
         if not do_sample:                                  # HF applies the warpers (temperature / top-k / top-p) in sampling mode only
             temperature, top_k, top_p = 1.0, 0, 1.0
@@ -522,6 +541,50 @@ class TrajPointLLMForCausalLM(nn.Module):
             stop = int(first.max()) + 1
         sc = sc[:stop].clone()                              # the decoder's buffers are static (and the decoder may be reused by the next call):
         return GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
+
+    def _decoder(self, B, max_len, nb=1):
+        """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER
+        prepare(): load_state_dict() / _apply() leave the engine unprepared (or replace it), and a decoder made before them holds stacked
+        copies of the old weights and the old RoPE tables."""
+        from ..decode import Decoder
+        eng = self.engine
+        if not eng.prepared:
+            eng.prepare()
+        key = (id(eng), eng.prepare_epoch, B, max_len, nb)
+        cache = self.__dict__.setdefault("_decoders", {})
+        reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
+        dec = cache.get(key) if reuse else None
+        if dec is None:
+            dec = Decoder(eng, B * nb, max_len, num_beams=nb)
+            if reuse:
+                while len(cache) >= 2:                     # the full batch and the split's short last one; a cache is 2 * L * B * H * Smax * hd elements
+                    cache.pop(next(iter(cache)))
+                cache[key] = dec
+        return dec
+
+    def _generate_beam(self, ids, attention_mask, point_clouds, fps_start, T, nb, n_ret, length_penalty, early_stopping, do_sample, temperature,
+                       top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph):
+        dev = self.engine.device
+        B, S0 = ids.shape
+        if isinstance(eos_token_id, str):
+            eos_token_id = self.dims.tok.eos
+        if eos_token_id is not None and pad_token_id is None:
+            pad_token_id = self.dims.tok.pad if self.dims.tok.pad is not None else eos_token_id
+        for name, v in (("temperature", temperature), ("repetition_penalty", repetition_penalty)):
+            if v is not None and not float(v) > 0:
+                raise ValueError(f"`{name}` has to be a strictly positive float, but is {v}")
+        if top_p is not None and not (0 < float(top_p) <= 1.0):
+            raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+        dec = self._decoder(B, S0 + T, nb)
+        chunk = 16
+        if B > chunk:
+            dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=chunk, nb=nb)
+        else:
+            dec.prefill(ids, attention_mask, point_clouds, fps_start, T, nb=nb)
+        seq, ss, sc, bidx = dec.beam(T, num_return_sequences=n_ret, length_penalty=length_penalty, early_stopping=early_stopping,
+                                     do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                                     eos=eos_token_id, pad=pad_token_id, seed=seed, use_graph=use_graph)
+        return GenerateBeamOutput(sequences=seq, sequences_scores=ss, scores=tuple(sc[t] for t in range(sc.shape[0])), beam_indices=bidx)
 
     def train(self, mode: bool = True):
         """model_arch.py:110-124: frozen parts stay in eval(); embed_tokens follows `mode`."""

@@ -275,6 +275,36 @@ int egomi_sample_rows(const void* logits, int64_t ld, int B, int V, float* score
                       int pos, int rep_from, int64_t* ids, int* done, float repetition_penalty, float temperature, int top_k,
                       float top_p, int do_sample, const uint64_t* rng, int draw, int64_t eos_id, int64_t pad_id, int dtype,
                       egomi_stream_t stream);
+/* Beam search / beam sampling (num_beams > 1): HF GenerationMixin._beam_search, transformers 5.15 generation/utils.py:3208-3560.
+ * Logical rows r = b * nb + j (item b, beam j), R = B * nb.  Every step is one beam_rows + one beam_update launch; ctl (int32 [6], device)
+ * holds the loop-open flag [0] and the iteration count [1]: once a step closes the loop, both return at once, so T captured steps
+ * replay HF's data-dependent number of iterations.
+ *   beam_rows  : replaces :3347-3385 (log_softmax of fp32 logits, logits_processor on the LOG-PROBS against the row's own sequence
+ *                seq[r, 0:pos], + running_beam_scores) and the per-row half of _get_top_k_continuations :3077.  Row r reads logits row
+ *                r / lg_div (lg_div = nb at step 0: the item's prefill row).  scores[r, :] = the processed row (RepetitionPenalty,
+ *                with do_sample also Temperature -> TopK -> TopP with min_tokens_to_keep, :1299-1305); then acc = scores + run_score[r]
+ *                (+ Gumbel noise of egomi_sample_rows' Philox stream at (rng[0]; row r, token, rng[1] + draw) when sampling: Gumbel-top-K
+ *                is sequential sampling without replacement from softmax(acc), torch.multinomial's role); the row's K largest keys
+ *                (ties -> lower flat index j * V + token) -> cand_key (perturbed), cand_score (acc), cand_tok [R, K].
+ *   beam_update: one workgroup per item: the item's top K of its nb * K candidates (_get_top_k_continuations), stopping marks (eos,
+ *                cur_len + 1 >= max_len), _get_running_beams_for_next_iteration, _update_finished_beams :3153 (length penalty,
+ *                early_stopping 0 False / 1 True / 2 "never"), _check_early_stop_heuristic :3007, _beam_search_has_unfinished_sequences
+ *                :3055.  Gathers the parents of seq / fin_seq [R, ld_seq], beam_idx / fin_beam_idx [R, ld_bidx] (batch-offset, HF's
+ *                beam_indices) and kv_row [R, ld_kv] in place (kv_row[r, cur_len] = r: the row's own physical cache row), writes tok[r],
+ *                run_score, fin_score, fin_flag [R], heur [B].  Ties -> the lower position, as the kernel tests pin.
+ *   attn_decode_rows: attn_decode with key t of logical row r read from physical row kv_row[r, t] of the [n_phys, H, Smax, hd] caches
+ *                (the reorder of the cache by parent beam, :3437-3447, as a table gather: no K/V bytes move); key_mask [R, >= T_len]. */
+int egomi_beam_rows(const void* logits, int64_t ld, int lg_div, int R, int V, int nb, float* scores, int64_t ld_scores, const int64_t* seq,
+                    int64_t ld_seq, int pos, float repetition_penalty, float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                    int do_sample, const uint64_t* rng, int draw, const float* run_score, int K, float* cand_key, float* cand_score,
+                    int32_t* cand_tok, const int32_t* ctl, int dtype, egomi_stream_t stream);
+int egomi_beam_update(int B, int nb, int K, int V, const float* cand_key, const float* cand_score, const int32_t* cand_tok, int S0, int cur_len,
+                      int max_len, int64_t eos_id, float length_penalty, int early_stopping, int64_t* seq, int64_t* fin_seq, int64_t ld_seq,
+                      int32_t* beam_idx, int32_t* fin_beam_idx, int64_t ld_bidx, int32_t* kv_row, int64_t ld_kv, float* run_score,
+                      float* fin_score, int32_t* fin_flag, int32_t* heur, int64_t* tok, int32_t* ctl, egomi_stream_t stream);
+int egomi_attn_decode_rows(const void* q, int64_t ld_q, const void* kcache, const void* vcache, const int32_t* kv_row, int64_t ld_kv,
+                           int n_phys, const uint8_t* key_mask, int64_t ld_mask, void* out, int64_t ld_o, int B, int nb, int H, int hd,
+                           int Smax, int T_len, float scale, int dtype, egomi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * A14  trajectory <-> token ids for whole batches, displacement metrics (integer contracts bit-exact).
