@@ -27,6 +27,32 @@ def attn_decode(q, ld_q, kc, vc, key_mask, out, B, H, hd, Smax, T_len, scale):
          P(out), c_i64(out.stride(0)), c_i(B), c_i(H), c_i(hd), c_i(Smax), c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
 
 
+def kv_append_fp8(k, v, ld, kc, vc, ks, vs, B, Sq, H, hd, Smax, pos0):
+    """kv_append into the fp8 cache: codes kc / vc uint8 [B, H, Smax, hd], scales ks / vs fp32 [B, H, Smax] (include/egomi.h egomi_kv_append_fp8)."""
+    call("egomi_kv_append_fp8", P(k), P(v), c_i64(ld), P(kc), P(vc), P(ks), P(vs), c_i(B), c_i(Sq), c_i(H), c_i(hd), c_i(Smax), c_i(pos0),
+         c_i(dt(k.dtype)), S())
+
+
+def attn_decode_fp8(q, ld_q, kc, vc, ks, vs, key_mask, out, B, H, hd, Smax, T_len, scale):
+    """attn_decode over the fp8 cache (include/egomi.h egomi_attn_decode_fp8)."""
+    call("egomi_attn_decode_fp8", P(q), c_i64(ld_q), P(kc), P(vc), P(ks), P(vs), P(key_mask), c_i64(key_mask.stride(0) if key_mask is not None else 0),
+         P(out), c_i64(out.stride(0)), c_i(B), c_i(H), c_i(hd), c_i(Smax), c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+
+
+def kv8_quantize(x):
+    """The fp8 cache's numerics restated in torch (csrc/kv8.hip header): x [..., hd] -> (codes uint8 [..., hd], scales fp32 [...]),
+    s = amax / 448 (1 where amax == 0), codes = (x / s).to(float8_e4m3fn).  The kernels are bit-equal to it."""
+    x = x.float()
+    s = x.abs().amax(-1) / 448.0
+    s = torch.where(s == 0, torch.ones_like(s), s)
+    return (x / s[..., None]).to(torch.float8_e4m3fn).view(torch.uint8), s
+
+
+def kv8_dequantize(codes, scales):
+    """float(code) * s, fp32."""
+    return codes.view(torch.float8_e4m3fn).float() * scales[..., None]
+
+
 def argmax_rows(logits, ids, seq=None, pos=0):
     B, V = logits.shape
     call("egomi_argmax_rows", P(logits), c_i64(logits.stride(0)), c_i(B), c_i(V), P(ids), P(seq), c_i64(seq.stride(0) if seq is not None else 0),
@@ -68,15 +94,29 @@ def attn_decode_rows(q, ld_q, kc, vc, kv_row, n_phys, key_mask, out, B, nb, H, h
          c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
 
 
+def attn_decode_rows_fp8(q, ld_q, kc, vc, ks, vs, kv_row, n_phys, key_mask, out, B, nb, H, hd, Smax, T_len, scale):
+    """attn_decode_rows over the fp8 cache (include/egomi.h egomi_attn_decode_rows_fp8)."""
+    call("egomi_attn_decode_rows_fp8", P(q), c_i64(ld_q), P(kc), P(vc), P(ks), P(vs), P(kv_row), c_i64(kv_row.stride(0)), c_i(n_phys), P(key_mask),
+         c_i64(key_mask.stride(0) if key_mask is not None else 0), P(out), c_i64(out.stride(0)), c_i(B), c_i(nb), c_i(H), c_i(hd), c_i(Smax),
+         c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+
+
 class Decoder:
-    def __init__(self, engine, B, max_len, num_beams=1):
-        """B = rows of the cache and of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...))."""
-        self.eng, self.B, self.Smax, self.nb = engine, B, max_len, int(num_beams)
+    def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None):
+        """B = rows of the cache and of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...)).
+        kv_dtype="fp8": the KV cache holds e4m3fn codes kc / vc uint8 [L, B, H, Smax, hd] and fp32 scales ks / vs [L, B, H, Smax], one per
+        (layer, row, head, position) and tensor (csrc/kv8.hip); None: the model's dtype, as before."""
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', not {kv_dtype!r}")
+        self.eng, self.B, self.Smax, self.nb, self.kv_dtype = engine, B, max_len, int(num_beams), kv_dtype
         lm = engine.dims.lm
         L, H, hd, d, Fd, V = lm.num_hidden_layers, lm.num_attention_heads, lm.head_dim, lm.hidden_size, lm.intermediate_size, lm.vocab_size
         T, dev = engine.dtype, engine.device
-        self.kc = torch.zeros(L, B, H, max_len, hd, dtype=T, device=dev)
-        self.vc = torch.zeros(L, B, H, max_len, hd, dtype=T, device=dev)
+        self.fp8 = kv_dtype == "fp8"
+        self.kc = torch.zeros(L, B, H, max_len, hd, dtype=torch.uint8 if self.fp8 else T, device=dev)
+        self.vc = torch.zeros_like(self.kc)
+        self.ks = torch.zeros(L, B, H, max_len, dtype=torch.float32, device=dev) if self.fp8 else None
+        self.vs = torch.zeros_like(self.ks) if self.fp8 else None
         z = lambda *s, dtype=T: torch.zeros(*s, dtype=dtype, device=dev)
         self.x, self.h, self.qkv, self.ao, self.x_mid, self.h2 = z(B, d), z(B, d), z(B, 3 * d), z(B, d), z(B, d), z(B, d)
         self.gu, self.act, self.x_out, self.hn, self.lg = z(B, 2 * Fd), z(B, Fd), z(B, d), z(B, d), z(B, V)
@@ -134,9 +174,18 @@ class Decoder:
         self.seq = self.seq_buf[:, :S0 + total_new]
 
     def _sink(self, l, qkv, B, Sq):
+        d = self.eng.dims.lm.hidden_size
+        self._append(l, None, qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), B, Sq, 0)
+
+    def _append(self, l, b, k, v, ld, B, Sq, pos0):
+        """k / v rows -> layer l of the cache (all rows, or row b alone) at positions pos0 .. pos0 + Sq - 1."""
         lm = self.eng.dims.lm
-        H, hd, d = lm.num_attention_heads, lm.head_dim, lm.hidden_size
-        kv_append(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), self.kc[l], self.vc[l], B, Sq, H, hd, self.Smax, 0)
+        H, hd = lm.num_attention_heads, lm.head_dim
+        sel = (l,) if b is None else (l, b)
+        if self.fp8:
+            kv_append_fp8(k, v, ld, self.kc[sel], self.vc[sel], self.ks[sel], self.vs[sel], B, Sq, H, hd, self.Smax, pos0)
+        else:
+            kv_append(k, v, ld, self.kc[sel], self.vc[sel], B, Sq, H, hd, self.Smax, pos0)
 
     def prefill(self, input_ids, attention_mask, point_clouds, fps_start, total_new, nb=1):
         """nb > 1 (beam mode): the B prompts run ONCE each; their K/V land in physical cache rows 0..B-1 and their logits in rows 0..B-1 of
@@ -156,8 +205,7 @@ class Decoder:
         what limits the batch, not the cache) and every chunk appends its K/V rows to its own slice of the static cache."""
         B, S0 = input_ids.shape
         eng, dev = self.eng, self.eng.device
-        lm = eng.dims.lm
-        H, hd, d = lm.num_attention_heads, lm.head_dim, lm.hidden_size
+        d = eng.dims.lm.hidden_size
         mask = torch.ones(B, S0, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
         self._set_inputs(input_ids, mask, total_new, nb)
         for b0 in range(0, B, chunk):
@@ -165,8 +213,7 @@ class Decoder:
 
             def sink(l, qkv, Bc, Sq, b0=b0):
                 for i in range(Bc):               # a batch slice of the [L,B,H,Smax,hd] cache is not contiguous over samples: one append each
-                    kv_append(qkv[i * Sq:(i + 1) * Sq, d:2 * d], qkv[i * Sq:(i + 1) * Sq, 2 * d:], qkv.stride(0), self.kc[l, b0 + i], self.vc[l, b0 + i],
-                              1, Sq, H, hd, self.Smax, 0)
+                    self._append(l, b0 + i, qkv[i * Sq:(i + 1) * Sq, d:2 * d], qkv[i * Sq:(i + 1) * Sq, 2 * d:], qkv.stride(0), 1, Sq, 0)
             pcs = None if point_clouds is None else point_clouds[b0:b1]
             st = None if fps_start is None else fps_start[b0:b1]
             hn = eng.forward_hidden(input_ids[b0:b1], mask[b0:b1], pcs, st, save=False, kv_sink=sink)
@@ -191,12 +238,20 @@ class Decoder:
                 ops.rmsnorm(x, w[p + "input_layernorm.weight"], lm.rms_norm_eps, out=self.h)
             if fq:
                 n = ops.mm_slabs(self.h, self.wqkv[l], self.qkv, self.gws)
-                ops.qkv_finish(self.gws, n, self.qkv, eng.cos, eng.sin, pos, self.kc[l], self.vc[l], B, H, hd, self.Smax)
+                if self.fp8:
+                    ops.qkv_finish_fp8(self.gws, n, self.qkv, eng.cos, eng.sin, pos, self.kc[l], self.vc[l], self.ks[l], self.vs[l], B, H, hd, self.Smax)
+                else:
+                    ops.qkv_finish(self.gws, n, self.qkv, eng.cos, eng.sin, pos, self.kc[l], self.vc[l], B, H, hd, self.Smax)
             else:
                 ops.mm(self.h, self.wqkv[l], out=self.qkv, workspace=self.gws)
                 ops.rope_(self.qkv, eng.cos, eng.sin, B, 1, pos, 2 * H, hd, 3 * d)
-                kv_append(self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, self.kc[l], self.vc[l], B, 1, H, hd, self.Smax, pos)
-            if self.kv_row is None:
+                self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos)
+            if self.fp8 and self.kv_row is None:
+                attn_decode_fp8(self.qkv, 3 * d, self.kc[l], self.vc[l], self.ks[l], self.vs[l], self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
+            elif self.fp8:
+                attn_decode_rows_fp8(self.qkv, 3 * d, self.kc[l], self.vc[l], self.ks[l], self.vs[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd,
+                                     self.Smax, pos + 1, scale)
+            elif self.kv_row is None:
                 attn_decode(self.qkv, 3 * d, self.kc[l], self.vc[l], self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
             else:
                 attn_decode_rows(self.qkv, 3 * d, self.kc[l], self.vc[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd, self.Smax, pos + 1, scale)

@@ -313,6 +313,12 @@ def qkv_finish(workspace, slices, qkv, cos, sin, pos, kc, vc, B, H, hd, Smax):
          c_i(Smax), c_i(dt(qkv.dtype)), S())
 
 
+def qkv_finish_fp8(workspace, slices, qkv, cos, sin, pos, kc, vc, ks, vs, B, H, hd, Smax):
+    """qkv_finish with k / v quantised into the fp8 cache at `pos`: codes kc / vc uint8, scales ks / vs fp32  (egomi_qkv_finish_fp8)."""
+    call("egomi_qkv_finish_fp8", P(workspace), c_i(slices), P(qkv), c_i64(_ld(qkv)), P(cos), P(sin), c_i(pos), P(kc), P(vc), P(ks), P(vs), c_i(B),
+         c_i(H), c_i(hd), c_i(Smax), c_i(dt(qkv.dtype)), S())
+
+
 # ------------------------------------------------------------------------------------------ rows
 def layernorm(x, w, b, eps=1e-5, add=None, sum_out=None, out=None):
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]

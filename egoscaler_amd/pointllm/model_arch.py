@@ -470,7 +470,8 @@ class TrajPointLLMForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, point_clouds=None, max_length=20, temperature=1.0, top_k=50,
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
-                 eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, **kwargs):
+                 eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
+                 **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -486,7 +487,14 @@ class TrajPointLLMForCausalLM(nn.Module):
         device under one hipGraph (decode.Decoder.beam -> egomi_beam_rows / egomi_beam_update / egomi_attn_decode_rows; each prompt is
         prefilled once and shared by its beams).  Returns GenerateBeamOutput(sequences [B*nrs, S0+Lgen], sequences_scores [B*nrs], scores
         (one [B*num_beams, V] per iteration HF runs: processed log-probs), beam_indices [B*nrs, Lgen]).  Golden: tests/golden/beam_search.npz,
-        recorded from HF's own generate."""
+        recorded from HF's own generate.
+
+        kv_cache_dtype: None or "auto" = a KV cache in the model's dtype; "fp8" = OCP e4m3fn codes with one fp32 scale per (layer, row,
+        head, position) and tensor, s = amax / 448 (decode.Decoder(kv_dtype="fp8"), csrc/kv8.hip): half the cache bytes of bf16, and of what
+        every decode step's attention streams.  Applies to every mode; the prefill logits (step 0) never read the cache."""
+        if kv_cache_dtype not in (None, "auto", "fp8"):
+            raise ValueError(f"`kv_cache_dtype` must be None, 'auto' or 'fp8', but is {kv_cache_dtype!r}")
+        kv = "fp8" if kv_cache_dtype == "fp8" else None
         eng = self.engine
         eng.wait_param_updates()                           # the decoder reads the weights outside the engine's forward pass
         dev = eng.device
@@ -506,7 +514,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                 raise NotImplementedError("num_beams > 1 with a list of ragged clouds is not built")
             return self._generate_beam(ids, attention_mask, point_clouds, fps_start, int(max_length), nb, n_ret, float(length_penalty),
                                        early_stopping, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id,
-                                       seed, kwargs.get("use_graph", True))
+                                       seed, kwargs.get("use_graph", True), kv)
         if n_ret > 1:                                      # HF expands every input n times (generation/utils.py _expand_inputs_for_generation)
             if isinstance(point_clouds, (list, tuple)):
                 raise NotImplementedError("num_return_sequences > 1 with a list of ragged clouds is not built")
@@ -528,7 +536,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         # one Decoder (static KV cache + captured token loops) per geometry, kept while the decoder layers it holds stacked copies of cannot
         # change: frozen-LLM mode, same prepared weights.  run_validation / evaluate (train.py:207-264, evaluate.py:104-154) call generate()
         # once per batch: without this every batch re-allocated the cache and re-captured a graph of (new tokens x ~300) kernels
-        dec = self._decoder(B, S0 + T)
+        dec = self._decoder(B, S0 + T, kv=kv)
         dec.prefill(ids, attention_mask, point_clouds, fps_start, T)
         if not do_sample:                                  # HF applies the warpers (temperature / top-k / top-p) in sampling mode only
             temperature, top_k, top_p = 1.0, 0, 1.0
@@ -542,20 +550,20 @@ class TrajPointLLMForCausalLM(nn.Module):
         sc = sc[:stop].clone()                              # the decoder's buffers are static (and the decoder may be reused by the next call):
         return GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
 
-    def _decoder(self, B, max_len, nb=1):
+    def _decoder(self, B, max_len, nb=1, kv=None):
         """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER
         prepare(): load_state_dict() / _apply() leave the engine unprepared (or replace it), and a decoder made before them holds stacked
-        copies of the old weights and the old RoPE tables."""
+        copies of the old weights and the old RoPE tables.  It also holds the KV dtype: a bf16 and an fp8 decoder never stand in for each other."""
         from ..decode import Decoder
         eng = self.engine
         if not eng.prepared:
             eng.prepare()
-        key = (id(eng), eng.prepare_epoch, B, max_len, nb)
+        key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv)
         cache = self.__dict__.setdefault("_decoders", {})
         reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
         dec = cache.get(key) if reuse else None
         if dec is None:
-            dec = Decoder(eng, B * nb, max_len, num_beams=nb)
+            dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv)
             if reuse:
                 while len(cache) >= 2:                     # the full batch and the split's short last one; a cache is 2 * L * B * H * Smax * hd elements
                     cache.pop(next(iter(cache)))
@@ -563,7 +571,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         return dec
 
     def _generate_beam(self, ids, attention_mask, point_clouds, fps_start, T, nb, n_ret, length_penalty, early_stopping, do_sample, temperature,
-                       top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph):
+                       top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph, kv=None):
         dev = self.engine.device
         B, S0 = ids.shape
         if isinstance(eos_token_id, str):
@@ -575,7 +583,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                 raise ValueError(f"`{name}` has to be a strictly positive float, but is {v}")
         if top_p is not None and not (0 < float(top_p) <= 1.0):
             raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
-        dec = self._decoder(B, S0 + T, nb)
+        dec = self._decoder(B, S0 + T, nb, kv=kv)
         chunk = 16
         if B > chunk:
             dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=chunk, nb=nb)

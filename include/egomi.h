@@ -306,6 +306,27 @@ int egomi_attn_decode_rows(const void* q, int64_t ld_q, const void* kcache, cons
                            int n_phys, const uint8_t* key_mask, int64_t ld_mask, void* out, int64_t ld_o, int B, int nb, int H, int hd,
                            int Smax, int T_len, float scale, int dtype, egomi_stream_t stream);
 
+/* FP8 (OCP e4m3fn) KV cache (csrc/kv8.hip): codes uint8 [B, H, Smax, hd] per layer (the bf16 cache's layout), scales fp32 [B, H, Smax]
+ * per layer; hd in {32, 64, 128} (EGOMI_E_UNSUPPORTED otherwise); codes 8-B (attention: 16-B) aligned, scales 4-B aligned.  Per (row, head, position)
+ * and tensor: s = amax / 448 (1 when amax == 0), code = e4m3fn_rne(x / s), value = float(code) * s, x being what the bf16 / fp32
+ * kernel below would have stored (bit-equal to torch's (x / s).to(torch.float8_e4m3fn); see the header of csrc/kv8.hip).
+ *   kv_append_fp8       : egomi_kv_append into the fp8 cache
+ *   qkv_finish_fp8      : egomi_qkv_finish with k, v quantised into the fp8 cache at pos (q -> qkv bit-equal to egomi_qkv_finish)
+ *   attn_decode_fp8     : egomi_attn_decode over the fp8 cache (a masked or out-of-range key is selected away, never read as 0 * code)
+ *   attn_decode_rows_fp8: egomi_attn_decode_rows over the fp8 cache (kv_row entries outside [0, n_phys) are masked keys) */
+int egomi_kv_append_fp8(const void* k, const void* v, int64_t ld, uint8_t* kcodes, uint8_t* vcodes, float* kscale, float* vscale, int B, int S,
+                        int H, int hd, int Smax, int pos0, int dtype, egomi_stream_t stream);
+int egomi_qkv_finish_fp8(const float* slabs, int slices, void* qkv, int64_t ld, const float* cos_tab, const float* sin_tab, int pos,
+                         uint8_t* kcodes, uint8_t* vcodes, float* kscale, float* vscale, int B, int H, int hd, int Smax, int dtype,
+                         egomi_stream_t stream);
+int egomi_attn_decode_fp8(const void* q, int64_t ld_q, const uint8_t* kcodes, const uint8_t* vcodes, const float* kscale, const float* vscale,
+                          const uint8_t* key_mask, int64_t ld_mask, void* out, int64_t ld_o, int B, int H, int hd, int Smax, int T_len,
+                          float scale, int dtype, egomi_stream_t stream);
+int egomi_attn_decode_rows_fp8(const void* q, int64_t ld_q, const uint8_t* kcodes, const uint8_t* vcodes, const float* kscale,
+                               const float* vscale, const int32_t* kv_row, int64_t ld_kv, int n_phys, const uint8_t* key_mask,
+                               int64_t ld_mask, void* out, int64_t ld_o, int B, int nb, int H, int hd, int Smax, int T_len, float scale,
+                               int dtype, egomi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * A14  trajectory <-> token ids for whole batches, displacement metrics (integer contracts bit-exact).
  * replaces models/pointllm/utils/utils.py:13-21 (discretize_action / token_to_action), :47-104
