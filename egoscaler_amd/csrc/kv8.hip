@@ -11,35 +11,15 @@
 //   code_j = e4m3fn_rne(x_j / s)  (IEEE division; no reciprocal-multiply)
 //   value  = float(code_j) * s
 // e4m3fn_rne is torch's float -> float8_e4m3fn conversion (round to nearest even, |y| >= 480 and NaN -> 0x7F | sign), written out in
-// software below so that the codes are bit-equal to torch's `(x / s[..., None]).to(torch.float8_e4m3fn)`.  Decoding uses the hardware
+// software (fp8.h, shared with w8.hip) so that the codes are bit-equal to torch's `(x / s[..., None]).to(torch.float8_e4m3fn)`.  Decoding uses the hardware
 // v_cvt_pk_f32_fp8 (OCP on gfx950), which is exact for every finite code.
 //
 // Decode attention: score_t = (sum_j code_j * q_j * scale) * s_k[t]; acc += (p_t * s_v[t]) * code, with attn_decode's online softmax
 // and wave combine.  A masked or out-of-range key never reaches the accumulators through a multiplication by p = 0: its code words and
 // its p * s_v are SELECTED to zero (unwritten cache bytes may hold NaN codes 0x7F / 0xFF and NaN scales, and NaN * 0 is NaN).
 #include "common.h"
+#include "fp8.h"
 #include <math.h>
-
-// torch c10 fp8e4m3fn_from_fp32_value: RNE, no saturation (|y| >= 480 -> NaN 0x7F), sign kept (-0 -> 0x80)
-__device__ __forceinline__ uint32_t e4m3fn_rne(float f) {
-    uint32_t b = __float_as_uint(f);
-    const uint32_t sign = b & 0x80000000u;
-    b ^= sign;
-    uint32_t r;
-    if (b >= (1087u << 20)) {
-        r = 0x7Fu;
-    } else if (b < (121u << 23)) {                                   // below the smallest normal: the magic-add of c10
-        r = __float_as_uint(__uint_as_float(b) + __uint_as_float(141u << 23)) - (141u << 23);
-    } else {
-        r = (b + (uint32_t)(-(120 << 23)) + 0x7FFFFu + ((b >> 20) & 1u)) >> 20;
-    }
-    return (r | (sign >> 24)) & 0xFFu;
-}
-
-__device__ __forceinline__ float kv8_scale(float amax) {
-#pragma clang fp contract(off)
-    return amax == 0.f ? 1.0f : amax / 448.0f;
-}
 
 // 8 values -> 8 codes (little-endian: element j in byte j)
 __device__ __forceinline__ u32x2 kv8_encode8(const float (&x)[8], float s) {
@@ -48,13 +28,6 @@ __device__ __forceinline__ u32x2 kv8_encode8(const float (&x)[8], float s) {
     w[0] = e4m3fn_rne(x[0] / s) | (e4m3fn_rne(x[1] / s) << 8) | (e4m3fn_rne(x[2] / s) << 16) | (e4m3fn_rne(x[3] / s) << 24);
     w[1] = e4m3fn_rne(x[4] / s) | (e4m3fn_rne(x[5] / s) << 8) | (e4m3fn_rne(x[6] / s) << 16) | (e4m3fn_rne(x[7] / s) << 24);
     return w;
-}
-
-// 4 codes in one word -> 4 floats (exact)
-__device__ __forceinline__ void kv8_decode4(uint32_t w, float* o) {
-    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-    const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-    o[0] = lo[0]; o[1] = lo[1]; o[2] = hi[0]; o[3] = hi[1];
 }
 
 // max over the G consecutive lanes of an aligned group (G a power of two <= 64)
@@ -87,7 +60,7 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(const T* k, const T*
         float ak = 0.f, av = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) { ak = fmaxf(ak, fabsf(xk[j])); av = fmaxf(av, fabsf(xv[j])); }
-        const float sk = kv8_scale(group_max<CPR>(ak)), sv = kv8_scale(group_max<CPR>(av));
+        const float sk = e4m3fn_scale(group_max<CPR>(ak)), sv = e4m3fn_scale(group_max<CPR>(av));
         *reinterpret_cast<u32x2*>(kc + slot * HD + c * 8) = kv8_encode8(xk, sk);
         *reinterpret_cast<u32x2*>(vc + slot * HD + c * 8) = kv8_encode8(xv, sv);
         if (c == 0) { ks[slot] = sk; vs[slot] = sv; }
@@ -177,7 +150,7 @@ __global__ __launch_bounds__(256) void qkv_finish_fp8_kernel(const float* slabs,
         float am = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) am = fmaxf(am, fmaxf(fabsf(oa[j]), fabsf(ob[j])));
-        const float s = kv8_scale(group_max<CPV>(am));
+        const float s = e4m3fn_scale(group_max<CPV>(am));
         if (part > 0) {
             const long long slot = (b * H + h) * Smax + pos;
             uint8_t* dst = (part == 1 ? kc : vc) + slot * HD + i;
@@ -289,7 +262,7 @@ __global__ __launch_bounds__(256) void attn_decode_fp8_kernel(const T* q, long l
 #pragma unroll
             for (int c = 0; c < NW; ++c) {
                 float x[4];
-                kv8_decode4(ok[u] ? kw[u][c] : 0u, x);                 // select, never multiply a NaN code by zero
+                e4m3fn_decode4(ok[u] ? kw[u][c] : 0u, x);                 // select, never multiply a NaN code by zero
 #pragma unroll
                 for (int j = 0; j < 4; ++j) dot += x[j] * qv[c * 4 + j];
             }
@@ -314,8 +287,8 @@ __global__ __launch_bounds__(256) void attn_decode_fp8_kernel(const T* q, long l
 #pragma unroll
         for (int c = 0; c < NW; ++c) {
             float x0[4], x1[4];
-            kv8_decode4(ok[0] ? vw[0][c] : 0u, x0);
-            kv8_decode4(ok[1] ? vw[1][c] : 0u, x1);
+            e4m3fn_decode4(ok[0] ? vw[0][c] : 0u, x0);
+            e4m3fn_decode4(ok[1] ? vw[1][c] : 0u, x1);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[c * 4 + j] = acc[c * 4 + j] * alpha + pv0 * x0[j] + pv1 * x1[j];
         }

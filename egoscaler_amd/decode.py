@@ -53,6 +53,15 @@ def kv8_dequantize(codes, scales):
     return codes.view(torch.float8_e4m3fn).float() * scales[..., None]
 
 
+def w8_quantize(w):
+    """The fp8 decode weights' numerics restated in torch (csrc/w8.hip header): rows w [N, K] -> (codes uint8 [N, K], scales fp32 [N]),
+    s_n = amax_n / 448 (1 where amax == 0), codes = (w.float() / s[:, None]).to(float8_e4m3fn).  egomi_quantize_rows_fp8 is bit-equal to it."""
+    w = w.float()
+    s = w.abs().amax(1) / 448.0
+    s = torch.where(s == 0, torch.ones_like(s), s)
+    return (w / s[:, None]).to(torch.float8_e4m3fn).view(torch.uint8), s
+
+
 def argmax_rows(logits, ids, seq=None, pos=0):
     B, V = logits.shape
     call("egomi_argmax_rows", P(logits), c_i64(logits.stride(0)), c_i(B), c_i(V), P(ids), P(seq), c_i64(seq.stride(0) if seq is not None else 0),
@@ -102,12 +111,21 @@ def attn_decode_rows_fp8(q, ld_q, kc, vc, ks, vs, kv_row, n_phys, key_mask, out,
 
 
 class Decoder:
-    def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None):
+    def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None, weight_dtype=None):
         """B = rows of the cache and of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...)).
         kv_dtype="fp8": the KV cache holds e4m3fn codes kc / vc uint8 [L, B, H, Smax, hd] and fp32 scales ks / vs [L, B, H, Smax], one per
-        (layer, row, head, position) and tensor (csrc/kv8.hip); None: the model's dtype, as before."""
+        (layer, row, head, position) and tensor (csrc/kv8.hip); None: the model's dtype, as before.
+        weight_dtype="fp8": step() runs the four projections of every layer (q|k|v, o_proj, gate|up, down_proj) on e4m3fn codes with one fp32
+        scale per output row (W8A16, csrc/w8.hip; self.w8); lm_head, the embeddings and the norms keep the model's dtype, and prefill runs
+        on the bf16 weights.  bf16 engines and B <= 512 only; None: the model's weights, as before."""
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', not {kv_dtype!r}")
+        if weight_dtype not in (None, "fp8"):
+            raise ValueError(f"weight_dtype must be None or 'fp8', not {weight_dtype!r}")
+        if weight_dtype == "fp8" and engine.dtype != torch.bfloat16:
+            raise ValueError(f"fp8 decode weights need a bf16 model, not {engine.dtype}")
+        if weight_dtype == "fp8" and B > 512:
+            raise ValueError(f"fp8 decode weights support at most 512 decoder rows, not {B}")
         self.eng, self.B, self.Smax, self.nb, self.kv_dtype = engine, B, max_len, int(num_beams), kv_dtype
         lm = engine.dims.lm
         L, H, hd, d, Fd, V = lm.num_hidden_layers, lm.num_attention_heads, lm.head_dim, lm.hidden_size, lm.intermediate_size, lm.vocab_size
@@ -150,10 +168,40 @@ class Decoder:
         # round trip of each product through HBM fewer per layer.  Slice counts are the library's plan for these shapes (0 =
         # it would not split: that projection keeps the plain path).  EGOMI_DECODE_FUSED=0 switches the whole thing off (A/B).
         self.fused = {"qkv": 0, "o": 0, "down": 0}
-        if T == torch.bfloat16 and os.environ.get("EGOMI_DECODE_FUSED", "1") != "0" and B <= 512:
+        self.w8 = None
+        if weight_dtype == "fp8":                           # the fp8 products always leave slabs: their only path
+            self.w8 = self._fp8_weights()
+            q = self.w8[0]
+            self.fused = {"qkv": ops.mm_w8_slabs(self.h, *q["qkv"], self.gws, count_only=True),
+                          "o": ops.mm_w8_slabs(self.ao, *q["o"], self.gws, count_only=True),
+                          "down": ops.mm_w8_slabs(self.act, *q["down"], self.gws, count_only=True)}
+            if not all(self.fused.values()):
+                raise ValueError(f"fp8 decode weights cannot run this model's projection shapes ({self.fused})")
+        elif T == torch.bfloat16 and os.environ.get("EGOMI_DECODE_FUSED", "1") != "0" and B <= 512:
             self.fused["qkv"] = ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
             self.fused["o"] = ops.mm_slabs(self.ao, w["model.layers.0.self_attn.o_proj.weight"], self.x_mid, self.gws, count_only=True)
             self.fused["down"] = ops.mm_slabs(self.act, w["model.layers.0.mlp.down_proj.weight"], self.x, self.gws, count_only=True)
+
+    def _fp8_weights(self):
+        """Per layer {"qkv", "o", "gu", "down": (codes uint8 [N, K], scales fp32 [N])} of the stacked forms step() multiplies ([Wq;Wk;Wv],
+        [Wgate;Wup] in its interleaved-32 order when engine.gu_il).  Frozen layers: one copy per engine and prepare_epoch, shared by every
+        decoder (Engine.prepared = False drops it); trainable layers change under every optimizer step, so each decoder quantizes afresh."""
+        eng = self.eng
+        if eng.w8 is not None and eng.w8[0] == eng.prepare_epoch and not eng.any_layer_trainable:
+            return eng.w8[1]
+        w = eng.w
+        q = [{"qkv": ops.quantize_rows_fp8(self.wqkv[l]), "o": ops.quantize_rows_fp8(w[f"model.layers.{l}.self_attn.o_proj.weight"]),
+              "gu": ops.quantize_rows_fp8(self.wgu[l]), "down": ops.quantize_rows_fp8(w[f"model.layers.{l}.mlp.down_proj.weight"])}
+             for l in range(len(self.wqkv))]
+        if not eng.any_layer_trainable:
+            eng.w8 = (eng.prepare_epoch, q)
+        return q
+
+    def _slabs(self, l, name, a, out_like, weight):
+        """The split-K slabs of one projection (fp8 or model-dtype weights) at the start of self.gws; -> their number."""
+        if self.w8 is not None:
+            return ops.mm_w8_slabs(a, *self.w8[l][name], self.gws)
+        return ops.mm_slabs(a, weight, out_like, self.gws)
 
     # -- prefill -------------------------------------------------------------------------------------
     def _set_inputs(self, input_ids, mask, total_new, nb=1):
@@ -237,7 +285,7 @@ class Decoder:
             if not normed:
                 ops.rmsnorm(x, w[p + "input_layernorm.weight"], lm.rms_norm_eps, out=self.h)
             if fq:
-                n = ops.mm_slabs(self.h, self.wqkv[l], self.qkv, self.gws)
+                n = self._slabs(l, "qkv", self.h, self.qkv, self.wqkv[l])
                 if self.fp8:
                     ops.qkv_finish_fp8(self.gws, n, self.qkv, eng.cos, eng.sin, pos, self.kc[l], self.vc[l], self.ks[l], self.vs[l], B, H, hd, self.Smax)
                 else:
@@ -256,18 +304,21 @@ class Decoder:
             else:
                 attn_decode_rows(self.qkv, 3 * d, self.kc[l], self.vc[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd, self.Smax, pos + 1, scale)
             if fo:
-                n = ops.mm_slabs(self.ao, w[p + "self_attn.o_proj.weight"], self.x_mid, self.gws)
+                n = self._slabs(l, "o", self.ao, self.x_mid, w[p + "self_attn.o_proj.weight"])
                 ops.slabs_rmsnorm(self.gws, n, x, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, self.x_mid, self.h2)
             else:
                 ops.mm(self.ao, w[p + "self_attn.o_proj.weight"], out=self.x_mid, residual=x, workspace=self.gws)
                 ops.rmsnorm(self.x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, out=self.h2)
-            ops.mm(self.h2, self.wgu[l], out=self.gu, workspace=self.gws)
+            if self.w8 is not None:
+                ops.mm_w8(self.h2, *self.w8[l]["gu"], out=self.gu, workspace=self.gws)
+            else:
+                ops.mm(self.h2, self.wgu[l], out=self.gu, workspace=self.gws)
             if eng.gu_il:
                 ops.swiglu_il(self.gu, self.act)
             else:
                 ops.swiglu(self.gu[:, :Fd], self.gu[:, Fd:], self.act)
             if fd:                                          # x is not an input of this product: the tail writes the new residual stream into it
-                n = ops.mm_slabs(self.act, w[p + "mlp.down_proj.weight"], x, self.gws)
+                n = self._slabs(l, "down", self.act, x, w[p + "mlp.down_proj.weight"])
                 last = l + 1 == L
                 ops.slabs_rmsnorm(self.gws, n, self.x_mid, w["model.norm.weight"] if last else w[f"model.layers.{l + 1}.input_layernorm.weight"],
                                   lm.rms_norm_eps, x, self.hn if last else self.h)

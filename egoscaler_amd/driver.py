@@ -177,7 +177,8 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1):
         beam = {} if num_beams == 1 else {"num_beams": num_beams}
         out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"], max_length=max_new,
                              do_sample=sample, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device),
-                             kv_cache_dtype=getattr(args, "kv_cache_dtype", None), **beam)
+                             kv_cache_dtype=getattr(args, "kv_cache_dtype", None),
+                             decode_weight_dtype=getattr(args, "decode_weight_dtype", None), **beam)
         gen_ids = out.sequences[:, prompts.shape[1]:]
         # the prompt holds the first step; prepend its six tokens + <tsep> so step 0 is parsed like the rest
         vals, n = T.detokenize_batch(torch.cat([prompts[:, -7:], gen_ids], 1), dims.tok, args.num_steps + 4)
@@ -365,6 +366,9 @@ def parse_args(argv=None):
                     help="eval mode: beam search with N beams (beam sampling unless --val_greedy); the dump keeps the best hypothesis per image")
     ap.add_argument("--kv_cache_dtype", default="auto", choices=["auto", "fp8"],
                     help="KV cache of every generate() call in validation / eval: the model's dtype (auto) or e4m3fn codes with per-(token, head) scales")
+    ap.add_argument("--decode_weight_dtype", default="auto", choices=["auto", "fp8"],
+                    help="weights of the decode-step projections of every generate() call in validation / eval: the model's (auto) or "
+                         "e4m3fn codes with per-output-row scales (bf16 models; prefill stays bf16)")
     ap.add_argument("--root_dir", default=None, help="EgoScaler data root (pcrgbs/, trajs/ ...: dataset.py:36, dataset_base.py:68-103)")
     ap.add_argument("--data_dir", default=None, help="directory of the split files {train,val,test}.json (dataset.py:37)")
     ap.add_argument("--smooth_traj", action="store_true", help="smoothing_traj on the resampled tracks (dataset.py:39 reads this attribute)")

@@ -46,6 +46,7 @@ class Engine:
     def __init__(self, dims: EgoDims, params: Dict[str, torch.Tensor], device, dtype):
         self.dims, self.w, self.device, self.dtype = dims, params, device, dtype
         self.ws = Workspace(device)
+        self.w8 = None                 # (prepare_epoch, fp8 codes / scales of the decode projections): decode.Decoder(weight_dtype="fp8")
         self.prepared = False
         self.prepare_epoch = 0         # bumped by prepare(): holders of derived weight copies (decode.Decoder caches) key on it
         self.lm_wT, self.lm_wT_stale, self.lm_wT_ver = None, True, None     # padded transpose of lm_head for its dgrad (backward_logits)
@@ -170,6 +171,16 @@ class Engine:
         f["c4_w"] = w[pre + "second_conv.3.weight"].squeeze(-1).contiguous()
         self.folded = f
         self.fold_stale = False
+
+    @property
+    def prepared(self):
+        return self._prepared
+
+    @prepared.setter
+    def prepared(self, v):
+        self._prepared = v
+        if not v:
+            self.w8 = None             # every path that marks the weights stale drops the fp8 copies derived from them
 
     def prepare(self):
         """One-time derived weights: BatchNorm fold (fold_batchnorm), resident transposes / stacks of the decoder weights, RoPE tables."""

@@ -319,6 +319,50 @@ def qkv_finish_fp8(workspace, slices, qkv, cos, sin, pos, kc, vc, ks, vs, B, H, 
          c_i(H), c_i(hd), c_i(Smax), c_i(dt(qkv.dtype)), S())
 
 
+# ------------------------------------------------------------------------------------------ fp8 weights (decode projections)
+def quantize_rows_fp8(w):
+    """bf16 rows w [N, K] -> (codes uint8 [N, K], scales fp32 [N]): s_n = amax_n / 448 (1 where amax == 0), codes = e4m3fn(w / s_n)
+    (egomi_quantize_rows_fp8; bit-equal to decode.kv8_quantize applied row-wise)."""
+    if w.dtype != torch.bfloat16:
+        raise TypeError("quantize_rows_fp8 takes bf16 rows")
+    N, K = w.shape
+    codes = torch.empty(N, K, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, dtype=torch.float32, device=w.device)
+    call("egomi_quantize_rows_fp8", P(w), c_i64(_ld(w)), c_i(N), c_i(K), P(codes), c_i64(K), P(scales), S())
+    return codes, scales
+
+
+def _w8(x, codes, scales, out, residual, workspace, epilogue):
+    M, K = x.shape
+    N = codes.shape[0]
+    if x.dtype != torch.bfloat16 or codes.dtype != torch.uint8 or scales.dtype != torch.float32 or codes.shape[1] != K or scales.shape != (N,):
+        raise TypeError("mm_w8: x bf16 [M, K], codes uint8 [N, K], scales fp32 [N]")
+    call("egomi_gemm_w8", P(x), c_i64(_ld(x)), P(codes), c_i64(_ld(codes)), P(scales), P(out), c_i64(_ld(out) if out is not None else 0),
+         P(residual), c_i64(_ld(residual) if residual is not None else 0), c_i(M), c_i(N), c_i(K), c_i(epilogue), P(workspace),
+         c_i64(workspace.numel() * workspace.element_size() if workspace is not None else 0), S())
+
+
+def mm_w8(x, codes, scales, out=None, residual=None, workspace=None):
+    """out = bf16(x . (codes * scales[:, None])^T (+ residual)): x bf16 [M, K] with M <= 512, fp8 weights from quantize_rows_fp8
+    (egomi_gemm_w8, EGOMI_EPI_NONE; `workspace` lets the library split K)."""
+    if out is None:
+        out = torch.empty(x.shape[0], codes.shape[0], dtype=torch.bfloat16, device=x.device)
+    _w8(x, codes, scales, out, residual, workspace, 0)
+    return out
+
+
+def mm_w8_slabs(x, codes, scales, workspace, count_only=False):
+    """x . (codes * scales[:, None])^T as UNSUMMED fp32 K-slice slabs [slices, M, N] at the start of `workspace` (egomi_gemm_w8,
+    EGOMI_EPI_SLABS); returns the number of slices (count_only: without launching; 0 = the library cannot run this shape)."""
+    M, K = x.shape
+    N = codes.shape[0]
+    n = _lib.lib().egomi_gemm_w8_slab_count(c_i(M), c_i(N), c_i(K), c_i64(workspace.numel() * workspace.element_size()))
+    if count_only:
+        return n
+    _w8(x, codes, scales, None, None, workspace, 2)
+    return n
+
+
 # ------------------------------------------------------------------------------------------ rows
 def layernorm(x, w, b, eps=1e-5, add=None, sum_out=None, out=None):
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]

@@ -471,7 +471,7 @@ class TrajPointLLMForCausalLM(nn.Module):
     def generate(self, input_ids=None, attention_mask=None, point_clouds=None, max_length=20, temperature=1.0, top_k=50,
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
                  eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
-                 **kwargs):
+                 decode_weight_dtype=None, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -491,10 +491,20 @@ class TrajPointLLMForCausalLM(nn.Module):
 
         kv_cache_dtype: None or "auto" = a KV cache in the model's dtype; "fp8" = OCP e4m3fn codes with one fp32 scale per (layer, row,
         head, position) and tensor, s = amax / 448 (decode.Decoder(kv_dtype="fp8"), csrc/kv8.hip): half the cache bytes of bf16, and of what
-        every decode step's attention streams.  Applies to every mode; the prefill logits (step 0) never read the cache."""
+        every decode step's attention streams.  Applies to every mode; the prefill logits (step 0) never read the cache.
+
+        decode_weight_dtype: None or "auto" = the decode steps multiply the model's weights; "fp8" = the four projections of every decoder
+        layer (q|k|v, o_proj, gate|up, down_proj) run on OCP e4m3fn codes with one fp32 scale per output row, s = amax / 448, W8A16
+        (decode.Decoder(weight_dtype="fp8"), csrc/w8.hip): half the weight bytes every decode step streams.  lm_head, the embeddings and the
+        norms keep the model's dtype.  Applies to every mode and either kv_cache_dtype; bf16 models with at most 512 decoder rows
+        (batch x num_beams) only.  The prefill runs on the bf16 weights, so the prefill logits (step 0) are those of the bf16 run; only
+        the later steps read the fp8 weights."""
         if kv_cache_dtype not in (None, "auto", "fp8"):
             raise ValueError(f"`kv_cache_dtype` must be None, 'auto' or 'fp8', but is {kv_cache_dtype!r}")
         kv = "fp8" if kv_cache_dtype == "fp8" else None
+        if decode_weight_dtype not in (None, "auto", "fp8"):
+            raise ValueError(f"`decode_weight_dtype` must be None, 'auto' or 'fp8', but is {decode_weight_dtype!r}")
+        wd = "fp8" if decode_weight_dtype == "fp8" else None
         eng = self.engine
         eng.wait_param_updates()                           # the decoder reads the weights outside the engine's forward pass
         dev = eng.device
@@ -514,7 +524,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                 raise NotImplementedError("num_beams > 1 with a list of ragged clouds is not built")
             return self._generate_beam(ids, attention_mask, point_clouds, fps_start, int(max_length), nb, n_ret, float(length_penalty),
                                        early_stopping, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id,
-                                       seed, kwargs.get("use_graph", True), kv)
+                                       seed, kwargs.get("use_graph", True), kv, wd)
         if n_ret > 1:                                      # HF expands every input n times (generation/utils.py _expand_inputs_for_generation)
             if isinstance(point_clouds, (list, tuple)):
                 raise NotImplementedError("num_return_sequences > 1 with a list of ragged clouds is not built")
@@ -536,7 +546,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         # one Decoder (static KV cache + captured token loops) per geometry, kept while the decoder layers it holds stacked copies of cannot
         # change: frozen-LLM mode, same prepared weights.  run_validation / evaluate (train.py:207-264, evaluate.py:104-154) call generate()
         # once per batch: without this every batch re-allocated the cache and re-captured a graph of (new tokens x ~300) kernels
-        dec = self._decoder(B, S0 + T, kv=kv)
+        dec = self._decoder(B, S0 + T, kv=kv, wd=wd)
         dec.prefill(ids, attention_mask, point_clouds, fps_start, T)
         if not do_sample:                                  # HF applies the warpers (temperature / top-k / top-p) in sampling mode only
             temperature, top_k, top_p = 1.0, 0, 1.0
@@ -550,20 +560,21 @@ class TrajPointLLMForCausalLM(nn.Module):
         sc = sc[:stop].clone()                              # the decoder's buffers are static (and the decoder may be reused by the next call):
         return GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
 
-    def _decoder(self, B, max_len, nb=1, kv=None):
+    def _decoder(self, B, max_len, nb=1, kv=None, wd=None):
         """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER
         prepare(): load_state_dict() / _apply() leave the engine unprepared (or replace it), and a decoder made before them holds stacked
-        copies of the old weights and the old RoPE tables.  It also holds the KV dtype: a bf16 and an fp8 decoder never stand in for each other."""
+        copies of the old weights and the old RoPE tables.  It also holds the KV dtype and the decode weight dtype: a bf16 and an fp8 decoder never
+        stand in for each other."""
         from ..decode import Decoder
         eng = self.engine
         if not eng.prepared:
             eng.prepare()
-        key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv)
+        key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv, wd)
         cache = self.__dict__.setdefault("_decoders", {})
         reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
         dec = cache.get(key) if reuse else None
         if dec is None:
-            dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv)
+            dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv, weight_dtype=wd)
             if reuse:
                 while len(cache) >= 2:                     # the full batch and the split's short last one; a cache is 2 * L * B * H * Smax * hd elements
                     cache.pop(next(iter(cache)))
@@ -571,7 +582,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         return dec
 
     def _generate_beam(self, ids, attention_mask, point_clouds, fps_start, T, nb, n_ret, length_penalty, early_stopping, do_sample, temperature,
-                       top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph, kv=None):
+                       top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph, kv=None, wd=None):
         dev = self.engine.device
         B, S0 = ids.shape
         if isinstance(eos_token_id, str):
@@ -583,7 +594,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                 raise ValueError(f"`{name}` has to be a strictly positive float, but is {v}")
         if top_p is not None and not (0 < float(top_p) <= 1.0):
             raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
-        dec = self._decoder(B, S0 + T, nb, kv=kv)
+        dec = self._decoder(B, S0 + T, nb, kv=kv, wd=wd)
         chunk = 16
         if B > chunk:
             dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=chunk, nb=nb)

@@ -327,6 +327,27 @@ int egomi_attn_decode_rows_fp8(const void* q, int64_t ld_q, const uint8_t* kcode
                                int64_t ld_mask, void* out, int64_t ld_o, int B, int nb, int H, int hd, int Smax, int T_len, float scale,
                                int dtype, egomi_stream_t stream);
 
+/* FP8 (OCP e4m3fn) weights of the single-token decode projections, W8A16 (csrc/w8.hip).  Replaces the bf16 q|k|v, o_proj, gate|up and
+ * down_proj products of a cached decode step (HF LlamaAttention / LlamaMLP forward, modeling_llama.py:243-281,174-176, in the generate()
+ * step of models/pointllm/model_arch.py:77-108 / pointllm/model/pointllm.py:255-275).  Per output row n of W [N, K]:
+ * s_n = amax_k |W[n,k]| / 448 (1 when amax == 0), code[n,k] = e4m3fn_rne(W[n,k] / s_n) -- the KV cache's rule, bit-equal to torch's
+ * (W.float() / s[:, None]).to(torch.float8_e4m3fn).
+ *   quantize_rows_fp8: bf16 rows w [N, K] (row stride ldw) -> codes uint8 [N, K] (row stride ldc), scales fp32 [N]
+ *   gemm_w8          : y[m,n] = s_n * sum_k x[m,k] * float(code[n,k]); x bf16 [M, K] (ldx % 8 == 0, 16-B aligned), codes [N, K] (ldw % 16
+ *                      == 0, 16-B aligned), fp32 accumulation in a fixed order, s_n applied after accumulation (to each K-slice).
+ *                      1 <= M <= 512, N % 4 == 0, K % 32 == 0 (EGOMI_E_UNSUPPORTED otherwise).  epilogue EGOMI_EPI_NONE: out bf16 [M, N]
+ *                      (row stride ldo) = bf16(y), or bf16(y + residual) when residual (bf16 [M, N], row stride ldr) is not NULL; the
+ *                      optional workspace lets the library split K.  EGOMI_EPI_SLABS: out and residual unused (residual must be NULL),
+ *                      the fp32 slabs [slices][M][N] (sum = y) land at the start of the 16-B aligned workspace for egomi_slabs_rmsnorm /
+ *                      egomi_qkv_finish(_fp8); a repeated call writes the same bits (no atomics).
+ *   gemm_w8_slab_count: the number of slabs egomi_gemm_w8 writes with EGOMI_EPI_SLABS for this shape and workspace (0: it cannot run it).
+ *                      Plan and launch are one function of the library. */
+int egomi_quantize_rows_fp8(const void* w, int64_t ldw, int N, int K, uint8_t* codes, int64_t ldc, float* scales, egomi_stream_t stream);
+int egomi_gemm_w8(const void* x, int64_t ldx, const uint8_t* codes, int64_t ldw, const float* scales, void* out, int64_t ldo,
+                  const void* residual, int64_t ldr, int M, int N, int K, int epilogue, void* workspace, int64_t workspace_bytes,
+                  egomi_stream_t stream);
+int egomi_gemm_w8_slab_count(int M, int N, int K, int64_t workspace_bytes);
+
 /* ------------------------------------------------------------------------------------------------
  * A14  trajectory <-> token ids for whole batches, displacement metrics (integer contracts bit-exact).
  * replaces models/pointllm/utils/utils.py:13-21 (discretize_action / token_to_action), :47-104
