@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from . import ops
+from . import lora, ops
 from ._lib import c_p, c_i, c_f, c_i64, call
 from .ops import P, S, dt
 
@@ -162,6 +162,9 @@ class Decoder:
                      for l in range(L)]
         self.wgu = [engine.wgu[l] if l in engine.wgu else engine.stack_gate_up(w[f"model.layers.{l}.mlp.gate_proj.weight"], w[f"model.layers.{l}.mlp.up_proj.weight"])
                     for l in range(L)]                     # interleaved-32 rows when ffn % 32 == 0 (engine.gu_il): gate|up come out interleaved
+        self.wo = self.wdown = None                        # LoRA: merged o_proj / down_proj copies (otherwise step() reads eng.w)
+        if engine.lora is not None:
+            self._merge_lora()
 
         # single-token step: the split-K projections leave their fp32 slabs unsummed and the NEXT kernel of the layer sums them
         # while doing its own work (qkv -> RoPE + cache append; o_proj / down_proj -> residual + RMSNorm): three launches and a
@@ -182,20 +185,45 @@ class Decoder:
             self.fused["o"] = ops.mm_slabs(self.ao, w["model.layers.0.self_attn.o_proj.weight"], self.x_mid, self.gws, count_only=True)
             self.fused["down"] = ops.mm_slabs(self.act, w["model.layers.0.mlp.down_proj.weight"], self.x, self.gws, count_only=True)
 
+    def _merge_lora(self):
+        """LoRA: the decode steps multiply merged copies W + s B A of the adapted projections (one fp32 sum, rounded once; csrc/lora.hip);
+        the prefill runs through the engine on the unmerged adapters.  A decoder is made for one set of adapter values: the model's decoder
+        cache keys on engine.lora_key()."""
+        eng = self.eng
+        w, tg = eng.w, eng.lora.targets
+        get = lambda l, t: eng.lora_merged(l, t) if t in tg else w[lora.base_name(l, t)]
+        self.wo = [w[lora.base_name(l, "o_proj")] for l in range(len(self.wqkv))]
+        self.wdown = [w[lora.base_name(l, "down_proj")] for l in range(len(self.wqkv))]
+        for l in range(len(self.wqkv)):
+            if any(t in tg for t in ("q_proj", "k_proj", "v_proj")):
+                self.wqkv[l] = torch.cat([get(l, t) for t in ("q_proj", "k_proj", "v_proj")], 0)
+            if any(t in tg for t in ("gate_proj", "up_proj")):
+                self.wgu[l] = eng.stack_gate_up(get(l, "gate_proj"), get(l, "up_proj"))
+            if "o_proj" in tg:
+                self.wo[l] = get(l, "o_proj")
+            if "down_proj" in tg:
+                self.wdown[l] = get(l, "down_proj")
+
     def _fp8_weights(self):
         """Per layer {"qkv", "o", "gu", "down": (codes uint8 [N, K], scales fp32 [N])} of the stacked forms step() multiplies ([Wq;Wk;Wv],
         [Wgate;Wup] in its interleaved-32 order when engine.gu_il).  Frozen layers: one copy per engine and prepare_epoch, shared by every
         decoder (Engine.prepared = False drops it); trainable layers change under every optimizer step, so each decoder quantizes afresh."""
         eng = self.eng
-        if eng.w8 is not None and eng.w8[0] == eng.prepare_epoch and not eng.any_layer_trainable:
+        if eng.w8 is not None and eng.w8[0] == eng.weights_key() and not eng.any_layer_trainable:
             return eng.w8[1]
-        w = eng.w
-        q = [{"qkv": ops.quantize_rows_fp8(self.wqkv[l]), "o": ops.quantize_rows_fp8(w[f"model.layers.{l}.self_attn.o_proj.weight"]),
-              "gu": ops.quantize_rows_fp8(self.wgu[l]), "down": ops.quantize_rows_fp8(w[f"model.layers.{l}.mlp.down_proj.weight"])}
+        q = [{"qkv": ops.quantize_rows_fp8(self.wqkv[l]), "o": ops.quantize_rows_fp8(self._w(l, "o")),
+              "gu": ops.quantize_rows_fp8(self.wgu[l]), "down": ops.quantize_rows_fp8(self._w(l, "down"))}
              for l in range(len(self.wqkv))]
         if not eng.any_layer_trainable:
-            eng.w8 = (eng.prepare_epoch, q)
+            eng.w8 = (eng.weights_key(), q)
         return q
+
+    def _w(self, l, name):
+        """o_proj / down_proj of layer l as the decode step multiplies it: the merged LoRA copy, else the engine's weight."""
+        merged = self.wo if name == "o" else self.wdown
+        if merged is not None:
+            return merged[l]
+        return self.eng.w[f"model.layers.{l}." + ("self_attn.o_proj.weight" if name == "o" else "mlp.down_proj.weight")]
 
     def _slabs(self, l, name, a, out_like, weight):
         """The split-K slabs of one projection (fp8 or model-dtype weights) at the start of self.gws; -> their number."""
@@ -304,10 +332,10 @@ class Decoder:
             else:
                 attn_decode_rows(self.qkv, 3 * d, self.kc[l], self.vc[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd, self.Smax, pos + 1, scale)
             if fo:
-                n = self._slabs(l, "o", self.ao, self.x_mid, w[p + "self_attn.o_proj.weight"])
+                n = self._slabs(l, "o", self.ao, self.x_mid, self._w(l, "o"))
                 ops.slabs_rmsnorm(self.gws, n, x, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, self.x_mid, self.h2)
             else:
-                ops.mm(self.ao, w[p + "self_attn.o_proj.weight"], out=self.x_mid, residual=x, workspace=self.gws)
+                ops.mm(self.ao, self._w(l, "o"), out=self.x_mid, residual=x, workspace=self.gws)
                 ops.rmsnorm(self.x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, out=self.h2)
             if self.w8 is not None:
                 ops.mm_w8(self.h2, *self.w8[l]["gu"], out=self.gu, workspace=self.gws)
@@ -318,13 +346,13 @@ class Decoder:
             else:
                 ops.swiglu(self.gu[:, :Fd], self.gu[:, Fd:], self.act)
             if fd:                                          # x is not an input of this product: the tail writes the new residual stream into it
-                n = self._slabs(l, "down", self.act, x, w[p + "mlp.down_proj.weight"])
+                n = self._slabs(l, "down", self.act, x, self._w(l, "down"))
                 last = l + 1 == L
                 ops.slabs_rmsnorm(self.gws, n, self.x_mid, w["model.norm.weight"] if last else w[f"model.layers.{l + 1}.input_layernorm.weight"],
                                   lm.rms_norm_eps, x, self.hn if last else self.h)
                 normed = True
             else:
-                ops.mm(self.act, w[p + "mlp.down_proj.weight"], out=x, residual=self.x_mid, workspace=self.gws)
+                ops.mm(self.act, self._w(l, "down"), out=x, residual=self.x_mid, workspace=self.gws)
                 normed = False
         if not normed:
             ops.rmsnorm(x, w["model.norm.weight"], lm.rms_norm_eps, out=self.hn)

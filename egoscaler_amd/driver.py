@@ -314,13 +314,31 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
     return history
 
 
+def check_adapter_keys(model, sd, path):
+    """The LoRA adapters of a checkpoint must be the ones the --lora_* flags built: same keys, same shapes."""
+    from . import lora
+    own = {k: tuple(v.shape) for k, v in model.state_dict().items() if lora.is_adapter(k)}
+    got = {k: tuple(v.shape) for k, v in sd.items() if lora.is_adapter(k)}
+    if own == got:
+        return
+    if got and not own:
+        raise ValueError(f"{path} holds LoRA adapters ({len(got)} tensors): pass the --lora_r / --lora_alpha / --lora_target_modules it was trained with")
+    if own and not got:
+        raise ValueError(f"{path} holds no LoRA adapters: drop --lora_r (or pass the checkpoint of a LoRA run)")
+    diff = sorted(set(own) ^ set(got)) or sorted(k for k in own if own[k] != got[k])
+    raise ValueError(f"{path}: its LoRA adapters do not match --lora_r {model.lora_cfg.r} / --lora_target_modules "
+                     f"{','.join(model.lora_cfg.targets)} (first difference: {diff[0]})")
+
+
 def evaluate(args, model, data, split="test", device="cuda"):
     """evaluate.py:70-170: load best_model_ade.pt, generate on the split, dump {split}_gen_trajs.json
     ({image_id: [[x,y,z,rx,ry,rz], ...]}, evaluate.py:150,167-170); --do_standard statistics come from
     `{checkpoint_dir}/norm_param.json` (evaluate.py:91 hands checkpoint_dir to the dataset as save_dir)."""
     best = os.path.join(args.checkpoint_dir, "best_model_ade.pt")
     if os.path.exists(best):
-        model.load_state_dict(torch.load(best, map_location="cpu", weights_only=True)["model_state_dict"])
+        sd = torch.load(best, map_location="cpu", weights_only=True)["model_state_dict"]
+        check_adapter_keys(model, sd, best)
+        model.load_state_dict(sd)
     norm = getattr(data, "norm", None)
     if norm is not None and norm.mode == "standard" and norm.mean is None:
         norm.load(args.checkpoint_dir)
@@ -347,6 +365,10 @@ def parse_args(argv=None):
     ap.add_argument("--do_standard", action="store_true")
     ap.add_argument("--unfreeze_pc_encoder", action="store_true")
     ap.add_argument("--unfreeze_language_model", action="store_true")
+    ap.add_argument("--lora_r", type=int, default=0, help="LoRA adapters of this rank on the decoder projections (0: none); base weights stay frozen")
+    ap.add_argument("--lora_alpha", type=float, default=16.0, help="LoRA scaling s = lora_alpha / lora_r")
+    ap.add_argument("--lora_target_modules", default="q_proj,v_proj",
+                    help="comma list of q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj")
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--bs", type=int, default=8)
     ap.add_argument("--grad_accum_steps", type=int, default=1)
@@ -414,7 +436,8 @@ def main(argv=None):
         dims = dims_tiny() if a.tiny else dims_7b()
         model = TrajPointLLMForCausalLM(a, dims, None, device=dev, dtype=dtype)
         sd = synth.synth_state_dict(dims, 0)
-        model.load_state_dict({k: (v.to(dtype) if v.dtype.is_floating_point else v) for k, v in sd.items()})
+        model.load_state_dict({k: (v.to(dtype) if v.dtype.is_floating_point else v) for k, v in sd.items()},
+                              strict=model.lora_cfg is None)         # (fresh LoRA adapters keep their initialisation)
     a.checkpoint_dir = a.checkpoint_dir or a.out_dir
     norm = T.TargetNorm(a.do_norm, a.do_standard)
     if a.mode == "train":

@@ -15,7 +15,7 @@ from typing import Dict
 
 import torch
 
-from . import ops
+from . import lora, ops
 from .config import EgoDims
 
 
@@ -78,6 +78,9 @@ class Engine:
         self.pb_train_mode = False          # set by TrajPointLLMForCausalLM.train(): point backbone in train() mode
         self.prepared_bn_stale = False
         self.fold_stale = False
+        self.lora = None                    # lora.LoraConfig (set by the model shell) or None: adapters on the decoder projections (_lora_fwd)
+        self.lora_version = 0               # bumped whenever adapter values may have changed: holders of merged copies (decode.Decoder) key on it
+        self._lora_ws = None                # fp32 slice partials of lora_down / lora_wgrad (_lora_workspace)
 
     @staticmethod
     def param_group_of(name):
@@ -193,7 +196,7 @@ class Engine:
         if self.dtype == torch.bfloat16:
             for l in range(lm.num_hidden_layers):
                 for nm in self.layer_param_names(l):
-                    if w[nm].dim() == 2 and not (self.use_tn and nm in self.trainable):
+                    if w[nm].dim() == 2 and not lora.is_adapter(nm) and not (self.use_tn and nm in self.trainable):
                         self.wT[nm] = ops.transpose(w[nm])     # trainable ones (EGOMI_GEMM_TN=0 only) are refreshed by after_weights_update()
         # [Wq;Wk;Wv] stacked: one N=3d product fills q|k|v (1102 vs 1010 TFLOP/s measured).  The model allocates the three side by side
         # (model_arch.py), so the stack is a VIEW of the parameters — also for trainable layers, whose stack thereby follows every
@@ -259,6 +262,8 @@ class Engine:
         """Called by the optimizer after a step: the resident W^T of TRAINABLE decoder weights must
         follow the new values (a 2-byte transpose pass per weight; frozen ones never change)."""
         self.lm_wT_stale = True
+        if self.lora is not None and any(lora.is_adapter(n) for n in self.trainable):
+            self.lora_version += 1              # merged decode copies of the adapted weights follow the new adapters
         if not self.prepared:
             return
         if self.pb_trainable:
@@ -487,19 +492,24 @@ class Engine:
         defer = self.use_tail_fuse and T == torch.bfloat16
         pend = pend_res = None
         fuse_swiglu = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and (2 * Fd) % 256 == 0 and ops.gemm_kernel_id(M, 2 * Fd, d) == 2
+        la = self.lora_groups
         for l in range(L):
             p = f"model.layers.{l}."
             self.wait_params(l)
+            lT = {}                                            # T = x A^T of every adapted input: kept for backward
+            for g, ts in la.items():
+                shp = (M, len(ts) * self.lora.r)
+                lT[g] = torch.empty(shp, dtype=T, device=self.device) if save else ws.get(f"lora_T_{g}", shp, T)
             if save:
                 lc = {"x_in": x, "rstd1": torch.empty(M, dtype=torch.float32, device=self.device),
                       "rstd2": torch.empty(M, dtype=torch.float32, device=self.device),
                       "qkv": torch.empty(M, 3 * d, dtype=T, device=self.device),
                       "gu": torch.empty(M, 2 * Fd, dtype=T, device=self.device)}
                 keep_in = self.any_layer_trainable
-                h = torch.empty(M, d, dtype=T, device=self.device) if keep_in else ws.get("h", (M, d), T)
-                ao = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or fused) else ws.get("ao", (M, d), T)
-                h2 = torch.empty(M, d, dtype=T, device=self.device) if keep_in else ws.get("h2", (M, d), T)
-                act = torch.empty(M, Fd, dtype=T, device=self.device) if keep_in else ws.get("act", (M, Fd), T)
+                h = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or "qkv" in la) else ws.get("h", (M, d), T)
+                ao = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or fused or "o" in la) else ws.get("ao", (M, d), T)
+                h2 = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or "gu" in la) else ws.get("h2", (M, d), T)
+                act = torch.empty(M, Fd, dtype=T, device=self.device) if (keep_in or "down" in la) else ws.get("act", (M, Fd), T)
                 x_mid = torch.empty(M, d, dtype=T, device=self.device)
                 x_out = torch.empty(M, d, dtype=T, device=self.device)
                 qkv, gu, rstd1, rstd2 = lc["qkv"], lc["gu"], lc["rstd1"], lc["rstd2"]
@@ -511,7 +521,7 @@ class Engine:
             pend = pend_res = None
             t_qkv = None
             if l in self.wqkv:
-                if defer:
+                if defer and "qkv" not in la:
                     _, t_qkv = ops.mm(h, self.wqkv[l], out=qkv, defer_tail=True)
                 else:
                     ops.mm(h, self.wqkv[l], out=qkv)
@@ -519,6 +529,8 @@ class Engine:
                 ops.mm(h, w[p + "self_attn.q_proj.weight"], out=qkv[:, :d])
                 ops.mm(h, w[p + "self_attn.k_proj.weight"], out=qkv[:, d:2 * d])
                 ops.mm(h, w[p + "self_attn.v_proj.weight"], out=qkv[:, 2 * d:])
+            if "qkv" in la:                                    # adapters: before RoPE, as PEFT wraps q_proj / k_proj / v_proj
+                self._lora_fwd(l, "qkv", h, qkv, lT["qkv"])
             if t_qkv is not None:
                 ops.rope_qkv_tail_(qkv, self.cos, self.sin, M, S, past, H, hd, 3 * d, t_qkv)
             else:
@@ -533,17 +545,22 @@ class Engine:
                 ops.attn_fwd(qkv, B, S, H, hd, scale, ao, lse, causal=True, key_mask=key_mask)
             else:
                 Pm = self._attention(qkv, B, S, H, hd, ao, True, key_mask, scale, save)
-            if defer:                                          # the K-sliced tail rows of the product are summed by the norm that reads them
+            if defer and "o" not in la:                        # the K-sliced tail rows of the product are summed by the norm that reads them
                 _, t_o = ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x, defer_tail=True)
                 ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, rstd=rstd2, out=h2, tail=t_o, tail_residual=x)
             else:
                 ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x)
+                if "o" in la:
+                    self._lora_fwd(l, "o", ao, x_mid, lT["o"])
                 ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, rstd=rstd2, out=h2)
-            if l in self.wgu and self.gu_il:
-                if fuse_swiglu:
+            gu_il = l in self.wgu and self.gu_il
+            if gu_il:
+                if fuse_swiglu and "gu" not in la:
                     ops.mm(h2, self.wgu[l], out=gu, swiglu_out=act)          # act leaves the GEMM epilogue; gu (interleaved-32) is kept for backward
                 else:
                     ops.mm(h2, self.wgu[l], out=gu)
+                    if "gu" in la:
+                        self._lora_fwd(l, "gu", h2, gu, lT["gu"], il=True)
                     ops.swiglu_il(gu, act)
             else:
                 if l in self.wgu or l in self.wgu_cat:
@@ -551,14 +568,18 @@ class Engine:
                 else:
                     ops.mm(h2, w[p + "mlp.gate_proj.weight"], out=gu[:, :Fd])
                     ops.mm(h2, w[p + "mlp.up_proj.weight"], out=gu[:, Fd:])
+                if "gu" in la:
+                    self._lora_fwd(l, "gu", h2, gu, lT["gu"])
                 ops.swiglu(gu[:, :Fd], gu[:, Fd:], act)
-            if defer:                                          # ... here by the NEXT layer's input norm (or the final norm)
+            if defer and "down" not in la:                     # ... here by the NEXT layer's input norm (or the final norm)
                 _, pend = ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid, defer_tail=True)
                 pend_res = x_mid
             else:
                 ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid)
+                if "down" in la:
+                    self._lora_fwd(l, "down", act, x_out, lT["down"])
             if save:
-                lc.update(P=Pm, lse=lse, x_mid=x_mid, h=h, ao=ao, h2=h2, act=act)
+                lc.update(P=Pm, lse=lse, x_mid=x_mid, h=h, ao=ao, h2=h2, act=act, lora_T=lT, gu_il=gu_il)
                 ctx["layers"].append(lc)
             x = x_out
         self.wait_params("post")
@@ -627,7 +648,86 @@ class Engine:
 
     @property
     def any_layer_trainable(self):
-        return any(n.startswith("model.layers.") for n in self.trainable)
+        """A BASE decoder weight is trainable (--unfreeze_language_model).  LoRA adapters share the model.layers. prefix but leave the base
+        layers on the frozen path (tail fusion, SwiGLU epilogue, resident W^T, decoder cache)."""
+        return any(n.startswith("model.layers.") and not lora.is_adapter(n) for n in self.trainable)
+
+    def lora_key(self):
+        """None without adapters; else what identifies their current values: the engine's counter (EgoAdamW steps, loads, merges) and the
+        parameters' in-place versions (torch optimizers)."""
+        if self.lora is None:
+            return None
+        return (self.lora_version, sum(p._version for n, p in self.param_ref.items() if lora.is_adapter(n)))
+
+    def weights_key(self):
+        """What derived decode copies of the decoder weights (fp8 codes, merged adapters) are valid for."""
+        return self.prepare_epoch if self.lora is None else (self.prepare_epoch, self.lora_key())
+
+    # ------------------------------------------------------------------------------------ LoRA (csrc/lora.hip)
+    @property
+    def lora_groups(self):
+        return dict(self.lora.groups()) if self.lora is not None else {}
+
+    def _lora_cat(self, l, targets):
+        """[A_1; ...; A_n] of the adapters that share one input: a view when they lie back to back (the model allocates them so), else a copy."""
+        As = [self.w[lora.adapter_names(l, t)[0]] for t in targets]
+        if len(As) == 1:
+            return As[0]
+        v = self._side_by_side(As)
+        return v if v is not None else torch.cat(As, 0)
+
+    def _lora_cols(self, grp, t, y, il):
+        """The columns of a group's product output (or its gradient) that belong to projection t."""
+        d, Fd = self.dims.lm.hidden_size, self.dims.lm.intermediate_size
+        if grp == "qkv":
+            i = ("q_proj", "k_proj", "v_proj").index(t)
+            return y[:, i * d:(i + 1) * d]
+        if grp == "gu":
+            if il:                                     # interleaved-32: the kernels map logical columns; up starts 32 columns in
+                return y[:, 32:] if t == "up_proj" else y
+            return y[:, Fd:] if t == "up_proj" else y[:, :Fd]
+        return y
+
+    def _lora_fwd(self, l, grp, x, y, T, il=False):
+        """y += s (x A^T) B^T for the adapted projections of one input x (PEFT lora.Linear.forward); T = x [A_1; ...]^T is kept."""
+        r, targets = self.lora.r, self.lora_groups[grp]
+        ops.lora_down(x, self._lora_cat(l, targets), T, workspace=self._lora_workspace(ops.lora_down_workspace_bytes(x.shape[0], x.shape[1], T.shape[1])))
+        for i, t in enumerate(targets):
+            ops.lora_up(T[:, i * r:(i + 1) * r], self.w[lora.adapter_names(l, t)[1]], self._lora_cols(grp, t, y, il), self.lora.scale, il=il)
+
+    def _lora_bwd(self, l, grp, dY, x, dX, T, il=False):
+        """U = dY B, dB = s dY^T T, dA = s U^T x per adapter, then dX += s U A for all adapters of the input in one pass."""
+        r, s, targets = self.lora.r, self.lora.scale, self.lora_groups[grp]
+        U = self.ws.get(f"lora_U_{grp}", (dY.shape[0], len(targets) * r), self.dtype)
+        for i, t in enumerate(targets):
+            an, bn = lora.adapter_names(l, t)
+            dYt, Ut = self._lora_cols(grp, t, dY, il), U[:, i * r:(i + 1) * r]
+            N = self.w[bn].shape[0]
+            ops.lora_down(dYt, self.w[bn], Ut, q_trans=True, il=il, workspace=self._lora_workspace(ops.lora_down_workspace_bytes(dY.shape[0], N, r)))
+            self._lora_wgrad(bn, dYt, T[:, i * r:(i + 1) * r], il=il)
+            self._lora_wgrad(an, Ut, x)
+        ops.lora_up(U, self._lora_cat(l, targets), dX, s, q_trans=True)
+
+    def _lora_wgrad(self, name, lm, rm, il=False):
+        if name not in self.trainable:
+            return
+        g = self.grad_buffer(name)
+        acc = name not in self.grad_fresh
+        self.grad_fresh.discard(name)
+        ws = self._lora_workspace(ops.lora_wgrad_workspace_bytes(rm.shape[0], g.shape[0], g.shape[1]))
+        ops.lora_wgrad(lm, rm, g, self.lora.scale, accumulate=acc, il=il, workspace=ws)
+
+    def _lora_workspace(self, need):
+        """The fp32 slice partials of the LoRA kernels: one buffer that grows to the largest request (used in stream order)."""
+        if need and (self._lora_ws is None or self._lora_ws.numel() < need):
+            self._lora_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._lora_ws
+
+    def lora_merged(self, l, target, W=None):
+        """A copy of projection `target` of layer l with its adapter folded in: W + s B A, one fp32 sum rounded once to the model dtype."""
+        an, bn = lora.adapter_names(l, target)
+        out = (self.w[lora.base_name(l, target)] if W is None else W).clone(memory_format=torch.contiguous_format)
+        return ops.lora_up(self.w[bn], self.w[an], out, self.lora.scale, q_trans=True)
 
     # ------------------------------------------------------------------------------------ backward
     def _dgrad(self, dY, name, out, residual=None):
@@ -728,19 +828,23 @@ class Engine:
         # frozen layers only: with trainable layers the wgrad products between a dgrad and its norm would reuse the slab area
         defer_b = self.use_tail_fuse and T == torch.bfloat16 and not self.any_layer_trainable
         fuse_swiglu_bwd = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and Fd % 64 == 0 and ops.gemm_kernel_id(M, Fd, d) == 2
+        la = self.lora_groups
         for l in reversed(range(L)):
             p = f"model.layers.{l}."
             lc = ctx["layers"][l]
+            lT = lc.get("lora_T")
             gu, qkv = lc["gu"], lc["qkv"]
             self._begin_direct(l)
             # ---- MLP
             dgu = ws.get("dgu", (M, 2 * Fd), T)
             wt_down = self.wT.get(p + "mlp.down_proj.weight") if self.prepared else None
-            if fuse_swiglu_bwd and wt_down is not None and l in self.wguT:
+            if fuse_swiglu_bwd and wt_down is not None and l in self.wguT and "down" not in la:
                 # d(act) = dx . W_down never reaches memory: the GEMM epilogue reads gate|up and writes d(gate|up) (EGOMI_EPI_SWIGLU_BWD)
                 ops.mm(dx, wt_down, out=dgu, swiglu_bwd_gu=gu)
             else:
                 d_act = self._dgrad(dx, p + "mlp.down_proj.weight", ws.get("d_act", (M, Fd), T))
+                if "down" in la:
+                    self._lora_bwd(l, "down", dx, lc["act"], d_act, lT["down"])
                 if self.prepared and l in self.wguT and self.gu_il:
                     ops.swiglu_il_bwd(d_act, gu, dgu)                           # gu / dgu in the interleaved-32 layout of the stacked weight
                 else:
@@ -748,7 +852,7 @@ class Engine:
             self._wgrad(p + "mlp.down_proj.weight", dx, lc["act"])
             t_h2 = None
             if self.prepared and l in self.wguT:
-                if defer_b:
+                if defer_b and "gu" not in la:
                     d_h2, t_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h", (M, d), T), defer_tail=True)
                 else:
                     d_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h", (M, d), T))
@@ -757,12 +861,16 @@ class Engine:
             else:
                 d_h2 = self._dgrad(dgu[:, :Fd], p + "mlp.gate_proj.weight", ws.get("d_h", (M, d), T))
                 self._dgrad(dgu[:, Fd:], p + "mlp.up_proj.weight", d_h2, residual=d_h2)
+            if "gu" in la:
+                self._lora_bwd(l, "gu", dgu, lc["h2"], d_h2, lT["gu"], il=lc["gu_il"])
             self._wgrad_stacked([p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], dgu, lc["h2"])
             n2 = p + "post_attention_layernorm.weight"
             d_mid = ops.rmsnorm_bwd(d_h2, lc["x_mid"], w[n2], lc["rstd2"], dx_add=dx,
                                     dw=self.grad_buffer(n2) if n2 in tr else None, out=ws.get("dx_b", (M, d), T), tail=t_h2)
             # ---- attention
             d_ao = self._dgrad(d_mid, p + "self_attn.o_proj.weight", ws.get("d_ao", (M, d), T))
+            if "o" in la:
+                self._lora_bwd(l, "o", d_mid, lc["ao"], d_ao, lT["o"])
             self._wgrad(p + "self_attn.o_proj.weight", d_mid, lc["ao"])
             dqkv = ws.get("dqkv", (M, 3 * d), T)
             if lc["lse"] is not None:
@@ -774,7 +882,7 @@ class Engine:
                 ops.rope_(dqkv, self.cos, self.sin, M, S, 0, 2 * H, hd, 3 * d, inverse=True)
             t_h = None
             if self.prepared and l in self.wqkvT:
-                if defer_b:
+                if defer_b and "qkv" not in la:
                     d_h, t_h = ops.mm(dqkv, self.wqkvT[l], out=ws.get("d_h", (M, d), T), defer_tail=True)
                 else:
                     d_h = ops.mm(dqkv, self.wqkvT[l], out=ws.get("d_h", (M, d), T))
@@ -784,6 +892,8 @@ class Engine:
                 d_h = self._dgrad(dqkv[:, :d], p + "self_attn.q_proj.weight", ws.get("d_h", (M, d), T))
                 self._dgrad(dqkv[:, d:2 * d], p + "self_attn.k_proj.weight", d_h, residual=d_h)
                 self._dgrad(dqkv[:, 2 * d:], p + "self_attn.v_proj.weight", d_h, residual=d_h)
+            if "qkv" in la:
+                self._lora_bwd(l, "qkv", dqkv, lc["h"], d_h, lT["qkv"])
             self._wgrad_stacked([p + f"self_attn.{nm}_proj.weight" for nm in "qkv"], dqkv, lc["h"])
             n1 = p + "input_layernorm.weight"
             dx = ops.rmsnorm_bwd(d_h, lc["x_in"], w[n1], lc["rstd1"], dx_add=d_mid,
@@ -834,9 +944,13 @@ class Engine:
         self.ctx = None
 
     def layer_param_names(self, l):
+        """The tensors of decoder layer l: its gradient block (one DP bucket) holds the trainable ones, LoRA adapters included."""
         p = f"model.layers.{l}."
-        return [p + f"self_attn.{n}_proj.weight" for n in "qkvo"] + [p + f"mlp.{n}_proj.weight" for n in ("gate", "up", "down")] + \
-               [p + "input_layernorm.weight", p + "post_attention_layernorm.weight"]
+        names = [p + f"self_attn.{n}_proj.weight" for n in "qkvo"] + [p + f"mlp.{n}_proj.weight" for n in ("gate", "up", "down")] + \
+                [p + "input_layernorm.weight", p + "post_attention_layernorm.weight"]
+        if self.lora is not None:
+            names += [n for t in self.lora.targets for n in lora.adapter_names(l, t)]
+        return names
 
     def backward_logits(self, d_logits, hn):
         """lm_head backward: d_hn = d_logits . W ; dW += d_logits^T . hn."""

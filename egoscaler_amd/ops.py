@@ -624,3 +624,71 @@ def attn_bwd(qkv, out, lse, dout, dqkv, delta, B, Sq, H, hd, scale, causal=True,
     d.ld_dqkv = dqkv.stride(0)
     call("egomi_attn_bwd", ctypes.byref(d), S())
     return dqkv
+
+
+# ------------------------------------------------------------------------------------------ LoRA (csrc/lora.hip)
+# PEFT's lora.Linear.forward: y = x W^T + s (x A^T) B^T, s = lora_alpha / r (no dropout, no bias).  `il`: the wide activation operand is
+# read / written in the interleaved-32 gate|up layout (include/egomi.h).
+def lora_down_workspace_bytes(M, K, R):
+    fn = _lib.lib().egomi_lora_down_workspace_bytes
+    fn.restype = c_i64
+    return int(fn(c_i(M), c_i(K), c_i(R)))
+
+
+def lora_down(x, q, out, q_trans=False, il=False, alpha=1.0, workspace=None):
+    """out [M, R] = alpha * x [M, K] . Q^T with Q [R, K] (q_trans: Q given as q = Q^T [K, R]).  T = x A^T (A stacked over the adapters
+    that share x), or U = dY B (q = B, q_trans=True).  workspace: a uint8 tensor of at least lora_down_workspace_bytes(M, K, R) bytes
+    (allocated here when too small)."""
+    R, K = (q.shape[1], q.shape[0]) if q_trans else (q.shape[0], q.shape[1])
+    M = out.shape[0]
+    if out.shape[1] != R or x.dtype != q.dtype or out.dtype != q.dtype or q.stride(1) != 1 or x.stride(1) != 1 or out.stride(1) != 1:
+        raise ValueError("lora_down: x [M, K], Q [R, K] (or Q^T), out [M, R] of one dtype, rows contiguous")
+    if x.shape[0] < M or x.shape[1] < (2 * K - 32 if il else K):
+        raise ValueError(f"lora_down: x {tuple(x.shape)} is smaller than [{M}, {2 * K - 32 if il else K}] (M rows, K logical columns)")
+    need = lora_down_workspace_bytes(M, K, R) if R % 8 == 0 and 8 <= R <= 192 else 0
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        workspace = torch.empty(need, dtype=torch.uint8, device=out.device)
+    wb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    call("egomi_lora_down", P(x), c_i64(x.stride(0)), P(q), c_i64(q.stride(0)), c_i(int(q_trans)), P(out), c_i64(out.stride(0)), c_i(M),
+         c_i(K), c_i(R), c_f(alpha), c_i(int(il)), P(workspace), c_i64(wb), c_i(dt(x.dtype)), S())
+    return out
+
+
+def lora_up(p, q, out, alpha, q_trans=False, il=False):
+    """out [M, N] += alpha * p [M, R] . Q^T with Q [N, R] (q_trans: Q given as q = Q^T [R, N]); one fp32 sum, rounded once.
+    y += s T B^T (q = B), dX += s U A (q = A, q_trans=True), merging W += s B A (p = B, q = A, q_trans=True)."""
+    M, R = p.shape
+    N = q.shape[1] if q_trans else q.shape[0]
+    if (q.shape[0] if q_trans else q.shape[1]) != R or p.dtype != q.dtype or out.dtype != q.dtype or \
+            p.stride(1) != 1 or q.stride(1) != 1 or out.stride(1) != 1 or out.shape[0] != M:
+        raise ValueError("lora_up: p [M, R], Q [N, R] (or Q^T), out [M, >= N] of one dtype, rows contiguous")
+    if out.shape[1] < (2 * N - 32 if il else N):
+        raise ValueError(f"lora_up: out {tuple(out.shape)} is narrower than {2 * N - 32 if il else N} columns")
+    call("egomi_lora_up", P(p), c_i64(p.stride(0)), P(q), c_i64(q.stride(0)), c_i(int(q_trans)), P(out), c_i64(out.stride(0)), c_i(M),
+         c_i(N), c_i(R), c_f(alpha), c_i(int(il)), c_i(dt(p.dtype)), S())
+    return out
+
+
+def lora_wgrad_workspace_bytes(M, Pd, Qd):
+    fn = _lib.lib().egomi_lora_wgrad_workspace_bytes
+    fn.restype = c_i64
+    return int(fn(c_i(M), c_i(Pd), c_i(Qd)))
+
+
+def lora_wgrad(l, r, g, alpha, accumulate=False, il=False, Pd=None, workspace=None):
+    """g fp32 [P, Q] (+)= alpha * l[:, :P]^T . r [M, Q], summed over M in a fixed order: dA = s U^T x (l = U), dB = s dY^T T (l = dY).
+    Pd: the logical width of l (default g's rows).  workspace: a uint8 tensor of at least lora_wgrad_workspace_bytes(M, P, Q) bytes."""
+    M, Qd = r.shape
+    Pd = g.shape[0] if Pd is None else Pd
+    if g.dtype != torch.float32 or g.shape[1] != Qd or g.stride(1) != 1 or l.dtype != r.dtype or l.stride(1) != 1 or r.stride(1) != 1 \
+            or l.shape[0] != M:
+        raise ValueError("lora_wgrad: l [M, >= P], r [M, Q] of one dtype, g fp32 [P, Q], rows contiguous")
+    if g.shape[0] != Pd or l.shape[1] < (2 * Pd - 32 if il else Pd):
+        raise ValueError(f"lora_wgrad: l {tuple(l.shape)} is narrower than {2 * Pd - 32 if il else Pd} columns, or g has not {Pd} rows")
+    need = lora_wgrad_workspace_bytes(M, Pd, Qd)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        workspace = torch.empty(need, dtype=torch.uint8, device=g.device)
+    wb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    call("egomi_lora_wgrad", P(l), c_i64(l.stride(0)), P(r), c_i64(r.stride(0)), P(g), c_i64(g.stride(0)), c_i(M), c_i(Pd), c_i(Qd),
+         c_f(alpha), c_i(int(accumulate)), c_i(int(il)), P(workspace), c_i64(wb), c_i(dt(r.dtype)), S())
+    return g

@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from ..config import EgoDims, LlamaDims, PointBertDims, SpecialTokens
 from ..engine import Engine
-from .. import ops, synth
+from .. import lora, ops, synth
 
 
 class PointLLMConfig:
@@ -204,6 +204,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         self.args, self.config, self.model_name = args, config, model_name
         self.dims = config.to_dims() if not isinstance(config, EgoDims) else config
         dev = torch.device(device or "cuda")
+        self.lora_cfg = lora.config_from_args(args, dtype)     # LoRA adapters on the decoder projections (None: off); validated before any allocation
         if dev.type != "cuda":
             raise RuntimeError("TrajPointLLMForCausalLM (egoscaler_amd) runs on an MI355X only; there is no CPU path")
         # q|k|v and gate|up of a decoder layer live side by side in ONE allocation each: every Parameter keeps its own name, shape and
@@ -225,6 +226,8 @@ class TrajPointLLMForCausalLM(nn.Module):
             is_buf = leaf in _BUFFER_LEAVES
             t = shared[k] if k in shared else torch.zeros(shape, dtype=torch.long if leaf == "num_batches_tracked" else dtype, device=dev)
             _install(self, k, t, is_buf)
+        if self.lora_cfg is not None:
+            self._install_lora(shapes, dtype, dev)
         self._anchor = torch.zeros((), device=dev, requires_grad=True)
         self.training_graph = True
         self.accumulate_grads = False
@@ -236,6 +239,83 @@ class TrajPointLLMForCausalLM(nn.Module):
             self.load_pretrained_weights()
         self._configure_trainable_parameters()
 
+    # -- LoRA ------------------------------------------------------------------------------------------
+    def _install_lora(self, shapes, dtype, dev):
+        """PEFT lora.Linear adapters: lora_A.weight [r, in] ~ U(+-1/sqrt(in)) (kaiming_uniform_(a=sqrt(5))), lora_B.weight [out, r] = 0.  The
+        A's of adapters that share an input (q|k|v, gate|up) lie back to back in one allocation: the engine reads them as one stacked operand."""
+        cfg, seed = self.lora_cfg, int(getattr(self.args, "seed", 0) or 0)
+        for l in range(self.dims.lm.num_hidden_layers):
+            for _, targets in cfg.groups():
+                n_in = shapes[lora.base_name(l, targets[0])][1]
+                block = torch.empty(len(targets) * cfg.r, n_in, dtype=dtype, device=dev)
+                for i, t in enumerate(targets):
+                    a_name, b_name = lora.adapter_names(l, t)
+                    A = block[i * cfg.r:(i + 1) * cfg.r]
+                    A.copy_(lora.init_A(A.shape, seed, l, t))
+                    _install(self, a_name, A, False)
+                    _install(self, b_name, torch.zeros(shapes[lora.base_name(l, t)][0], cfg.r, dtype=dtype, device=dev), False)
+
+    def lora_state_dict(self):
+        """{name: tensor} of the adapters (empty without LoRA)."""
+        self.engine.wait_param_updates()
+        return {n: p.detach() for n, p in self.named_parameters() if lora.is_adapter(n)}
+
+    def _adapters_changed(self):
+        self.engine.lora_version += 1
+        self.engine.w8 = None
+
+    def save_lora(self, path):
+        """The adapters in PEFT's save_pretrained layout: adapter_config.json and adapter_model.safetensors (keys
+        base_model.model.model.layers.{l}.<module>.lora_{A,B}.weight)."""
+        if self.lora_cfg is None:
+            raise ValueError("save_lora: the model has no LoRA adapters")
+        lora.save_dir(path, self.lora_cfg, self.lora_state_dict(), self.model_name)
+
+    def load_lora(self, path):
+        """Adapters from a PEFT adapter directory; r, lora_alpha and target_modules must match this model's."""
+        if self.lora_cfg is None:
+            raise ValueError("load_lora: the model has no LoRA adapters (build it with lora_r > 0)")
+        cfg, sd = lora.load_dir(path)
+        if (cfg.r, cfg.alpha, cfg.targets) != (self.lora_cfg.r, self.lora_cfg.alpha, self.lora_cfg.targets):
+            raise ValueError(f"adapter {path}: r={cfg.r}, lora_alpha={cfg.alpha}, targets={list(cfg.targets)} do not match the model's "
+                             f"r={self.lora_cfg.r}, lora_alpha={self.lora_cfg.alpha}, targets={list(self.lora_cfg.targets)}")
+        own = self.lora_state_dict()
+        if set(sd) != set(own):
+            raise ValueError(f"adapter {path}: keys differ from the model's (missing {sorted(set(own) - set(sd))[:4]}, "
+                             f"unexpected {sorted(set(sd) - set(own))[:4]})")
+        with torch.no_grad():
+            for k, v in sd.items():
+                own[k].copy_(v)
+        self._adapters_changed()
+
+    @torch.no_grad()
+    def merge_lora(self):
+        """Folds s B A into the base weights (W + s B A in fp32, rounded once to the model dtype), removes the adapters and turns LoRA off:
+        state_dict() then has exactly the reference's keys."""
+        if self.lora_cfg is None:
+            raise ValueError("merge_lora: the model has no LoRA adapters")
+        eng = self.engine
+        eng.wait_param_updates()
+        params = dict(self.named_parameters())
+        for l in range(self.dims.lm.num_hidden_layers):
+            for t in self.lora_cfg.targets:
+                W = params[lora.base_name(l, t)].data
+                W.copy_(eng.lora_merged(l, t))
+        for l in range(self.dims.lm.num_hidden_layers):
+            for t in self.lora_cfg.targets:
+                mod = self
+                for q in lora.adapter_names(l, t)[0].split(".")[:-2]:
+                    mod = getattr(mod, q)
+                del mod.lora_A, mod.lora_B
+        self.lora_cfg = None
+        if hasattr(self.args, "lora_r"):
+            self.args.lora_r = 0
+        tr = [n for n in eng.trainable if not lora.is_adapter(n)]
+        self.engine = None
+        self._build_engine()
+        self.engine.set_trainable(tr)
+        return self
+
     # -- plumbing ---------------------------------------------------------------------------------
     def _build_engine(self):
         tensors = {k: v for k, v in self.named_parameters()}
@@ -246,6 +326,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         self.__dict__.pop("_decoders", None)                # decoders hold stacked copies of the old engine's weights
         self.engine = Engine(self.dims, {k: v.data for k, v in tensors.items()}, dev, dtype)
         self.engine.param_ref = dict(self.named_parameters())
+        self.engine.lora = self.lora_cfg
         if old is not None:
             self.engine.trainable = old.trainable
         pb = self.dims.pb
@@ -279,6 +360,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         r = super().load_state_dict(sd, strict=strict, **kw)
         self.engine.prepared = False
         self.engine.lm_wT_stale = True          # the padded lm_head transpose follows the loaded values
+        self.engine.lora_version += 1           # ... and merged decode copies the loaded adapters
         return r
 
     def load_pretrained_weights(self):
@@ -341,6 +423,8 @@ class TrajPointLLMForCausalLM(nn.Module):
         for n, p in self.named_parameters():
             if n.startswith("model.point_backbone."):
                 p.requires_grad = unfreeze_pc
+            elif lora.is_adapter(n):
+                p.requires_grad = True                     # LoRA: the adapters train, their base weights stay frozen
             elif n.startswith("model.layers."):
                 p.requires_grad = unfreeze_llm
             else:
@@ -569,7 +653,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         eng = self.engine
         if not eng.prepared:
             eng.prepare()
-        key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv, wd)
+        key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv, wd, eng.lora_key())     # adapters: merged decode copies of their values
         cache = self.__dict__.setdefault("_decoders", {})
         reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
         dec = cache.get(key) if reuse else None

@@ -348,6 +348,29 @@ int egomi_gemm_w8(const void* x, int64_t ldx, const uint8_t* codes, int64_t ldw,
                   egomi_stream_t stream);
 int egomi_gemm_w8_slab_count(int M, int N, int K, int64_t workspace_bytes);
 
+/* LoRA adapters on the decoder projections (csrc/lora.hip): the low-rank products of PEFT's lora.Linear.forward (peft/tuners/lora/layer.py:
+ * result = base_layer(x) + lora_B(lora_A(x)) * scaling, scaling = lora_alpha / r; no dropout, no bias) and of its backward.  For one adapted
+ * projection with A [r, K], B [N, r] and s = lora_alpha / r: T = x A^T, y += s T B^T; U = dY B, dX += s U A, dA = s U^T x, dB = s dY^T T;
+ * merging W' = W + s B A.  dtype EGOMI_F32 or EGOMI_BF16 for every operand but G; fp32 accumulation in a fixed order, no atomics.
+ * il = 1: logical column c of the wide activation operand (X of lora_down, Y of lora_up, L of lora_wgrad) lies at 64 * (c / 32) + c % 32,
+ * the interleaved-32 gate|up layout (its row stride must hold 2 * width - 32 columns; the up half starts 32 columns in).
+ *   lora_down : y[m, j] = alpha * sum_k x[m, k] q(j, k), m < M, j < R, k < K; q(j, k) = q_trans ? q[k ldq + j] : q[j ldq + k].  Stacking n
+ *               adapters that share x ([A_1; ...; A_n], R = n r) reads x once.  K is cut into fixed 512-deep slices whose fp32 partials go
+ *               to `workspace` (egomi_lora_down_workspace_bytes(M, K, R) bytes; 0 = none needed) and are summed in slice order.
+ *   lora_up   : y[m, n] = dtype(float(y[m, n]) + alpha * sum_j p[m, j] q(n, j)), n < N, j < R; q(n, j) = q_trans ? q[j ldq + n] : q[n ldq + j].
+ *   lora_wgrad: G[p, q] = (accumulate ? G[p, q] : 0) + alpha * sum_m l[m, p] r[m, q] (G fp32 [P, Q], row stride ldg), m < M; one of P, Q
+ *               at most 192.  M is cut into fixed 256-row slices whose fp32 partials go to `workspace`
+ *               (egomi_lora_wgrad_workspace_bytes(M, P, Q) bytes; 0 = none needed) and are summed in slice order.
+ * R (lora_down, lora_up) % 8 == 0 and 8 <= R <= 192, il with a width % 32 != 0, and other dtypes return EGOMI_E_UNSUPPORTED. */
+int64_t egomi_lora_down_workspace_bytes(int M, int K, int R);
+int egomi_lora_down(const void* x, int64_t ldx, const void* q, int64_t ldq, int q_trans, void* y, int64_t ldy, int M, int K, int R,
+                    float alpha, int il, void* workspace, int64_t workspace_bytes, int dtype, egomi_stream_t stream);
+int egomi_lora_up(const void* p, int64_t ldp, const void* q, int64_t ldq, int q_trans, void* y, int64_t ldy, int M, int N, int R, float alpha,
+                  int il, int dtype, egomi_stream_t stream);
+int64_t egomi_lora_wgrad_workspace_bytes(int M, int P, int Q);
+int egomi_lora_wgrad(const void* l, int64_t ldl, const void* r, int64_t ldr, float* g, int64_t ldg, int M, int P, int Q, float alpha,
+                     int accumulate, int il, void* workspace, int64_t workspace_bytes, int dtype, egomi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * A14  trajectory <-> token ids for whole batches, displacement metrics (integer contracts bit-exact).
  * replaces models/pointllm/utils/utils.py:13-21 (discretize_action / token_to_action), :47-104
