@@ -102,7 +102,10 @@ extern "C" int egomi_layernorm_bwd(const void* dy, const void* x, const void* w,
 }
 
 // ------------------------------------------------------------------------------------------------
-// column statistics: sum[c] += sum_r x[r,c], sumsq[c] += sum_r x[r,c]^2  (optionally of x*mask-free)
+// column statistics about a per-channel pivot k[c] = x[0, c]: sum[c] = sum_r (x[r,c] - k), sumsq[c] = sum_r (x[r,c] - k)^2.
+// The batch variance is then sumsq/R - (sum/R)^2 of values centred near the channel's mean: the plain sumsq/R - mean^2 of fp32 sums
+// cancels when |mean| >> std (a conv output with a bias in front of the BatchNorm): replayed in this summation order at R = 131072, its rstd
+// was off by 1e-3 (relative) at |mean| = 100 std and by 0.15 at 1000 std.  The pivot costs one extra load per column and block; the order stays fixed.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void colstats_kernel(const T* x, long long R, int C, float* part /* [gridDim.y][2*C] */, int rows_per_block) {
@@ -110,13 +113,14 @@ __global__ __launch_bounds__(256) void colstats_kernel(const T* x, long long R, 
     if (c >= C) return;
     const long long r0 = (long long)blockIdx.y * rows_per_block;
     long long r1 = r0 + rows_per_block; r1 = r1 < R ? r1 : R;
+    const float k = Cvt<T>::ld(x + c);
     float a = 0.f, b = 0.f;
-    for (long long r = r0; r < r1; ++r) { const float v = Cvt<T>::ld(x + r * C + c); a += v; b += v * v; }
+    for (long long r = r0; r < r1; ++r) { const float v = Cvt<T>::ld(x + r * C + c) - k; a += v; b += v * v; }
     part[(long long)blockIdx.y * 2 * C + c] = a;
     part[(long long)blockIdx.y * 2 * C + C + c] = b;
 }
 
-// y = relu?((x - mean) * rstd * gamma + beta), mean/rstd from the batch sums (biased variance, nn.BatchNorm1d
+// y = relu?((x - mean) * rstd * gamma + beta), mean/rstd from the pivoted batch sums (biased variance, nn.BatchNorm1d
 // training mode); block (0,0) also updates running_mean / running_var (momentum, unbiased variance).
 template <typename T>
 __global__ __launch_bounds__(256) void bn_train_apply_kernel(const T* x, long long R, int C, const float* sum, const float* sumsq, const T* gamma,
@@ -125,10 +129,11 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const T* x, long lo
     const long long total = R * C;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int c = (int)(e % C);
-        const float mean = sum[c] / (float)R;
-        const float var = fmaxf(sumsq[c] / (float)R - mean * mean, 0.f);
+        const float k = Cvt<T>::ld(x + c), d = sum[c] / (float)R;             // d = mean - k
+        const float mean = k + d;
+        const float var = fmaxf(sumsq[c] / (float)R - d * d, 0.f);
         const float rstd = rsqrtf(var + eps);
-        float v = (Cvt<T>::ld(x + e) - mean) * rstd * Cvt<T>::ld(gamma + c) + Cvt<T>::ld(beta + c);
+        float v = ((Cvt<T>::ld(x + e) - k) - d) * rstd * Cvt<T>::ld(gamma + c) + Cvt<T>::ld(beta + c);
         if (relu) v = fmaxf(v, 0.f);
         Cvt<T>::st(y + e, v);
         if (e < C) {                                   // one thread per channel
@@ -143,7 +148,7 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const T* x, long lo
 }
 
 extern "C" int egomi_bn_train_fwd(const void* x, int64_t R, int C, const void* gamma, const void* beta, float eps, int relu, void* y,
-                                  float* stats /* [4*C]: sum, sumsq (scratch), mean, rstd (saved) */, void* running_mean, void* running_var,
+                                  float* stats /* [4*C]: sum, sumsq about x[0,:] (scratch), mean, rstd (saved) */, void* running_mean, void* running_var,
                                   float momentum, float* partials, int64_t partial_floats, int dtype, egomi_stream_t stream) {
     if (!x || !gamma || !beta || !y || !stats || !partials) return EGOMI_E_BADARG;
     if (R <= 0 || C <= 0) return EGOMI_E_SHAPE;

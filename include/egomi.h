@@ -399,7 +399,7 @@ int egomi_traj_metrics(const float* gen, const int32_t* n_gen, const float* gt, 
  *   layernorm_bwd : dx = dx_add + LN'(dy); dw, db (fp32 [cols], caller-zeroed, may be NULL) accumulate
  *   bn_train_fwd  : y = relu?(BatchNorm1d(x)) with BATCH statistics over the R rows (biased variance),
  *                   running stats updated with `momentum` (unbiased variance), stats = fp32 [4*C]
- *                   scratch/saved block {sum, sumsq, mean, rstd}
+ *                   scratch/saved block {sum, sumsq (both of x - x[0,:]: scratch), mean, rstd (saved)}
  *   bn_train_bwd  : dx, dgamma, dbeta (fp32 [C], written by the call) from dy, x, y and the saved stats
  *   group_argmax  : x [BG,M,C] -> max over M and its first arg-max;  group_max_bwd scatters dout back
  *   smallk_wgrad  : dW[n,k] (fp32, caller-zeroed/accumulating) += sum_r dy[r,n]*x[r,k], K <= 8

@@ -96,22 +96,36 @@ def _bn_eval(x, sd, p, eps=1e-5, training=False):
                         training=training, momentum=0.1, eps=eps)
 
 
-def pointnet_encoder(sd, prefix: str, neighborhood: torch.Tensor, training=False) -> torch.Tensor:
+def _group_max(x, pick, taps, key):
+    """max over the M points of each group: x [BG,C,M] -> [BG,C].  pick [BG,C] (optional): the rows to take instead of the arg-max — the
+    picks of a product that computed x in lower precision, where near-ties may select another row; the gradient then flows through the
+    same rows.  taps[key] = max |x.max - x[pick]| / max |x| tells the caller whether the picks are maxima to within its rounding."""
+    if pick is None:
+        return x.max(dim=2)[0]
+    got = x.gather(2, pick.to(torch.int64).unsqueeze(2)).squeeze(2)
+    if taps is not None:
+        xd = x.detach()
+        taps[key] = float((xd.max(dim=2)[0] - got.detach()).abs().max() / xd.abs().max())
+    return got
+
+
+def pointnet_encoder(sd, prefix: str, neighborhood: torch.Tensor, training=False, picks=None, taps=None) -> torch.Tensor:
     """[B,G,M,C] -> [B,G,encoder_dims]; BatchNorm uses running stats (frozen backbone stays in
-    eval(), model_arch.py:121-122) unless training=True."""
+    eval(), model_arch.py:121-122) unless training=True.  picks: None or the rows ([BG,C] each) the two group maxima take (_group_max)."""
     B, G, M, C = neighborhood.shape
+    p1, p2 = picks if picks is not None else (None, None)
     x = neighborhood.reshape(B * G, M, C).transpose(2, 1)                        # dvae.py:213-215
     p = prefix + "first_conv."
     x = F.conv1d(x, sd[p + "0.weight"], sd[p + "0.bias"])
     x = F.relu(_bn_eval(x, sd, p + "1.", training=training))
     x = F.conv1d(x, sd[p + "3.weight"], sd[p + "3.bias"])                        # [BG,256,M]
-    g = x.max(dim=2, keepdim=True)[0]                                            # dvae.py:216
+    g = _group_max(x, p1, taps, "pick_gap1").unsqueeze(2)                        # dvae.py:216
     x = torch.cat([g.expand(-1, -1, M), x], dim=1)                               # dvae.py:217
     p = prefix + "second_conv."
     x = F.conv1d(x, sd[p + "0.weight"], sd[p + "0.bias"])
     x = F.relu(_bn_eval(x, sd, p + "1.", training=training))
     x = F.conv1d(x, sd[p + "3.weight"], sd[p + "3.bias"])
-    return x.max(dim=2)[0].reshape(B, G, -1)                                     # dvae.py:219-220
+    return _group_max(x, p2, taps, "pick_gap2").reshape(B, G, -1)               # dvae.py:219-220
 
 
 # ---------------------------------------------------------------------------------------------
@@ -141,10 +155,11 @@ def vit_block(sd, p, x, num_heads, eps=1e-5, drop=None):
     return x + (h if drop is None else h * drop[1].to(h.dtype)[:, None, None])   # point_encoder.py:75
 
 
-def point_transformer_from_groups(sd, prefix, neighborhood, center, depth, num_heads, taps=None, training=False, drop=None):
+def point_transformer_from_groups(sd, prefix, neighborhood, center, depth, num_heads, taps=None, training=False, drop=None, picks=None):
     """Everything after grouping (point_encoder.py:173-186). neighborhood/center: torch f32.
-    training=True: BatchNorm in train mode; DropPath through `drop` [depth, 2, B] (per-sample branch scales, see vit_block; None = rate 0)."""
-    tok = pointnet_encoder(sd, prefix + "encoder.", neighborhood, training=training)
+    training=True: BatchNorm in train mode; DropPath through `drop` [depth, 2, B] (per-sample branch scales, see vit_block; None = rate 0).
+    picks: rows for the mini-PointNet's two group maxima (see _group_max); None = their own arg-max."""
+    tok = pointnet_encoder(sd, prefix + "encoder.", neighborhood, training=training, picks=picks, taps=taps)
     if taps is not None:
         taps["pointnet"] = tok
     tok = F.linear(tok, sd[prefix + "reduce_dim.weight"], sd[prefix + "reduce_dim.bias"])
