@@ -45,6 +45,14 @@ extern "C" int egomi_event_elapsed_ms(void* start, void* stop, float* ms) {
     }
     return EGOMI_OK;
 }
+thread_local int egomi_route_[5] = {0, 1, 0, 0, 0};
+
+extern "C" int egomi_gemm_last_route(int* out4) {
+    if (!out4) return EGOMI_E_BADARG;
+    for (int i = 0; i < 4; ++i) out4[i] = egomi_route_[i + 1];
+    return egomi_route_[0];
+}
+
 extern "C" int egomi_gemm_time_next(void* start, void* stop) {
     if ((start == nullptr) != (stop == nullptr)) return EGOMI_E_BADARG;
     egomi_time_start_ = (hipEvent_t)start; egomi_time_stop_ = (hipEvent_t)stop;

@@ -123,6 +123,11 @@ extern thread_local int egomi_last_hip_error_;
         const hipError_t e_ = hipGetLastError();                       \
         if (e_ != hipSuccess) { egomi_launch_err_ = 1; egomi_last_hip_error_ = (int)e_; } \
     } while (0)
+// the route of this thread's latest egomi_gemm (include/egomi.h egomi_gemm_last_route): form, split-K slices, tail row0, tail slices, Na
+extern thread_local int egomi_route_[5];      // defined in api.hip
+static inline void egomi_route_set(int form, int splitk, int row0, int slices, int na) {
+    egomi_route_[0] = form; egomi_route_[1] = splitk; egomi_route_[2] = row0; egomi_route_[3] = slices; egomi_route_[4] = na;
+}
 static inline int egomi_launch_status() {
     const int e = egomi_launch_err_;
     egomi_launch_err_ = 0;

@@ -192,6 +192,7 @@ static int launch_generic(const egomi_gemm_desc* d, hipStream_t s) {
     else if (!TA && TB) EGOMI_LAUNCH((gemm_generic_kernel<T, TC, false, true>), grid, block, 0, s, g, aa, ba);
     else if (TA && !TB) EGOMI_LAUNCH((gemm_generic_kernel<T, TC, true, false>), grid, block, 0, s, g, aa, ba);
     else EGOMI_LAUNCH((gemm_generic_kernel<T, TC, true, true>), grid, block, 0, s, g, aa, ba);
+    egomi_route_set(1, 1, d->M, 0, 0);
     return egomi_launch_status();
 }
 
@@ -200,6 +201,7 @@ int egomi_gemm_tn_try(const egomi_gemm_desc* d, hipStream_t s);     // gemm_tn.h
 extern thread_local hipEvent_t egomi_time_start_, egomi_time_stop_;  // api.hip
 
 extern "C" int egomi_gemm(const egomi_gemm_desc* d, egomi_stream_t stream) {
+    egomi_route_set(0, 1, d ? d->M : 0, 0, 0);                         // egomi_gemm_last_route: each launch_* records what it ran
     if (!d || !d->A || !d->B || !d->C) return EGOMI_E_BADARG;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0) return EGOMI_E_SHAPE;
     if (d->a_layout < 0 || d->a_layout > 1 || d->b_layout < 0 || d->b_layout > 1 || d->act < 0 || d->act > 2) return EGOMI_E_BADARG;

@@ -1672,6 +1672,7 @@ static int launch_gemv(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s) {
         if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, g);
         else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, g);
     }
+    egomi_route_set(4, g.splitk, d->M, 0, 0);
     return egomi_launch_status();
 }
 
@@ -1689,6 +1690,7 @@ static int launch_m256(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s) {
         if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, g);
         else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, g);
     }
+    egomi_route_set(5, g.splitk, d->M, 0, 0);
     return egomi_launch_status();
 }
 
@@ -1718,6 +1720,7 @@ static int launch_fast(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s) {
         if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, g);
         else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, g);
     }
+    egomi_route_set(BM == 256 ? 3 : 2, g.splitk, d->M, 0, 0);
     return egomi_launch_status();
 }
 
@@ -1832,6 +1835,7 @@ static int launch_p8(const egomi_gemm_desc* d, FastArgs& g, const P8Sched& sc, h
     if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(gemm_nt_bf16_p8_kernel<bf16_t>, dim3(grid), dim3(512), 0, s, g, sc);
     else if (d->c_dtype == EGOMI_F32) EGOMI_LAUNCH(gemm_nt_bf16_p8_kernel<float>, dim3(grid), dim3(512), 0, s, g, sc);
     else return EGOMI_E_UNSUPPORTED;
+    egomi_route_set(7, 1, d->M, 0, 0);
     return egomi_launch_status();
 }
 
@@ -1872,6 +1876,7 @@ static int launch_tall(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s, hip
     if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH((gemm_nt_bf16_tall_kernel<bf16_t, false>), dim3(nwg), dim3(512), 0, s, g);
     else EGOMI_LAUNCH((gemm_nt_bf16_tall_kernel<float, false>), dim3(nwg), dim3(512), 0, s, g);
     if (t1) (void)hipEventRecord(t1, s);
+    egomi_route_set(8, 1, d->M, 0, 0);
     return egomi_launch_status();
 }
 
@@ -1901,12 +1906,14 @@ int egomi_tall_kmajor_try(const egomi_gemm_desc* d, hipStream_t s, bool query) {
     g.tiles_m = (d->M + TL_BM - 1) / TL_BM; g.tiles_n = Na / 256;
     g.splitk = 1; g.full_tm = 8;
     EGOMI_LAUNCH((gemm_nt_bf16_tall_kernel<bf16_t, true>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
-    if (Na == d->N) return egomi_launch_status();
+    if (Na == d->N) { egomi_route_set(11, 1, d->M, 0, 0); return egomi_launch_status(); }
     egomi_gemm_desc d2 = *d;                                             // the rest on gemm_tn.hip's 256x256 tiles (its own tail plan)
     d2.N = d->N - Na;
     d2.B = (const bf16_t*)d->B + Na;
     d2.C = (bf16_t*)d->C + Na;
-    return egomi_gemm_tn_rest(&d2, s);
+    const int rc = egomi_gemm_tn_rest(&d2, s);
+    egomi_route_[0] = 12; egomi_route_[4] = Na;                          // (the rest's tail plan stays in the record)
+    return rc;
 }
 
 // the tail plan launch_8phase will run for this descriptor (d->workspace already points at the slab area)
@@ -1969,6 +1976,7 @@ static int launch_8phase(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s, i
     if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(gemm_nt_bf16_8phase_kernel<bf16_t>, dim3(nwg, 1), dim3(512), 0, s, g);
     else EGOMI_LAUNCH(gemm_nt_bf16_8phase_kernel<float>, dim3(nwg, 1), dim3(512), 0, s, g);
     if (t1) (void)hipEventRecord(t1, s);
+    egomi_route_set(6, 1, tp.rows ? g.full_tm * 256 : d->M, tp.rows ? tp.s : 0, 0);
     if (tp.rows && g.epi == 1 && g.tickets) g.tickets = nullptr;         // the fused SwiGLU epilogue wants the separate combine + tail pass below
     if (leave_slabs) return egomi_launch_status();                       // EGOMI_EPI_SLABS: the caller's next kernel sums the tail rows' slabs
     if (tp.rows && g.epi == 3) {                                         // K-sliced tail rows of d(act): summed and turned into d(gate|up) in one pass
@@ -2049,7 +2057,9 @@ static int launch_split(const egomi_gemm_desc* d, const FastArgs& g, int Na, hip
     if (d->residual) d2.residual = g2.residual = (const char*)d->residual + (long long)Na * esz;
     if (d->epilogue == EGOMI_EPI_SWIGLU) d2.C2 = g2.C2 = (char*)d->C2 + (long long)(Na / 2) * 2;   // act [M, N/2]
     if (d->epilogue == EGOMI_EPI_SWIGLU_BWD) d2.C2 = g2.C2 = (char*)d->C2 + 2ll * Na * 2;          // gate|up [M, 2N]
-    return launch_8phase(&d2, g2, s, nullptr, nullptr, t1);
+    rc = launch_8phase(&d2, g2, s, nullptr, nullptr, t1);
+    egomi_route_[0] = 9; egomi_route_[4] = Na;                           // (the second part's tail plan stays in the record)
+    return rc;
 }
 
 // returns 0 on success, <0 on error, 1 when the tuned kernel does not apply

@@ -416,6 +416,7 @@ int egomi_gemm_tn_rest(const egomi_gemm_desc* d, hipStream_t s) {
         if (f32) EGOMI_LAUNCH((gemm_bf16_8phase_t_kernel<float, false, true>), grid, block, 0, s, g);
         else EGOMI_LAUNCH((gemm_bf16_8phase_t_kernel<bf16_t, false, true>), grid, block, 0, s, g);
     }
+    egomi_route_set(10, 1, rows > 0 ? g.full_tm * 256 : d->M, rows > 0 ? slices : 0, 0);
     if (rows > 0) {
         const long long row0 = (long long)g.full_tm * 256;
         const int esz = f32 ? 4 : 2;

@@ -8,7 +8,9 @@ Here the prefill is Engine.forward_hidden with a kv_sink; each later step runs
 on static buffers.  Every length is a launch argument, so T steps are captured into ONE hipGraph
 (BASELINE.json config 5) and replayed with a single launch; token ids never leave the device.
 """
+import contextlib
 import ctypes
+import gc
 import os
 
 import torch
@@ -16,6 +18,26 @@ import torch
 from . import lora, ops
 from ._lib import c_p, c_i, c_f, c_i64, call
 from .ops import P, S, dt
+
+
+@contextlib.contextmanager
+def _capture(g):
+    """Capture the block into CUDAGraph g on a side stream, with the cyclic garbage collector off.  This torch does not collect before a
+    capture, so a collection could start inside one and run the finalizers of whatever unrelated objects it frees (a dropped model's
+    graphs, events, memory pools); their HIP calls are illegal during a capture and abort the process (a beam-search capture aborted with
+    the main thread inside such a collection).  Garbage is collected after the capture instead."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                yield
+    finally:
+        if enabled:
+            gc.enable()
+    torch.cuda.current_stream().wait_stream(side)
 
 
 def kv_append(k, v, ld, kc, vc, B, Sq, H, hd, Smax, pos0):
@@ -391,12 +413,8 @@ class Decoder:
             g = self._graphs.get(key)
             if g is None:
                 g = torch.cuda.CUDAGraph()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(g, stream=side):
-                        steps()
-                torch.cuda.current_stream().wait_stream(side)
+                with _capture(g):
+                    steps()
                 self._graphs[key] = g
             g.replay()
             self.graph = g
@@ -418,17 +436,13 @@ class Decoder:
             return self.seq, scores
         sc_buf = torch.zeros(T_new, self.B, self.lg.shape[1], dtype=torch.float32, device=self.eng.device) if keep_scores else None
         g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                for t in range(T_new):
-                    if keep_scores:
-                        ops.cast(self.lg, torch.float32, out=sc_buf[t])
-                    argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
-                    if t + 1 < T_new:
-                        self.step(S0 + t)
-        torch.cuda.current_stream().wait_stream(side)
+        with _capture(g):
+            for t in range(T_new):
+                if keep_scores:
+                    ops.cast(self.lg, torch.float32, out=sc_buf[t])
+                argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
+                if t + 1 < T_new:
+                    self.step(S0 + t)
         g.replay()
         self.graph = g
         self.pos = S0 + T_new
@@ -505,12 +519,8 @@ class Decoder:
             g = self._graphs.get(key)
             if g is None:
                 g = torch.cuda.CUDAGraph()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(g, stream=side):
-                        steps()
-                torch.cuda.current_stream().wait_stream(side)
+                with _capture(g):
+                    steps()
                 self._graphs[key] = g
             g.replay()
             self.graph = g

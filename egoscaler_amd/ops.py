@@ -457,6 +457,20 @@ def mm_kernel_id(a, b, out, a_layout=0, b_layout=0, accumulate=False):
     return _lib.lib().egomi_gemm_kernel_id(ctypes.byref(d))
 
 
+GEMM_FORMS = {0: "none", 1: "generic", 2: "128x128", 3: "256x128", 4: "gemv_m16", 5: "m256", 6: "8phase", 7: "persistent", 8: "tall",
+              9: "split", 10: "kmajor", 11: "kmajor_tall", 12: "kmajor_split"}
+
+
+def gemm_last_route():
+    """The route of this thread's most recent egomi_gemm (include/egomi.h egomi_gemm_last_route), as recorded by the launch that ran:
+    (form name, split-K slices, first K-sliced tail row, tail slices, column split Na)."""
+    out = (c_i * 4)()
+    form = _lib.lib().egomi_gemm_last_route(out)
+    if form < 0:
+        _lib.check(form, "egomi_gemm_last_route")
+    return (GEMM_FORMS[form],) + tuple(out)
+
+
 def swiglu_bwd(dact, gate, up, dgate, dup):
     rows, cols = gate.shape
     call("egomi_swiglu_bwd", P(dact), P(gate), P(up), P(dgate), P(dup), c_i64(rows), c_i(cols), c_i64(_ld(gate)), c_i64(_ld(dact)),

@@ -182,6 +182,16 @@ int egomi_gemm_tail_plan(const egomi_gemm_desc* desc, int* row0, int* slices);
  * rows [row0, M) egomi_gemm will compute as `slices` K-slices and sum in its own combine pass (ragged last round of 256x256 tiles);
  * slices = 0: none.  EGOMI_E_UNSUPPORTED when the descriptor does not take that kernel. */
 int egomi_gemm_tn_tail_plan(const egomi_gemm_desc* desc, int* row0, int* slices);
+/* The route the calling thread's most recent egomi_gemm took, as its launch functions recorded it (tests: a case asserts the form it was
+ * written for).  Returns the form code; out4 = {split-K slices (1 = none), first K-sliced tail row (M = none), tail slices (0 = none),
+ * column split Na (0 = none)}.  Form codes:
+ *   0 none (no egomi_gemm on this thread yet, or the last one launched nothing)   1 generic (gemm.hip)
+ *   2 128x128 (+ skinny split-K)     3 256x128     4 gemv_m16 (M <= 16)     5 m256 ring (128 < M <= 256)
+ *   6 256x256 8-phase, per tile (+ K-sliced tail rows)     7 256x256 8-phase, persistent     8 352x256
+ *   9 column split: 352x256 on columns [0, Na), 256x256 per tile on the rest
+ *  10 k-major 256x256 (gemm_tn.hip)     11 k-major 352x256     12 k-major column split (352x256 on [0, Na), 10 on the rest) */
+int egomi_gemm_last_route(int* out4);
+#define EGOMI_ROUTE_FORMS 13
 /* Measurement hooks (bench.py `roofline`; no reference counterpart).  egomi_gemm_time_next(start, stop): the NEXT egomi_gemm call
  * of this thread, if it takes the 256x256 kernel (egomi_gemm_kernel_id == 2), records `start` right before and `stop` right after
  * THAT kernel on the launch stream — the slab-combine pass of K-sliced tail rows is a separate kernel and lies outside the
