@@ -5,7 +5,7 @@
 //   models/pointllm/utils/utils.py:47-104 str_to_float (rt2, 6-DoF): split on <tsep>, first run of six
 //       <p*> tokens per segment, unmatched segments repeat the previous step
 //   models/pointllm/dataset.py:16-19,150-194 sequence layout  <ts> (p*6 <tsep>)*T <te> eos pad...
-//   models/utils/metrics.py:7-55          ADE / FDE (documented [T,D] form)
+//   models/utils/metrics.py:7-55          ADE / FDE (documented [T,D] form); best-of-K minima of them (minADE_K / minFDE_K)
 // The bin edges are computed once on the host in float64 exactly as numpy.linspace does and passed in.
 #include "common.h"
 #include <math.h>
@@ -101,6 +101,39 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const float* gen, cons
     fde[b] = lastd;
 }
 
+// best of K: gen [B, K, Tmax, D], n_gen [B, K]; per clip the minimum ADE and the minimum FDE over the samples with n_gen > 0 (each
+// computed as traj_metrics_kernel does), best = arg-min ADE (lowest index on ties); no such sample: NaN, NaN, -1
+__global__ __launch_bounds__(64) void traj_metrics_min_kernel(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int K,
+                                                              int Tmax, int D, double* min_ade, double* min_fde, int32_t* best) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const int nt = n_gt ? n_gt[b] : Tmax;
+    double ba = NAN, bf = NAN;
+    int bi = -1;
+    for (int j = 0; j < K && nt > 0; ++j) {
+        const int ng = n_gen ? n_gen[(long long)b * K + j] : Tmax;
+        if (ng <= 0) continue;
+        const float* g = gen + ((long long)b * K + j) * Tmax * D;
+        double acc = 0.0, lastd = 0.0;
+        for (int t = 0; t < nt; ++t) {
+            const int tg = t < ng ? t : ng - 1;
+            double s = 0.0;
+            for (int c = 0; c < D; ++c) {
+                const double df = (double)gt[((long long)b * Tmax + t) * D + c] - (double)g[(long long)tg * D + c];
+                s += df * df;
+            }
+            lastd = sqrt(s);
+            acc += lastd;
+        }
+        const double ade = acc / nt;
+        if (bi < 0 || ade < ba) { ba = ade; bi = j; }
+        if (!(bf <= lastd)) bf = lastd;                                    // first sample (bf NaN) or a smaller FDE
+    }
+    min_ade[b] = ba;
+    min_fde[b] = bf;
+    best[b] = bi;
+}
+
 extern "C" int egomi_traj_tokenize(const float* traj, const int32_t* steps, int B, int Tmax, const double* bins, int num_bins, int64_t p0,
                                    int64_t ts, int64_t tsep, int64_t te, int64_t eos, int64_t pad, int L, int64_t* ids, uint8_t* mask,
                                    int32_t* err, egomi_stream_t stream) {
@@ -123,5 +156,14 @@ extern "C" int egomi_traj_metrics(const float* gen, const int32_t* n_gen, const 
     if (!gen || !gt || !ade || !fde) return EGOMI_E_BADARG;
     if (B <= 0 || Tmax <= 0 || D <= 0) return EGOMI_E_SHAPE;
     EGOMI_LAUNCH(traj_metrics_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, gen, n_gen, gt, n_gt, B, Tmax, D, ade, fde);
+    return egomi_launch_status();
+}
+
+extern "C" int egomi_traj_metrics_min(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int K, int Tmax, int D,
+                                      double* min_ade, double* min_fde, int32_t* best, egomi_stream_t stream) {
+    if (!gen || !gt || !min_ade || !min_fde || !best) return EGOMI_E_BADARG;
+    if (B <= 0 || K <= 0 || Tmax <= 0 || D <= 0) return EGOMI_E_SHAPE;
+    EGOMI_LAUNCH(traj_metrics_min_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, gen, n_gen, gt, n_gt, B, K, Tmax, D, min_ade,
+                 min_fde, best);
     return egomi_launch_status();
 }

@@ -132,14 +132,27 @@ def attn_decode_rows_fp8(q, ld_q, kc, vc, ks, vs, kv_row, n_phys, key_mask, out,
          c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
 
 
+def attn_decode_shared(q, ld_q, kp, vp, key_mask, ks, vs, out, B, K, H, hd, Sp, S0, Tmax, T_len, scale):
+    """Attention of the B * K logical rows r = b * K + j over clip b's prompt cache kp / vp [B, H, Sp, hd] (keys 0 .. S0-1, key_mask
+    [B, >= S0]) and the row's own suffix cache ks / vs [B*K, H, Tmax, hd] (keys 0 .. T_len-1)  (include/egomi.h egomi_attn_decode_shared)."""
+    call("egomi_attn_decode_shared", P(q), c_i64(ld_q), P(kp), P(vp), P(key_mask), c_i64(key_mask.stride(0) if key_mask is not None else 0),
+         P(ks), P(vs), P(out), c_i64(out.stride(0)), c_i(B), c_i(K), c_i(H), c_i(hd), c_i(Sp), c_i(S0), c_i(Tmax), c_i(T_len), c_f(scale),
+         c_i(dt(q.dtype)), S())
+
+
 class Decoder:
-    def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None, weight_dtype=None):
+    def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None, weight_dtype=None, samples_per_prompt=1, max_new_tokens=None):
         """B = rows of the cache and of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...)).
         kv_dtype="fp8": the KV cache holds e4m3fn codes kc / vc uint8 [L, B, H, Smax, hd] and fp32 scales ks / vs [L, B, H, Smax], one per
         (layer, row, head, position) and tensor (csrc/kv8.hip); None: the model's dtype, as before.
         weight_dtype="fp8": step() runs the four projections of every layer (q|k|v, o_proj, gate|up, down_proj) on e4m3fn codes with one fp32
         scale per output row (W8A16, csrc/w8.hip; self.w8); lm_head, the embeddings and the norms keep the model's dtype, and prefill runs
-        on the bf16 weights.  bf16 engines and B <= 512 only; None: the model's weights, as before."""
+        on the bf16 weights.  bf16 engines and B <= 512 only; None: the model's weights, as before.
+        samples_per_prompt = K > 1 (best-of-K sampling; needs max_new_tokens = Tmax): the B rows are K samples of each of B / K prompts,
+        row r = b * K + j.  The cache is a prompt cache kp / vp [L, B / K, H, Sp, hd] (Sp = max_len - Tmax, one row per PROMPT, filled by one
+        prefill per prompt) plus a suffix cache ksfx / vsfx [L, B, H, Tmax, hd] (the tokens each row generated) instead of
+        [L, B, H, max_len, hd]; step() attends over both with egomi_attn_decode_shared (csrc/shared.hip).  sample() / greedy() are unchanged:
+        same rows, same seed, same draws as the expanded decoder."""
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', not {kv_dtype!r}")
         if weight_dtype not in (None, "fp8"):
@@ -148,13 +161,36 @@ class Decoder:
             raise ValueError(f"fp8 decode weights need a bf16 model, not {engine.dtype}")
         if weight_dtype == "fp8" and B > 512:
             raise ValueError(f"fp8 decode weights support at most 512 decoder rows, not {B}")
+        K = int(samples_per_prompt)
+        if K != 1:
+            if not 1 < K <= 32:
+                raise ValueError(f"samples_per_prompt must be between 1 and 32, not {samples_per_prompt}")
+            if int(num_beams) != 1:
+                raise NotImplementedError("samples_per_prompt > 1 with num_beams > 1 is not built")
+            if kv_dtype == "fp8":
+                raise NotImplementedError("samples_per_prompt > 1 with an fp8 KV cache is not built")
+            if B % K:
+                raise ValueError(f"{B} decoder rows are not a multiple of samples_per_prompt = {K}")
+            if max_new_tokens is None or not 0 < int(max_new_tokens) < max_len:
+                raise ValueError("samples_per_prompt > 1 needs max_new_tokens (the suffix cache length) in 1 .. max_len - 1")
         self.eng, self.B, self.Smax, self.nb, self.kv_dtype = engine, B, max_len, int(num_beams), kv_dtype
+        self.K = K
         lm = engine.dims.lm
         L, H, hd, d, Fd, V = lm.num_hidden_layers, lm.num_attention_heads, lm.head_dim, lm.hidden_size, lm.intermediate_size, lm.vocab_size
         T, dev = engine.dtype, engine.device
         self.fp8 = kv_dtype == "fp8"
-        self.kc = torch.zeros(L, B, H, max_len, hd, dtype=torch.uint8 if self.fp8 else T, device=dev)
-        self.vc = torch.zeros_like(self.kc)
+        if K > 1:
+            self.Tmax = int(max_new_tokens)
+            self.Sp = max_len - self.Tmax
+            self.kc = self.vc = None
+            self.kp = torch.zeros(L, B // K, H, self.Sp, hd, dtype=T, device=dev)
+            self.vp = torch.zeros_like(self.kp)
+            self.ksfx = torch.zeros(L, B, H, self.Tmax, hd, dtype=T, device=dev)
+            self.vsfx = torch.zeros_like(self.ksfx)
+            self.S0 = 0
+        else:
+            self.kc = torch.zeros(L, B, H, max_len, hd, dtype=torch.uint8 if self.fp8 else T, device=dev)
+            self.vc = torch.zeros_like(self.kc)
         self.ks = torch.zeros(L, B, H, max_len, dtype=torch.float32, device=dev) if self.fp8 else None
         self.vs = torch.zeros_like(self.ks) if self.fp8 else None
         z = lambda *s, dtype=T: torch.zeros(*s, dtype=dtype, device=dev)
@@ -202,8 +238,12 @@ class Decoder:
                           "down": ops.mm_w8_slabs(self.act, *q["down"], self.gws, count_only=True)}
             if not all(self.fused.values()):
                 raise ValueError(f"fp8 decode weights cannot run this model's projection shapes ({self.fused})")
+            if K > 1:
+                self.fused["qkv"] = 0
         elif T == torch.bfloat16 and os.environ.get("EGOMI_DECODE_FUSED", "1") != "0" and B <= 512:
-            self.fused["qkv"] = ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
+            # shared-prompt mode rotates at S0 + t but appends at suffix slot t; egomi_qkv_finish takes one `pos` for both, so its q|k|v
+            # product keeps the unfused mm + rope_ + kv_append path
+            self.fused["qkv"] = 0 if K > 1 else ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
             self.fused["o"] = ops.mm_slabs(self.ao, w["model.layers.0.self_attn.o_proj.weight"], self.x_mid, self.gws, count_only=True)
             self.fused["down"] = ops.mm_slabs(self.act, w["model.layers.0.mlp.down_proj.weight"], self.x, self.gws, count_only=True)
 
@@ -262,6 +302,8 @@ class Decoder:
             raise ValueError("prompt + new tokens exceed the decoder's cache length")
         if B * nb != self.B:
             raise ValueError(f"{B} prompts x {nb} beams do not fill the decoder's {self.B} rows")
+        if self.K > 1 and (S0 > self.Sp or total_new > self.Tmax):
+            raise ValueError(f"prompt length {S0} / {total_new} new tokens exceed the decoder's prompt cache ({self.Sp}) / suffix cache ({self.Tmax})")
         if nb > 1:
             input_ids, mask = input_ids.repeat_interleave(nb, 0), mask.repeat_interleave(nb, 0)
         self.mask_buf.fill_(1)
@@ -275,11 +317,16 @@ class Decoder:
         d = self.eng.dims.lm.hidden_size
         self._append(l, None, qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), B, Sq, 0)
 
-    def _append(self, l, b, k, v, ld, B, Sq, pos0):
-        """k / v rows -> layer l of the cache (all rows, or row b alone) at positions pos0 .. pos0 + Sq - 1."""
+    def _append(self, l, b, k, v, ld, B, Sq, pos0, suffix=False):
+        """k / v rows -> layer l of the cache (all rows, or row b alone) at positions pos0 .. pos0 + Sq - 1.  Shared-prompt mode: the
+        prompt cache (prefill: rows are prompts), or with suffix=True the suffix cache (step: rows are samples, pos0 = suffix slot)."""
         lm = self.eng.dims.lm
         H, hd = lm.num_attention_heads, lm.head_dim
         sel = (l,) if b is None else (l, b)
+        if self.K > 1:
+            kc, vc, Smax = (self.ksfx, self.vsfx, self.Tmax) if suffix else (self.kp, self.vp, self.Sp)
+            kv_append(k, v, ld, kc[sel], vc[sel], B, Sq, H, hd, Smax, pos0)
+            return
         if self.fp8:
             kv_append_fp8(k, v, ld, self.kc[sel], self.vc[sel], self.ks[sel], self.vs[sel], B, Sq, H, hd, self.Smax, pos0)
         else:
@@ -290,13 +337,23 @@ class Decoder:
         self.lg, which every beam of the item reads at step 0 (HF expands to B * nb identical rows and prefills them all)."""
         B, S0 = input_ids.shape
         dev = self.eng.device
+        if self.K > 1:
+            nb = self.K
         mask = torch.ones(B, S0, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
         self._set_inputs(input_ids, mask, total_new, nb)
         hn = self.eng.forward_hidden(input_ids, mask, point_clouds, fps_start, save=False, kv_sink=self._sink)
         self.pos = S0
         last = hn.view(B, S0, -1)[:, -1].contiguous()
         ops.mm(last, self.eng.w["lm_head.weight"], out=self.lg[:B])
-        return self.lg[:B]
+        return self._share_logits(B, S0)
+
+    def _share_logits(self, B, S0):
+        """Shared-prompt mode: every sample of a prompt starts from the prompt's step-0 logits (HF prefills K identical rows)."""
+        if self.K == 1:
+            return self.lg[:B]
+        self.S0 = S0
+        self.lg.copy_(self.lg[:B].repeat_interleave(self.K, 0))
+        return self.lg
 
     def prefill_chunked(self, input_ids, attention_mask, point_clouds, fps_start, total_new, chunk=16, nb=1):
         """prefill() for large batches (config 5: bs=256): the prompt pass runs `chunk` samples at a time (its activations are
@@ -304,6 +361,8 @@ class Decoder:
         B, S0 = input_ids.shape
         eng, dev = self.eng, self.eng.device
         d = eng.dims.lm.hidden_size
+        if self.K > 1:
+            nb = self.K
         mask = torch.ones(B, S0, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
         self._set_inputs(input_ids, mask, total_new, nb)
         for b0 in range(0, B, chunk):
@@ -318,7 +377,7 @@ class Decoder:
             last = hn.view(b1 - b0, S0, -1)[:, -1].contiguous()
             ops.mm(last, eng.w["lm_head.weight"], out=self.lg[b0:b1])
         self.pos = S0
-        return self.lg[:B]
+        return self._share_logits(B, S0)
 
     # -- one decode step on static buffers: consumes self.tok, leaves logits in self.lg ---------------------
     def step(self, pos):
@@ -341,10 +400,19 @@ class Decoder:
                 else:
                     ops.qkv_finish(self.gws, n, self.qkv, eng.cos, eng.sin, pos, self.kc[l], self.vc[l], B, H, hd, self.Smax)
             else:
-                ops.mm(self.h, self.wqkv[l], out=self.qkv, workspace=self.gws)
+                if self.w8 is not None:                     # (shared-prompt mode: the only unfused q|k|v product on fp8 weights)
+                    ops.mm_w8(self.h, *self.w8[l]["qkv"], out=self.qkv, workspace=self.gws)
+                else:
+                    ops.mm(self.h, self.wqkv[l], out=self.qkv, workspace=self.gws)
                 ops.rope_(self.qkv, eng.cos, eng.sin, B, 1, pos, 2 * H, hd, 3 * d)
-                self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos)
-            if self.fp8 and self.kv_row is None:
+                if self.K > 1:
+                    self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos - self.S0, suffix=True)
+                else:
+                    self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos)
+            if self.K > 1:
+                attn_decode_shared(self.qkv, 3 * d, self.kp[l], self.vp[l], self.mask[::self.K], self.ksfx[l], self.vsfx[l], self.ao, B // self.K,
+                                   self.K, H, hd, self.Sp, self.S0, self.Tmax, pos - self.S0 + 1, scale)
+            elif self.fp8 and self.kv_row is None:
                 attn_decode_fp8(self.qkv, 3 * d, self.kc[l], self.vc[l], self.ks[l], self.vs[l], self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
             elif self.fp8:
                 attn_decode_rows_fp8(self.qkv, 3 * d, self.kc[l], self.vc[l], self.ks[l], self.vs[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd,

@@ -141,7 +141,7 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
 
 
 @torch.no_grad()
-def run_validation(model, data, args, device, max_batches=None, num_beams=1):
+def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None):
     """Generation + metrics on the rank's shard (train.py:207-264, evaluate.py:104-154): prompts up to the first <tsep>,
     `generate` of the remaining positions (sampling with the reference's defaults top_k 50 / top_p 0.95 / T 1.0 unless
     args.val_sample is False -> greedy), cut at eos, de-tokenise, de-normalise (dataset.denorm), pad with the last step,
@@ -151,14 +151,25 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1):
     drivers log (they pass [1,T,6], so the norm runs over TIME: SURVEY.md §0.1); 'GD' is metrics.py:61-87 on the rotation
     vectors [T,3] (the reference's own call passes [1,T,6] and raises inside scipy).
 
-    num_beams > 1 (eval only): beam search (or beam sampling with the sampling flags) with one returned hypothesis per sample, the best."""
+    num_beams > 1 (eval only): beam search (or beam sampling with the sampling flags) with one returned hypothesis per sample, the best.
+
+    num_samples = K > 1 (default: args.num_samples, else 1): K sampled trajectories per clip from ONE prefill and one cached prompt per clip
+    (generate(num_return_sequences=K, share_prompt=True)); sampling only, not with num_beams > 1.  'ADE' / 'FDE' / 'ADE_as_called' / 'GD' /
+    'n' are those of sample 0 of every clip, computed as with K = 1; the record gains 'minADE' / 'minFDE' (best-of-K, T.metrics_best_of;
+    means over the 'n_min' clips with at least one parsed sample) and 'K', and the dump holds the K trajectories per image id (None for
+    an unparsed one).  K = 1 is the single-draw path unchanged."""
     dims = model.dims
+    K = int(num_samples if num_samples is not None else (getattr(args, "num_samples", 1) or 1))
+    if K < 1:
+        raise ValueError(f"num_samples has to be a strictly positive integer, but is {K}")
+    if K > 1 and (num_beams != 1 or not bool(getattr(args, "val_sample", True))):
+        raise ValueError("num_samples > 1 draws samples: it cannot be combined with --val_greedy or --num_beams > 1")
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
     sample = bool(getattr(args, "val_sample", True))
     per = micro_batch_per_rank(args.bs, 1, world)
     model.eval()
-    sums = np.zeros(5)                                   # ADE, FDE, ADE_as_called, GD, n
+    sums = np.zeros(8)                                   # ADE, FDE, ADE_as_called, GD, n; best-of-K: minADE, minFDE, n_min
     dump = {}
     # the reference's val / test DataLoader (train.py:79-82, evaluate.py:93-100: batch_size=bs, shuffle=False, NO drop_last) keeps the
     # short last batch: every sample is generated for and lands in the dump.  A batch is dealt over the ranks; the short one is split
@@ -175,11 +186,14 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1):
         prompts, tokens = batch["prompts"], batch["tokens"]
         max_new = tokens.shape[1] - prompts.shape[1]
         beam = {} if num_beams == 1 else {"num_beams": num_beams}
+        if K > 1:
+            beam = {"num_return_sequences": K, "share_prompt": True}
         out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"], max_length=max_new,
                              do_sample=sample, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device),
                              kv_cache_dtype=getattr(args, "kv_cache_dtype", None),
                              decode_weight_dtype=getattr(args, "decode_weight_dtype", None), **beam)
-        gen_ids = out.sequences[:, prompts.shape[1]:]
+        all_ids = out.sequences[:, prompts.shape[1]:]
+        gen_ids = all_ids[::K]                                                  # sample 0 of every clip (K = 1: every row)
         # the prompt holds the first step; prepend its six tokens + <tsep> so step 0 is parsed like the rest
         vals, n = T.detokenize_batch(torch.cat([prompts[:, -7:], gen_ids], 1), dims.tok, args.num_steps + 4)
         gt = batch["trajectories"]
@@ -197,9 +211,24 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1):
         for j in range(len(idx)):
             if n_h[j] <= 0:
                 continue                                                     # detokenize_traj returned None (train.py:249-250)
-            sums += [ade[j], fde[j], T.average_displacement_error(gen[j][None], gt_h[j][None]),
+            sums[:5] += [ade[j], fde[j], T.average_displacement_error(gen[j][None], gt_h[j][None]),
                      T.anglar_distance(gen[j][:, 3:6].astype(np.float64), gt_h[j][:, 3:6].astype(np.float64)), 1.0]
             dump[int(ids_h[j])] = gen[j].tolist()                            # evaluate.py:150: keyed by image_id.item(), not by the dataset index
+        if K > 1:                                                            # all K samples of every clip: rows b * K + j
+            vals, n = T.detokenize_batch(torch.cat([prompts[:, -7:].repeat_interleave(K, 0), all_ids], 1), dims.tok, args.num_steps + 4)
+            n = torch.clamp(n, max=Tn)
+            vals_h, n_h = vals[:, :Tn].cpu().numpy(), n.cpu().numpy()
+            for r in range(len(idx) * K):
+                if 0 < n_h[r] < Tn:
+                    vals_h[r, n_h[r]:] = vals_h[r, n_h[r] - 1]
+            gen = norm.denorm(vals_h, np.repeat(batch["max_abs"].cpu().numpy(), K, axis=0))
+            gen_d = torch.from_numpy(np.ascontiguousarray(gen, dtype=np.float32)).to(device)
+            made, mfde, best = T.metrics_best_of(gen_d.view(len(idx), K, Tn, -1), (n > 0).to(torch.int32).view(len(idx), K) * Tn, gt)
+            made, mfde, best = made.cpu().numpy(), mfde.cpu().numpy(), best.cpu().numpy()
+            for j in range(len(idx)):
+                if best[j] >= 0:
+                    sums[5:8] += [made[j], mfde[j], 1.0]
+                dump[int(ids_h[j])] = [gen[j * K + i].tolist() if n_h[j * K + i] > 0 else None for i in range(K)]
     if world > 1:
         t = torch.from_numpy(sums).to(device)
         dist.all_reduce(t)
@@ -208,7 +237,11 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1):
     k = max(sums[4], 1.0)
     nan = float("nan")
     mean = lambda i: float(sums[i] / k) if sums[4] else nan            # plain floats: the records go into checkpoints read with weights_only=True
-    return {"ADE": mean(0), "FDE": mean(1), "ADE_as_called": mean(2), "GD": mean(3), "n": int(sums[4])}, dump
+    rec = {"ADE": mean(0), "FDE": mean(1), "ADE_as_called": mean(2), "GD": mean(3), "n": int(sums[4])}
+    if K > 1:
+        rec.update({"minADE": float(sums[5] / sums[7]) if sums[7] else nan, "minFDE": float(sums[6] / sums[7]) if sums[7] else nan,
+                    "n_min": int(sums[7]), "K": K})
+    return rec, dump
 
 
 def train(args, model, train_data, val_data=None, device="cuda", log=print, step_log=None):
@@ -342,7 +375,8 @@ def evaluate(args, model, data, split="test", device="cuda"):
     norm = getattr(data, "norm", None)
     if norm is not None and norm.mode == "standard" and norm.mean is None:
         norm.load(args.checkpoint_dir)
-    metrics, dump = run_validation(model, data, args, device, num_beams=int(getattr(args, "num_beams", 1)))
+    metrics, dump = run_validation(model, data, args, device, num_beams=int(getattr(args, "num_beams", 1)),
+                                   num_samples=int(getattr(args, "num_samples", 1) or 1))
     rank, world = _rank_world()
     if world > 1:
         parts = [None] * world
@@ -386,6 +420,9 @@ def parse_args(argv=None):
                     help="validate with greedy decoding instead of the reference's sampling defaults (model_arch.py:82-88)")
     ap.add_argument("--num_beams", type=int, default=1,
                     help="eval mode: beam search with N beams (beam sampling unless --val_greedy); the dump keeps the best hypothesis per image")
+    ap.add_argument("--num_samples", type=int, default=1,
+                    help="validation / eval: K sampled trajectories per clip from one prefill and one cached prompt per clip; adds best-of-K "
+                         "minADE / minFDE to the record and keeps all K in the dump (not with --val_greedy or --num_beams > 1)")
     ap.add_argument("--kv_cache_dtype", default="auto", choices=["auto", "fp8"],
                     help="KV cache of every generate() call in validation / eval: the model's dtype (auto) or e4m3fn codes with per-(token, head) scales")
     ap.add_argument("--decode_weight_dtype", default="auto", choices=["auto", "fp8"],

@@ -555,7 +555,7 @@ class TrajPointLLMForCausalLM(nn.Module):
     def generate(self, input_ids=None, attention_mask=None, point_clouds=None, max_length=20, temperature=1.0, top_k=50,
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
                  eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
-                 decode_weight_dtype=None, **kwargs):
+                 decode_weight_dtype=None, share_prompt=False, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -582,7 +582,25 @@ class TrajPointLLMForCausalLM(nn.Module):
         (decode.Decoder(weight_dtype="fp8"), csrc/w8.hip): half the weight bytes every decode step streams.  lm_head, the embeddings and the
         norms keep the model's dtype.  Applies to every mode and either kv_cache_dtype; bf16 models with at most 512 decoder rows
         (batch x num_beams) only.  The prefill runs on the bf16 weights, so the prefill logits (step 0) are those of the bf16 run; only
-        the later steps read the fp8 weights."""
+        the later steps read the fp8 weights.
+
+        share_prompt=True with num_return_sequences = K > 1 and num_beams == 1 (best-of-K sampling): same outputs, shapes and row order
+        (row b * K + j = sample j of prompt b) as the default, but every prompt is prefilled ONCE and its K/V are kept once: the decoder holds
+        a prompt cache [L, B, H, S0, hd] plus a suffix cache [L, B*K, H, max_length, hd], and every step's attention reads a prompt's K/V once
+        for its K samples (decode.Decoder(samples_per_prompt=K), csrc/shared.hip).  The draws of row r are those of the default path (same
+        seed, same row numbering), but the attention sums in another order, so logits differ in their last bits and a sampled token can
+        differ at a near-tie; hence the default stays False.  1 <= K <= 32 (K = 1 is the default path); not with num_beams > 1, a list of
+        ragged clouds or kv_cache_dtype="fp8"; decode_weight_dtype="fp8" and LoRA adapters work as in the default path."""
+        share = bool(share_prompt) and int(num_return_sequences) > 1
+        if share_prompt:
+            if int(num_beams) > 1:
+                raise NotImplementedError("share_prompt=True with num_beams > 1 is not built (beam search already prefills each prompt once)")
+            if isinstance(point_clouds, (list, tuple)):
+                raise NotImplementedError("share_prompt=True with a list of ragged clouds is not built")
+            if kv_cache_dtype == "fp8":
+                raise NotImplementedError("share_prompt=True with kv_cache_dtype='fp8' is not built")
+            if int(num_return_sequences) > 32:
+                raise ValueError(f"share_prompt=True supports at most 32 return sequences, not {num_return_sequences}")
         if kv_cache_dtype not in (None, "auto", "fp8"):
             raise ValueError(f"`kv_cache_dtype` must be None, 'auto' or 'fp8', but is {kv_cache_dtype!r}")
         kv = "fp8" if kv_cache_dtype == "fp8" else None
@@ -609,7 +627,7 @@ class TrajPointLLMForCausalLM(nn.Module):
             return self._generate_beam(ids, attention_mask, point_clouds, fps_start, int(max_length), nb, n_ret, float(length_penalty),
                                        early_stopping, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id,
                                        seed, kwargs.get("use_graph", True), kv, wd)
-        if n_ret > 1:                                      # HF expands every input n times (generation/utils.py _expand_inputs_for_generation)
+        if n_ret > 1 and not share:                        # HF expands every input n times (generation/utils.py _expand_inputs_for_generation)
             if isinstance(point_clouds, (list, tuple)):
                 raise NotImplementedError("num_return_sequences > 1 with a list of ragged clouds is not built")
             ids = ids.repeat_interleave(n_ret, 0)
@@ -618,6 +636,8 @@ class TrajPointLLMForCausalLM(nn.Module):
             fps_start = None if fps_start is None else torch.as_tensor(fps_start).to(dev).repeat_interleave(n_ret, 0)
         B, S0 = ids.shape
         T = int(max_length)
+        if share and T < 1:
+            raise ValueError("share_prompt=True needs max_length >= 1")
         if isinstance(eos_token_id, str):
             eos_token_id = self.dims.tok.eos
         if eos_token_id is not None and pad_token_id is None:
@@ -630,8 +650,16 @@ class TrajPointLLMForCausalLM(nn.Module):
         # one Decoder (static KV cache + captured token loops) per geometry, kept while the decoder layers it holds stacked copies of cannot
         # change: frozen-LLM mode, same prepared weights.  run_validation / evaluate (train.py:207-264, evaluate.py:104-154) call generate()
         # once per batch: without this every batch re-allocated the cache and re-captured a graph of (new tokens x ~300) kernels
-        dec = self._decoder(B, S0 + T, kv=kv, wd=wd)
-        dec.prefill(ids, attention_mask, point_clouds, fps_start, T)
+        if share:                                          # B prompts, B * n_ret decoder rows: one prefill and one cached K/V per prompt
+            dec = self._decoder(B * n_ret, S0 + T, kv=kv, wd=wd, share=(n_ret, T))
+            if B > 16:
+                dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=16)
+            else:
+                dec.prefill(ids, attention_mask, point_clouds, fps_start, T)
+            B = B * n_ret
+        else:
+            dec = self._decoder(B, S0 + T, kv=kv, wd=wd)
+            dec.prefill(ids, attention_mask, point_clouds, fps_start, T)
         if not do_sample:                                  # HF applies the warpers (temperature / top-k / top-p) in sampling mode only
             temperature, top_k, top_p = 1.0, 0, 1.0
         seq, sc = dec.sample(T, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
@@ -644,21 +672,26 @@ class TrajPointLLMForCausalLM(nn.Module):
         sc = sc[:stop].clone()                              # the decoder's buffers are static (and the decoder may be reused by the next call):
         return GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
 
-    def _decoder(self, B, max_len, nb=1, kv=None, wd=None):
+    def _decoder(self, B, max_len, nb=1, kv=None, wd=None, share=None):
         """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER
         prepare(): load_state_dict() / _apply() leave the engine unprepared (or replace it), and a decoder made before them holds stacked
         copies of the old weights and the old RoPE tables.  It also holds the KV dtype and the decode weight dtype: a bf16 and an fp8 decoder never
-        stand in for each other."""
+        stand in for each other.  share = (K, Tmax): the shared-prompt decoder of K samples per prompt; the key holds the mode and K."""
         from ..decode import Decoder
         eng = self.engine
         if not eng.prepared:
             eng.prepare()
         key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv, wd, eng.lora_key())     # adapters: merged decode copies of their values
+        if share is not None:
+            key = key + ("share",) + tuple(share)
         cache = self.__dict__.setdefault("_decoders", {})
         reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
         dec = cache.get(key) if reuse else None
         if dec is None:
-            dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv, weight_dtype=wd)
+            if share is not None:
+                dec = Decoder(eng, B, max_len, kv_dtype=kv, weight_dtype=wd, samples_per_prompt=share[0], max_new_tokens=share[1])
+            else:
+                dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv, weight_dtype=wd)
             if reuse:
                 while len(cache) >= 2:                     # the full batch and the split's short last one; a cache is 2 * L * B * H * Smax * hd elements
                     cache.pop(next(iter(cache)))

@@ -74,6 +74,30 @@ def metrics_batch(gen, n_gen, gt, n_gt=None):
     return ade, fde
 
 
+def metrics_best_of(gen, n_gen, gt, n_gt=None):
+    """Best-of-K metrics per clip (float64, on the device): gen [B, K, T, D], n_gen [B, K] or None, gt [B, T, D], n_gt [B] or None ->
+    (min_ade [B], min_fde [B], best [B] int32).  Every sample is scored as metrics_batch scores it; a sample with n_gen <= 0 (nothing
+    parsed) takes no part.  best = arg-min of ADE over the others (lowest index on ties), -1 with NaN metrics when none is left;
+    min_fde is the minimum FDE over the samples, not the FDE of `best`."""
+    gen, gt = gen.to(torch.float32).contiguous(), gt.to(torch.float32).contiguous()
+    B, T, D = gt.shape
+    if gen.dim() != 4 or gen.shape[0] != B or tuple(gen.shape[2:]) != (T, D):
+        raise ValueError("gen must be [B,K,T,D] for gt [B,T,D]")
+    K = gen.shape[1]
+    if K < 1:
+        raise ValueError("gen holds no sample")
+    if n_gen is not None and tuple(n_gen.shape) != (B, K):
+        raise ValueError("n_gen must be [B,K]")
+    dev = gt.device
+    min_ade = torch.empty(B, dtype=torch.float64, device=dev)
+    min_fde = torch.empty(B, dtype=torch.float64, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
+    nt = None if n_gt is None else n_gt.to(torch.int32).contiguous()
+    call("egomi_traj_metrics_min", P(gen), P(ng), P(gt), P(nt), c_i(B), c_i(K), c_i(T), c_i(D), P(min_ade), P(min_fde), P(best), S())
+    return min_ade, min_fde, best
+
+
 # ------------------------------------------------------------------------------------------ host
 def discretize_action(action_vector, num_bins=256):
     """utils/utils.py:13-16."""

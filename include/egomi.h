@@ -315,6 +315,19 @@ int egomi_beam_update(int B, int nb, int K, int V, const float* cand_key, const 
 int egomi_attn_decode_rows(const void* q, int64_t ld_q, const void* kcache, const void* vcache, const int32_t* kv_row, int64_t ld_kv,
                            int n_phys, const uint8_t* key_mask, int64_t ld_mask, void* out, int64_t ld_o, int B, int nb, int H, int hd,
                            int Smax, int T_len, float scale, int dtype, egomi_stream_t stream);
+/* Shared-prompt decode attention (csrc/shared.hip): best-of-K sampling without HF's _expand_inputs_for_generation (generation/utils.py,
+ * reached from models/pointllm/model_arch.py:94-108 with num_return_sequences = K), which repeats every prompt K times in the batch and
+ * in the KV cache.  Logical rows r = b * K + j (clip b, sample j), 1 <= K <= 32.
+ *   kprompt, vprompt [B, H, Sp, hd]     one row per CLIP, keys 0 .. S0-1; key_mask [B, >= S0] u8 (1 = visible) or NULL
+ *   ksuffix, vsuffix [B*K, H, Tmax, hd] one row per logical row, keys 0 .. T_len-1 (the tokens the row generated; T_len = 0: may be NULL)
+ *   out[r] = attention of q[r] over (prompt keys of clip r / K, then the row's suffix keys): what egomi_attn_decode gives on the
+ *            physically concatenated cache of row r.  q [B*K, H*hd] (16-B aligned rows), out [B*K, H*hd]; a row that sees no key gives 0.
+ * One workgroup per (clip, head) serves all K queries, so every prompt K/V element is loaded once per (clip, head) and launch (bf16 at
+ * hd 64 / 128: MFMA; otherwise VALU over an LDS-staged tile).  Fixed summation order: replays are bit-equal, and a row's result does not
+ * depend on its slot j.  dtype EGOMI_BF16 / EGOMI_F32, hd in {32, 64, 128} (EGOMI_E_UNSUPPORTED otherwise). */
+int egomi_attn_decode_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask, int64_t ld_mask,
+                             const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0,
+                             int Tmax, int T_len, float scale, int dtype, egomi_stream_t stream);
 
 /* FP8 (OCP e4m3fn) KV cache (csrc/kv8.hip): codes uint8 [B, H, Smax, hd] per layer (the bf16 cache's layout), scales fp32 [B, H, Smax]
  * per layer; hd in {32, 64, 128} (EGOMI_E_UNSUPPORTED otherwise); codes 8-B (attention: 16-B) aligned, scales 4-B aligned.  Per (row, head, position)
@@ -401,6 +414,13 @@ int egomi_traj_detokenize(const int64_t* ids, int B, int L, const double* bins, 
                           int Tmax, float* out, int32_t* n_steps, egomi_stream_t stream);
 int egomi_traj_metrics(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int Tmax, int D, double* ade,
                        double* fde, egomi_stream_t stream);
+/* metrics_min: best-of-K (minADE_K / minFDE_K; the reference's run_validation, train.py:207-264, scores one draw per clip with
+ *              models/utils/metrics.py:7-55).  gen f32 [B,K,Tmax,D], n_gen i32 [B,K] (NULL = Tmax), gt f32 [B,Tmax,D], n_gt i32 [B] (NULL = Tmax)
+ *              -> min_ade, min_fde float64 [B], best i32 [B].  Every sample is scored as `metrics` scores it; samples with n_gen <= 0 take no
+ *              part; best = arg-min ADE (lowest index on ties); min_fde is the minimum over the samples, not the FDE of `best`; no sample
+ *              left (or n_gt <= 0): NaN, NaN, -1. */
+int egomi_traj_metrics_min(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int K, int Tmax, int D,
+                           double* min_ade, double* min_fde, int32_t* best, egomi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Trainable point backbone (--unfreeze_pc_encoder, models/pointllm/model_arch.py:33-36): the backward
