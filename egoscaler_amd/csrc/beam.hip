@@ -1,5 +1,5 @@
 // Beam search and beam sampling on the device (A13): HF GenerationMixin._beam_search (transformers 5.15 generation/utils.py:3208-3560)
-// as two launches per step plus an attention kernel that reads the KV cache through a per-row table.
+// as two launches per step; attention reads the KV cache through the per-row table they maintain (attn_decode.hip, ROWS).
 //
 // Rows are LOGICAL beams r = b * nb + j (item b, beam j).  Per step:
 //   beam_rows   (one 1024-thread workgroup per row, the row in registers as in sample_rows_kernel):
@@ -14,7 +14,7 @@
 //               sequences, beam-index history and KV row tables are gathered in place (a workgroup owns all rows of its item).
 //               ctl[0] is the loop-open flag: once a step closes it, every later launch of both kernels returns at once, so a captured
 //               loop of T steps replays HF's data-dependent number of iterations exactly (ctl[1] counts them).
-//   attn_decode_rows: attn_decode_kernel's arithmetic, key t of row r read from physical cache row kv_row[r, t].  Prompt positions of
+//   attn_decode_rows (attn_decode.hip): key t of row r is read from physical cache row kv_row[r, t].  Prompt positions of
 //               every beam point at its item's single prompt row, later positions at the row that computed the token, so a reorder
 //               moves no K/V bytes and no referenced slot is ever overwritten (a step writes slot `pos` of each row's own physical row).
 #include "common.h"
@@ -452,120 +452,5 @@ extern "C" int egomi_beam_update(int B, int nb, int K, int V, const float* cand_
     a.kv_row = kv_row; a.ld_kv = ld_kv; a.run_score = run_score; a.fin_score = fin_score; a.fin_flag = fin_flag; a.heur = heur; a.tok = tok;
     a.ctl = ctl;
     EGOMI_LAUNCH(beam_update_kernel, dim3(B), dim3(BU_THREADS), 0, (hipStream_t)stream, a);
-    return egomi_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
-// attn_decode_rows: attn_decode_kernel with key t of logical row r read from physical row kv_row[r, t] of the [n_phys, H, Smax, hd]
-// caches.  Block order (item, head, beam): the nb beams of an item read the same prompt rows back to back, so the shared prompt comes
-// from HBM once and from L2 / MALL for the other beams.  A table entry outside [0, n_phys) is treated as a masked key (never read).
-// ------------------------------------------------------------------------------------------------
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_decode_rows_kernel(const T* q, long long ld_q, const T* kc, const T* vc, const int* kv_row,
-                                                               long long ld_kv, int n_phys, const uint8_t* key_mask, long long ld_mask, T* out,
-                                                               long long ld_o, int H, int nb, int Smax, int Tlen, float scale) {
-    constexpr int DPL = HD / 4;
-    __shared__ float sm_m[4], sm_l[4];
-    __shared__ float sm_acc[4][HD];
-    const int j = blockIdx.x % nb, h = (blockIdx.x / nb) % H, bi = blockIdx.x / (nb * H);
-    const int b = bi * nb + j;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int part = lane & 3, kslot = lane >> 2;
-    float qv[DPL];
-#pragma unroll
-    for (int c = 0; c < DPL / 8; ++c) {
-        float t[8];
-        load8<T>(q + (long long)b * ld_q + (long long)h * HD + part * DPL + c * 8, t);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) qv[c * 8 + i] = t[i] * scale;
-    }
-    const int* rows = kv_row + (long long)b * ld_kv;
-    float m = -INFINITY, l = 0.f, acc[DPL];
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
-    for (int k0 = wave * 16; k0 < Tlen; k0 += 64) {
-        const int key = k0 + kslot;
-        bool ok = key < Tlen;
-        const int kr = key < Tlen ? key : Tlen - 1;
-        int pr = rows[kr];
-        if (pr < 0 || pr >= n_phys) { ok = false; pr = 0; }
-        if (ok && key_mask) ok = key_mask[(long long)b * ld_mask + key] != 0;
-        const long long off = (((long long)pr * H + h) * Smax + kr) * HD + part * DPL;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < DPL / 8; ++c) {
-            float t[8];
-            load8<T>(kc + off + c * 8, t);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) s += t[i] * qv[c * 8 + i];
-        }
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        s = ok ? s : -INFINITY;
-        float mx = s;
-#pragma unroll
-        for (int o = 4; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        const float m_new = fmaxf(m, mx);
-        const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = m == -INFINITY ? 0.f : __expf(m - m_safe);
-        const float p = ok ? __expf(s - m_safe) : 0.f;
-        float ps = p;
-#pragma unroll
-        for (int o = 4; o < 64; o <<= 1) ps += __shfl_xor(ps, o, 64);
-        l = l * alpha + ps;
-        m = m_new;
-#pragma unroll
-        for (int c = 0; c < DPL / 8; ++c) {
-            float t[8];
-            load8<T>(vc + off + c * 8, t);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[c * 8 + i] = acc[c * 8 + i] * alpha + p * t[i];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) {
-        float v = acc[i];
-#pragma unroll
-        for (int o = 4; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-        acc[i] = v;
-    }
-    if (lane < 4) {
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) sm_acc[wave][lane * DPL + i] = acc[i];
-        if (lane == 0) { sm_m[wave] = m; sm_l[wave] = l; }
-    }
-    __syncthreads();
-    if (threadIdx.x < HD) {
-        float mm = fmaxf(fmaxf(sm_m[0], sm_m[1]), fmaxf(sm_m[2], sm_m[3]));
-        const float ms = mm == -INFINITY ? 0.f : mm;
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float f = sm_m[w] == -INFINITY ? 0.f : __expf(sm_m[w] - ms);
-            num += f * sm_acc[w][threadIdx.x];
-            den += f * sm_l[w];
-        }
-        Cvt<T>::st(out + (long long)b * ld_o + (long long)h * HD + threadIdx.x, den > 0.f ? num / den : 0.f);
-    }
-}
-
-extern "C" int egomi_attn_decode_rows(const void* q, int64_t ld_q, const void* kcache, const void* vcache, const int32_t* kv_row, int64_t ld_kv,
-                                      int n_phys, const uint8_t* key_mask, int64_t ld_mask, void* out, int64_t ld_o, int B, int nb, int H, int hd,
-                                      int Smax, int T_len, float scale, int dtype, egomi_stream_t stream) {
-    if (!q || !kcache || !vcache || !kv_row || !out) return EGOMI_E_BADARG;
-    if (B <= 0 || nb <= 0 || B % nb || H <= 0 || n_phys <= 0 || T_len <= 0 || T_len > Smax || ld_kv < T_len || ld_q % 8 ||
-        ld_q < (int64_t)H * hd || ld_o < (int64_t)H * hd) return EGOMI_E_SHAPE;
-    if (key_mask && ld_mask < T_len) return EGOMI_E_SHAPE;
-    hipStream_t s = (hipStream_t)stream;
-#define ADR(TT, HDV)                                                                                                                  \
-    EGOMI_LAUNCH((attn_decode_rows_kernel<TT, HDV>), dim3(B * H), dim3(256), 0, s, (const TT*)q, (long long)ld_q, (const TT*)kcache,     \
-                 (const TT*)vcache, (const int*)kv_row, (long long)ld_kv, n_phys, key_mask, (long long)ld_mask, (TT*)out, (long long)ld_o, H, \
-                 nb, Smax, T_len, scale)
-    if (dtype == EGOMI_BF16) {
-        if (hd == 128) ADR(bf16_t, 128); else if (hd == 64) ADR(bf16_t, 64); else if (hd == 32) ADR(bf16_t, 32); else return EGOMI_E_UNSUPPORTED;
-    } else if (dtype == EGOMI_F32) {
-        if (hd == 128) ADR(float, 128); else if (hd == 64) ADR(float, 64); else if (hd == 32) ADR(float, 32); else return EGOMI_E_UNSUPPORTED;
-    } else return EGOMI_E_BADARG;
-#undef ADR
     return egomi_launch_status();
 }

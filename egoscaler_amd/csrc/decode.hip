@@ -1,11 +1,10 @@
-// Single-token decode against a static KV cache (A13): kv_append, attn_decode, argmax.
-// replaces the cached branch of HF LlamaAttention.forward (modeling_llama.py:243-281 with
-// past_key_values.update) + eager attention for one query, and the greedy step of
-// GenerationMixin.generate reached from model_arch.py:94-108.  HBM-bound: per step each (batch, head)
-// streams its K and V rows once (2 * T * head_dim * 2 B); cache layout [B, H, Smax, hd] keeps every
-// stream contiguous.  All launches take their lengths as arguments, so 32 steps can be captured into
-// one hipGraph with per-step constants.
+// Single-token decode against a static KV cache (A13): kv_append, the consumers of the split-K slabs, argmax; the attention over the
+// cache is attn_decode.hip.  Replaces the cache update of HF LlamaAttention.forward (modeling_llama.py:243-281 with
+// past_key_values.update) and the greedy step of GenerationMixin.generate reached from model_arch.py:94-108.  Cache layout
+// [B, H, Smax, hd] keeps every (batch, head) stream contiguous.  All launches take their lengths as arguments, so 32 steps can be
+// captured into one hipGraph with per-step constants.
 #include "common.h"
+#include "qkv_finish.h"
 #include <math.h>
 
 // ------------------------------------------------------------------------------------------------
@@ -37,116 +36,6 @@ extern "C" int egomi_kv_append(const void* k, const void* v, int64_t ld, void* k
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
     EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH(kv_append_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)k, (const T*)v,
                                              (long long)ld, (T*)kcache, (T*)vcache, B, S, H, hd, Smax, pos0));
-    return egomi_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
-// attn_decode: one query per (b, h) against keys [0, T).  One 256-thread block per (b, h); a wave
-// handles 16 keys per iteration (4 lanes per key, HD/4 dims per lane), online softmax per wave,
-// waves combined through LDS.  key_mask [B, T] (1 = visible) may be NULL.
-// ------------------------------------------------------------------------------------------------
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const T* q, long long ld_q, const T* kc, const T* vc, const uint8_t* key_mask,
-                                                          long long ld_mask, T* out, long long ld_o, int H, int Smax, int Tlen, float scale) {
-    constexpr int DPL = HD / 4;                                    // dims per lane
-    __shared__ float sm_m[4], sm_l[4];
-    __shared__ float sm_acc[4][HD];
-    const int bh = blockIdx.x, b = bh / H, h = bh % H;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int part = lane & 3, kslot = lane >> 2;                  // 16 keys per wave-iteration
-    float qv[DPL];
-#pragma unroll
-    for (int c = 0; c < DPL / 8; ++c) {
-        float t[8];
-        load8<T>(q + (long long)b * ld_q + (long long)h * HD + part * DPL + c * 8, t);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qv[c * 8 + j] = t[j] * scale;
-    }
-    const T* Kb = kc + ((long long)bh * Smax) * HD + part * DPL;
-    const T* Vb = vc + ((long long)bh * Smax) * HD + part * DPL;
-    float m = -INFINITY, l = 0.f, acc[DPL];
-#pragma unroll
-    for (int j = 0; j < DPL; ++j) acc[j] = 0.f;
-    for (int k0 = wave * 16; k0 < Tlen; k0 += 64) {
-        const int key = k0 + kslot;
-        bool ok = key < Tlen;
-        if (ok && key_mask) ok = key_mask[(long long)b * ld_mask + key] != 0;
-        const int kr = key < Tlen ? key : Tlen - 1;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < DPL / 8; ++c) {
-            float t[8];
-            load8<T>(Kb + (long long)kr * HD + c * 8, t);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) s += t[j] * qv[c * 8 + j];
-        }
-        s += __shfl_xor(s, 1, 64);
-        s += __shfl_xor(s, 2, 64);
-        s = ok ? s : -INFINITY;
-        float mx = s;
-#pragma unroll
-        for (int o = 4; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        const float m_new = fmaxf(m, mx);
-        const float m_safe = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = m == -INFINITY ? 0.f : __expf(m - m_safe);
-        const float p = ok ? __expf(s - m_safe) : 0.f;
-        float ps = p;
-#pragma unroll
-        for (int o = 4; o < 64; o <<= 1) ps += __shfl_xor(ps, o, 64);
-        l = l * alpha + ps;
-        m = m_new;
-#pragma unroll
-        for (int c = 0; c < DPL / 8; ++c) {
-            float t[8];
-            load8<T>(Vb + (long long)kr * HD + c * 8, t);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[c * 8 + j] = acc[c * 8 + j] * alpha + p * t[j];
-        }
-    }
-    // reduce the 16 key slots of the wave (lanes with equal `part`)
-#pragma unroll
-    for (int j = 0; j < DPL; ++j) {
-        float a = acc[j];
-#pragma unroll
-        for (int o = 4; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
-        acc[j] = a;
-    }
-    if (lane < 4) {
-#pragma unroll
-        for (int j = 0; j < DPL; ++j) sm_acc[wave][lane * DPL + j] = acc[j];
-        if (lane == 0) { sm_m[wave] = m; sm_l[wave] = l; }
-    }
-    __syncthreads();
-    if (threadIdx.x < HD) {
-        float mm = fmaxf(fmaxf(sm_m[0], sm_m[1]), fmaxf(sm_m[2], sm_m[3]));
-        const float ms = mm == -INFINITY ? 0.f : mm;
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float f = sm_m[w] == -INFINITY ? 0.f : __expf(sm_m[w] - ms);
-            num += f * sm_acc[w][threadIdx.x];
-            den += f * sm_l[w];
-        }
-        Cvt<T>::st(out + (long long)b * ld_o + (long long)h * HD + threadIdx.x, den > 0.f ? num / den : 0.f);
-    }
-}
-
-extern "C" int egomi_attn_decode(const void* q, int64_t ld_q, const void* kcache, const void* vcache, const uint8_t* key_mask, int64_t ld_mask,
-                                 void* out, int64_t ld_o, int B, int H, int hd, int Smax, int T_len, float scale, int dtype,
-                                 egomi_stream_t stream) {
-    if (!q || !kcache || !vcache || !out) return EGOMI_E_BADARG;
-    if (B <= 0 || H <= 0 || T_len <= 0 || T_len > Smax || ld_q % 8 || ld_q < (int64_t)H * hd || ld_o < (int64_t)H * hd) return EGOMI_E_SHAPE;
-    if (key_mask && ld_mask < T_len) return EGOMI_E_SHAPE;
-    hipStream_t s = (hipStream_t)stream;
-#define ADK(TT, HDV)                                                                                                       \
-    EGOMI_LAUNCH((attn_decode_kernel<TT, HDV>), dim3(B * H), dim3(256), 0, s, (const TT*)q, (long long)ld_q, (const TT*)kcache, \
-                 (const TT*)vcache, key_mask, (long long)ld_mask, (TT*)out, (long long)ld_o, H, Smax, T_len, scale)
-    if (dtype == EGOMI_BF16) {
-        if (hd == 128) ADK(bf16_t, 128); else if (hd == 64) ADK(bf16_t, 64); else if (hd == 32) ADK(bf16_t, 32); else return EGOMI_E_UNSUPPORTED;
-    } else if (dtype == EGOMI_F32) {
-        if (hd == 128) ADK(float, 128); else if (hd == 64) ADK(float, 64); else if (hd == 32) ADK(float, 32); else return EGOMI_E_UNSUPPORTED;
-    } else return EGOMI_E_BADARG;
-#undef ADK
     return egomi_launch_status();
 }
 
@@ -224,7 +113,7 @@ extern "C" int egomi_slabs_rmsnorm(const float* slabs, int slices, int rows, int
 
 // ------------------------------------------------------------------------------------------------
 // qkv_finish (single-token step): q|k|v = bf16(sum_s slab[s]) [B, 3*H*hd]; RoPE at position `pos` on q and k (rope_vec8_kernel's
-// arithmetic, HF apply_rotary_pos_emb), q written to qkv (attn_decode reads it there), k and v written straight into the
+// arithmetic, HF apply_rotary_pos_emb; qkv_finish.h), q written to qkv (attn_decode reads it there), k and v written straight into the
 // [B,H,Smax,hd] caches at `pos`.  Replaces splitk_reduce + rope + kv_append.  One thread per 8 rotation pairs / 16 v columns.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
@@ -239,41 +128,9 @@ __global__ __launch_bounds__(256) void qkv_finish_kernel(const float* slabs, int
         const int part = (int)((e / ((long long)cpv * H)) % 3);
         const long long b = e / ((long long)cpv * H * 3);
         const long long col = part * d + (long long)h * hd + i;
-        float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int s2 = 0; s2 < sk; ++s2) {
-            float t[8];
-            load8<float>(slabs + (long long)s2 * slab_stride + b * 3 * d + col, t);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += t[j];
-            load8<float>(slabs + (long long)s2 * slab_stride + b * 3 * d + col + half, t);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bb[j] += t[j];
-        }
-        if (sizeof(T) == 2) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { a[j] = bf2f(f2bf(a[j])); bb[j] = bf2f(f2bf(bb[j])); }       // the product as the combine pass would have stored it
-        }
         float oa[8], ob[8];
-        if (part < 2) {
-            float c[8], sn[8];
-            load8<float>(cos_tab + (long long)pos * half + i, c);
-            load8<float>(sin_tab + (long long)pos * half + i, sn);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float cj = c[j], sj = sn[j];
-                if (sizeof(T) == 2) {
-                    cj = bf2f(f2bf(cj)); sj = bf2f(f2bf(sj));
-                    oa[j] = bf2f(f2bf(a[j] * cj)) + bf2f(f2bf(-bb[j] * sj));
-                    ob[j] = bf2f(f2bf(bb[j] * cj)) + bf2f(f2bf(a[j] * sj));
-                } else {
-                    oa[j] = a[j] * cj + (-bb[j]) * sj;
-                    ob[j] = bb[j] * cj + a[j] * sj;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { oa[j] = a[j]; ob[j] = bb[j]; }
-        }
+        qkv_sum_round_rope<T>(slabs + b * 3 * d + col, sk, slab_stride, half, cos_tab + (long long)pos * half + i, sin_tab + (long long)pos * half + i,
+                              part < 2, oa, ob);
         if (part == 0) {
             store8<T>(qkv + b * ld + col, oa);
             store8<T>(qkv + b * ld + col + half, ob);

@@ -1,4 +1,4 @@
-// OCP e4m3fn helpers shared by the fp8 KV cache (kv8.hip) and the fp8 weights of the decode projections (w8.hip).
+// OCP e4m3fn helpers shared by the fp8 KV cache (kv8.hip, attn_decode.hip) and the fp8 weights of the decode projections (w8.hip).
 // Quantisation rule of both (normative): s = amax / 448 (IEEE division), or 1 when amax == 0; code = e4m3fn_rne(x / s) (IEEE division,
 // no reciprocal-multiply); value = float(code) * s.  Bit-equal to torch's `(x / s).to(torch.float8_e4m3fn)`.
 #pragma once

@@ -332,6 +332,24 @@ class Decoder:
         else:
             kv_append(k, v, ld, self.kc[sel], self.vc[sel], B, Sq, H, hd, self.Smax, pos0)
 
+    def _attend(self, l, pos):
+        """Attention of this step's queries (self.qkv[:, :d]) over layer l of the cache, keys 0 .. pos, into self.ao: the read side of
+        _append.  Shared-prompt mode: prompt cache + the row's suffix; otherwise the dense or fp8 cache, each row's own physical row or,
+        in beam mode, the rows that self.kv_row names."""
+        lm = self.eng.dims.lm
+        B, H, hd = self.B, lm.num_attention_heads, lm.head_dim
+        ld_q, scale = 3 * lm.hidden_size, hd ** -0.5
+        if self.K > 1:
+            attn_decode_shared(self.qkv, ld_q, self.kp[l], self.vp[l], self.mask[::self.K], self.ksfx[l], self.vsfx[l], self.ao, B // self.K,
+                               self.K, H, hd, self.Sp, self.S0, self.Tmax, pos - self.S0 + 1, scale)
+            return
+        cache = (self.kc[l], self.vc[l], self.ks[l], self.vs[l]) if self.fp8 else (self.kc[l], self.vc[l])
+        if self.kv_row is None:
+            (attn_decode_fp8 if self.fp8 else attn_decode)(self.qkv, ld_q, *cache, self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
+        else:
+            (attn_decode_rows_fp8 if self.fp8 else attn_decode_rows)(self.qkv, ld_q, *cache, self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd,
+                                                                     self.Smax, pos + 1, scale)
+
     def prefill(self, input_ids, attention_mask, point_clouds, fps_start, total_new, nb=1):
         """nb > 1 (beam mode): the B prompts run ONCE each; their K/V land in physical cache rows 0..B-1 and their logits in rows 0..B-1 of
         self.lg, which every beam of the item reads at step 0 (HF expands to B * nb identical rows and prefills them all)."""
@@ -386,7 +404,6 @@ class Decoder:
         B, d, Fd, H, hd, L = self.B, lm.hidden_size, lm.intermediate_size, lm.num_attention_heads, lm.head_dim, lm.num_hidden_layers
         ops.embed_splice(self.tok, w["model.embed_tokens.weight"], None, None, eng.dims.pb.point_token_len, out=self.x.view(B, 1, d))
         x = self.x
-        scale = hd ** -0.5
         fq, fo, fd = self.fused["qkv"], self.fused["o"], self.fused["down"]
         normed = False                                      # self.h already holds this layer's input norm (written by the previous layer's tail)
         for l in range(L):
@@ -409,18 +426,7 @@ class Decoder:
                     self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos - self.S0, suffix=True)
                 else:
                     self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos)
-            if self.K > 1:
-                attn_decode_shared(self.qkv, 3 * d, self.kp[l], self.vp[l], self.mask[::self.K], self.ksfx[l], self.vsfx[l], self.ao, B // self.K,
-                                   self.K, H, hd, self.Sp, self.S0, self.Tmax, pos - self.S0 + 1, scale)
-            elif self.fp8 and self.kv_row is None:
-                attn_decode_fp8(self.qkv, 3 * d, self.kc[l], self.vc[l], self.ks[l], self.vs[l], self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
-            elif self.fp8:
-                attn_decode_rows_fp8(self.qkv, 3 * d, self.kc[l], self.vc[l], self.ks[l], self.vs[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd,
-                                     self.Smax, pos + 1, scale)
-            elif self.kv_row is None:
-                attn_decode(self.qkv, 3 * d, self.kc[l], self.vc[l], self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
-            else:
-                attn_decode_rows(self.qkv, 3 * d, self.kc[l], self.vc[l], self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd, self.Smax, pos + 1, scale)
+            self._attend(l, pos)
             if fo:
                 n = self._slabs(l, "o", self.ao, self.x_mid, self._w(l, "o"))
                 ops.slabs_rmsnorm(self.gws, n, x, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, self.x_mid, self.h2)

@@ -257,7 +257,8 @@ int egomi_qkv_finish(const float* slabs, int slices, void* qkv, int64_t ld, cons
  * per-(batch, head) streams).  No entry point reads a length from device memory: every step's
  * constants are arguments, so a whole multi-step decode can be captured into one hipGraph.
  *   kv_append : k, v rows [B*S, H*hd] (row stride ld) -> cache[b, h, pos0+s, :]
- *   attn_decode: q [B, H*hd] against keys [0, T_len) -> out [B, H*hd]; key_mask [B, >=T_len] u8 or NULL
+ *   attn_decode: q [B, H*hd] against keys [0, T_len) -> out [B, H*hd]; key_mask [B, >=T_len] u8 or NULL.  One kernel
+ *                (csrc/attn_decode.hip) serves this entry point, attn_decode_rows and the two fp8 forms below.
  *   argmax_rows: ids[b] = argmax logits[b, :] (lowest index on ties); seq[b*ld_seq + pos] = ids[b]
  */
 int egomi_kv_append(const void* k, const void* v, int64_t ld, void* kcache, void* vcache, int B, int S, int H, int hd, int Smax,
@@ -329,7 +330,7 @@ int egomi_attn_decode_shared(const void* q, int64_t ld_q, const void* kprompt, c
                              const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0,
                              int Tmax, int T_len, float scale, int dtype, egomi_stream_t stream);
 
-/* FP8 (OCP e4m3fn) KV cache (csrc/kv8.hip): codes uint8 [B, H, Smax, hd] per layer (the bf16 cache's layout), scales fp32 [B, H, Smax]
+/* FP8 (OCP e4m3fn) KV cache (csrc/kv8.hip; attention: csrc/attn_decode.hip): codes uint8 [B, H, Smax, hd] per layer (the bf16 cache's layout), scales fp32 [B, H, Smax]
  * per layer; hd in {32, 64, 128} (EGOMI_E_UNSUPPORTED otherwise); codes 8-B (attention: 16-B) aligned, scales 4-B aligned.  Per (row, head, position)
  * and tensor: s = amax / 448 (1 when amax == 0), code = e4m3fn_rne(x / s), value = float(code) * s, x being what the bf16 / fp32
  * kernel below would have stored (bit-equal to torch's (x / s).to(torch.float8_e4m3fn); see the header of csrc/kv8.hip).

@@ -1,5 +1,5 @@
-"""float64 oracle and per-element error metric for the attention kernels (csrc/attention.hip, the decode attention of decode.hip,
-beam.hip and kv8.hip).  A plain module, not a test file: tests/test_attn_oracle_host.py checks the metric on the CPU,
+"""float64 oracle and per-element error metric for the attention kernels (csrc/attention.hip, the decode attention of
+attn_decode.hip).  A plain module, not a test file: tests/test_attn_oracle_host.py checks the metric on the CPU,
 tests/test_gpu_attention_oracle.py runs every kernel form against it.
 
 Reference.  Everything is computed in float64 on the CPU from the values the kernel receives (bf16 q|k|v, dout, the bf16-rounded O and the

@@ -1,6 +1,6 @@
 """GPU: every form of the fused attention kernels (csrc/attention.hip: forward forms 1-4 with both block orders and a capped persistent grid,
-backward forms 1-3 with and without the inverse-RoPE epilogue, head_dim 128 and 64) and the decode attention kernels (decode.hip, beam.hip,
-kv8.hip) against the float64 oracle of tests/attn_oracle.py, element by element: |got - ref| <= TAU * E + PHI * max(E), E the magnitude of
+backward forms 1-3 with and without the inverse-RoPE epilogue, head_dim 128 and 64) and the decode attention kernel (every form of
+attn_decode.hip) against the float64 oracle of tests/attn_oracle.py, element by element: |got - ref| <= TAU * E + PHI * max(E), E the magnitude of
 the terms that make up the element (the bounds and their measurements are in attn_oracle.py's docstring).  Each case's reference is computed
 once and shared by every form.  The backward is handed the oracle's O (bf16) and LSE (fp32), so it is judged on exact inputs.
 

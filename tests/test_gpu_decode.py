@@ -226,3 +226,42 @@ def test_gemv_m16_kernel_matches_reference(M, N, K):
             assert ops.mm_slabs(A, W, out, ws) == n
             slabs = torch.frombuffer(ws.cpu().numpy().tobytes(), dtype=torch.float32)[:n * M * N].view(n, M, N)
             assert float((slabs.sum(0) - ref).abs().max()) <= 2e-3 * float(ref.abs().max())
+
+
+def test_attn_decode_bad_arguments_are_refused():
+    """egomi_attn_decode / egomi_attn_decode_rows refuse a bad call on the host, before any launch, with the code include/egomi.h names:
+    a NULL pointer or another dtype is a bad argument, a length or stride that does not fit is a shape error, another head_dim is
+    unsupported (and is looked at only after the shapes)."""
+    import ctypes
+    from egoscaler_amd._lib import c_f, c_i, c_i64, lib
+    from egoscaler_amd.ops import P, S
+    E_BADARG, E_SHAPE, E_UNSUPPORTED = -1, -2, -4
+    L = lib()
+    L.egomi_attn_decode.restype = L.egomi_attn_decode_rows.restype = ctypes.c_int
+    B, H, hd, Smax = 2, 2, 64, 16
+    d = H * hd
+    x = torch.zeros(B, 3 * d, dtype=torch.bfloat16, device="cuda")
+    kc = torch.zeros(B, H, Smax, hd, dtype=torch.bfloat16, device="cuda")
+    out = torch.zeros(B, d, dtype=torch.bfloat16, device="cuda")
+    mask = torch.ones(B, Smax, dtype=torch.uint8, device="cuda")
+    tab = torch.zeros(B, Smax, dtype=torch.int32, device="cuda")
+    nul = ctypes.c_void_p(None)
+
+    def att(q=P(x), c=P(kc), v=P(kc), o=P(out), m=nul, ldm=0, T=4, dt=1, hd_=hd, ldq=3 * d, ldo=d, B_=B):
+        return L.egomi_attn_decode(q, c_i64(ldq), c, v, m, c_i64(ldm), o, c_i64(ldo), c_i(B_), c_i(H), c_i(hd_), c_i(Smax), c_i(T), c_f(0.1), c_i(dt),
+                                   S())
+
+    def rws(q=P(x), c=P(kc), v=P(kc), o=P(out), tb=P(tab), ldkv=Smax, m=nul, ldm=0, T=4, nb=2, n_phys=B, dt=1, hd_=hd, ldq=3 * d, ldo=d, B_=B):
+        return L.egomi_attn_decode_rows(q, c_i64(ldq), c, v, tb, c_i64(ldkv), c_i(n_phys), m, c_i64(ldm), o, c_i64(ldo), c_i(B_), c_i(nb), c_i(H),
+                                        c_i(hd_), c_i(Smax), c_i(T), c_f(0.1), c_i(dt), S())
+
+    for f in (att, rws):
+        assert f(q=nul) == E_BADARG and f(c=nul) == E_BADARG and f(v=nul) == E_BADARG and f(o=nul) == E_BADARG
+        assert f(B_=0) == E_SHAPE and f(ldo=d - 8) == E_SHAPE
+        assert f(T=0) == E_SHAPE and f(T=Smax + 1) == E_SHAPE
+        assert f(ldq=3 * d + 4) == E_SHAPE and f(ldq=d - 8) == E_SHAPE
+        assert f(m=P(mask), ldm=3) == E_SHAPE
+        assert f(hd_=48) == E_UNSUPPORTED and f(hd_=48, T=0) == E_SHAPE
+        assert f(dt=5) == E_BADARG and f(dt=5, hd_=48) == E_BADARG
+    assert rws(tb=nul) == E_BADARG
+    assert rws(nb=3) == E_SHAPE and rws(n_phys=0) == E_SHAPE and rws(ldkv=3) == E_SHAPE

@@ -6,7 +6,7 @@ VERDICT r2 weak #1a: every other 7B-width decode test compares HIP with HIP (fus
 decode == full forward of the same engine); the only oracle comparison of cached decoding was the tiny fp32 golden, where none of
   * the M <= 512 split-K `gemm_nt_bf16_kernel<128,128,2>` with EGOMI_EPI_SLABS and its consumers `qkv_finish_kernel`
     (sum + RoPE(pos) + cache append) and `slabs_rmsnorm_kernel` (sum + residual + RMSNorm),
-  * `attn_decode_kernel` at head_dim 128 against a 540-row cache with a key mask,
+  * `attn_decode_kernel` (csrc/attn_decode.hip, dense cache) at head_dim 128 against a 540-row cache with a key mask,
   * `prefill_chunked` (per-sample cache appends; chunk = 2 -> M = 1080, the ADVICE r2 range of the GEMM router)
 is selected.  A wrong slab stride at d=4096 would have passed everything.  Here the per-step scores and the K/V rows the steps append
 are compared with `oracle.pointllm.forward` driven with a KV cache (pointllm.py:255-275, HF modeling_llama.py:243-281), evaluated in

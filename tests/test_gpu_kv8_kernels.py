@@ -1,4 +1,4 @@
-"""GPU: the fp8 (e4m3fn) KV-cache kernels of csrc/kv8.hip.  kv_append_fp8 / qkv_finish_fp8 are bit-equal to the torch restatement
+"""GPU: the fp8 (e4m3fn) KV-cache kernels of csrc/kv8.hip and the fp8 forms of csrc/attn_decode.hip.  kv_append_fp8 / qkv_finish_fp8 are bit-equal to the torch restatement
 (decode.kv8_quantize) of what kv_append / qkv_finish store; attn_decode_fp8 matches fp32 attention over the dequantised cache and ignores
 poisoned (NaN-coded) keys beyond T_len or under the mask; attn_decode_rows_fp8 follows its row table; every operand may end an allocation."""
 import ctypes
