@@ -32,6 +32,7 @@ struct AttnArgs {
     long long ld_qkv, ld_o, ld_dqkv;
     float scale;
     int causal;
+    int q_blocks;                                                       // query window (egomi_attn_desc.q_rows): only the last q_blocks end-aligned 128-query blocks have work; 0 = all
     const float* rope_cos; const float* rope_sin;
 };
 
@@ -874,7 +875,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd3_kernel(AttnArgs a, const int
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int rank, h, b;
     const int S32 = (a.S + 31) & ~31;
-    if (!attn_block_map3(a, (S32 + 127) / 128, group, rank, h, b)) return;
+    if (!attn_block_map3(a, a.q_blocks ? a.q_blocks : (S32 + 127) / 128, group, rank, h, b)) return;     // query window: the grid holds q_blocks ranks
     const int q0 = S32 - 128 * (rank + 1);                             // may be negative for the last rank (the shortest block)
     const long long row_base = (long long)b * a.S;
     const bf16_t* Q = a.q + row_base * a.ld_qkv + h * AT_HD;
@@ -1634,6 +1635,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq3_kernel(AttnArgs a) {
     attn_block_map(a, rank, h, b);
     const int q0 = ((a.S + 31) & ~31) - 128 * (rank + 1);
     const long long row_base = (long long)b * a.S;
+    if (a.q_blocks && rank >= a.q_blocks) {                            // query window: dout is zero on this block's rows, so dq = 0 and delta = 0 (the dK/dV
+        bf16_t* DQ = a.dq + row_base * a.ld_dqkv + h * AT_HD;         // kernel may read delta there); written before any DMA is issued or LDS touched
+        const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = threadIdx.x + 256 * i, r = q0 + (c >> 4);
+            if (r >= 0 && r < a.S) *reinterpret_cast<u32x4*>(DQ + (long long)r * a.ld_dqkv + (c & 15) * 8) = z;
+        }
+        const int r = q0 + (int)threadIdx.x;
+        if (threadIdx.x < 128 && r >= 0 && r < a.S) a.delta[((long long)b * a.H + h) * a.S + r] = 0.f;
+        return;
+    }
     const bf16_t* Q = a.q + row_base * a.ld_qkv + h * AT_HD;
     const bf16_t* K = a.k + row_base * a.ld_qkv + h * AT_HD;
     const bf16_t* V = a.v + row_base * a.ld_qkv + h * AT_HD;
@@ -2033,7 +2046,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(AttnArgs a) {
         for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
     const float sc2 = a.scale * 1.4426950408889634f;
     const int nq = (a.S + 31) / 32;
-    const int qt0 = a.causal ? (kb0 / 32) : 0;
+    int qt0 = a.causal ? (kb0 / 32) : 0;
+    if (a.q_blocks) {                                                  // query window: dout (and this call's delta) are zero below the first block the dQ
+        const int q_lo = ((a.S + 31) & ~31) - 128 * a.q_blocks;       // kernel computed; q_lo is a multiple of the 32-query tile and < S, so a tile is always left
+        if (q_lo > qt0 * 32) qt0 = q_lo / 32;
+    }
     const bool ragged = nq * 32 > a.S;
 
     // per-lane DMA offsets of query tile qt0 (bytes from Q / dO / LSE), advanced by 32 rows per tile; the ragged last tile is clamped
@@ -2211,7 +2228,15 @@ static AttnArgs attn_args(const egomi_attn_desc* d) {
     a.key_mask = d->key_mask; a.B = d->B; a.H = d->H; a.S = d->S;
     a.ld_qkv = d->ld_qkv; a.ld_o = d->ld_o; a.ld_dqkv = d->ld_dqkv; a.scale = d->scale; a.causal = d->causal;
     a.rope_cos = d->rope_cos; a.rope_sin = d->rope_sin;
+    a.q_blocks = 0;
     return a;
+}
+// Query window (egomi.h, q_rows): the number of end-aligned 128-query blocks (q0 = S32 - 128 * (rank + 1)) that hold a row >= S - q_rows;
+// 0 = no window.  The blocks hang from S32, not S, so the count is ceil((q_rows + S32 - S) / 128): at S = 692 a window of 128 rows lies in two.
+static int attn_q_blocks(const egomi_attn_desc* d) {
+    if (d->q_rows <= 0 || d->q_rows >= d->S || d->head_dim != AT_HD) return 0;
+    const int s32 = (d->S + 31) & ~31;
+    return (d->q_rows + s32 - d->S + 127) / 128;
 }
 
 extern "C" int egomi_attn_fwd(const egomi_attn_desc* d, egomi_stream_t stream) {
@@ -2226,7 +2251,7 @@ extern "C" int egomi_attn_fwd(const egomi_attn_desc* d, egomi_stream_t stream) {
     if ((long long)d->S * d->ld_qkv * 2 >= (1ll << 32)) form = 1;      // the second and third forms address K/V rows with 32-bit byte offsets
     if (d->head_dim == 128 && form == 4 && d->S > 1024) form = 3;       // the persistent form keeps a sample's key-mask bytes in four registers per thread
     if (d->head_dim == 128 && form == 4) {
-        const int s32 = (d->S + 31) & ~31, nblk = (s32 + 127) / 128;
+        const int s32 = (d->S + 31) & ~31, qb = attn_q_blocks(d), nblk = qb ? qb : (s32 + 127) / 128;      // rank-major items: the window's ranks come first
         const int n_items = nblk * d->H * d->B;
         static int cus = 0;
         if (!cus) { int dev = 0; hipDeviceProp_t pr; cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
@@ -2238,7 +2263,8 @@ extern "C" int egomi_attn_fwd(const egomi_attn_desc* d, egomi_stream_t stream) {
         return egomi_launch_status();
     }
     if (d->head_dim == 128 && form == 3) {
-        const int s32 = (d->S + 31) & ~31, nblk = (s32 + 127) / 128;
+        const int s32 = (d->S + 31) & ~31, qb = attn_q_blocks(d), nblk = qb ? qb : (s32 + 127) / 128;
+        a.q_blocks = qb;
         int group = (d->H * d->B) % 8 == 0 ? attn_fwd_group() : 0;
         if (group > nblk) group = nblk;
         const int nb = group > 0 ? ((nblk + group - 1) / group) * group : nblk;
@@ -2274,6 +2300,7 @@ extern "C" int egomi_attn_bwd(const egomi_attn_desc* d, egomi_stream_t stream) {
     if ((d->rope_cos == nullptr) != (d->rope_sin == nullptr)) return EGOMI_E_BADARG;
     if (d->rope_cos && (((uintptr_t)d->rope_cos | (uintptr_t)d->rope_sin) & 15)) return EGOMI_E_SHAPE;
     AttnArgs a = attn_args(d);
+    a.q_blocks = attn_q_blocks(d);                                     // read by the third dQ form and the second dK/dV form; the others compute every block
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(((d->S + 127) / 128) * d->H * d->B));
     if (d->head_dim == 64) {

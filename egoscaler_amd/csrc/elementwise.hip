@@ -204,14 +204,30 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(T* dy, const T* x, con
 // columns over all the rows (4 lanes x 8 columns, 256 rows in flight per iteration), the 256 row-lane partials meet in LDS and are
 // summed in a fixed order, and the owner adds the result to dw with a plain read-modify-write.  No atomics: the same bits every run.
 // (Round 1's form split the rows over gridDim.y and met in dw with fp32 atomics: ~20 us at 5536 x 4096, order-dependent last bits.)
+// seq > 0 (egomi_rmsnorm_bwd_rows): dy, x, rstd hold only the last `win` rows of every sequence of `seq` rows, compact (rows = sequences * win);
+// each row is added where it would be if the other rows were present with dy = 0 — same lane, same order — so dw has the bits of the full-layout call.
 template <typename T>
-__global__ __launch_bounds__(1024) void rmsnorm_dw_kernel(const T* dy, const T* x, const float* rstd, float* dw, int rows, int cols) {
+__global__ __launch_bounds__(1024) void rmsnorm_dw_kernel(const T* dy, const T* x, const float* rstd, float* dw, int rows, int cols, int seq, int win) {
     __shared__ float red[256][33];
     __shared__ float red2[32][33];
     const int cl = threadIdx.x & 3, rl = threadIdx.x >> 2;
     const int c = blockIdx.x * 32 + cl * 8;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (c < cols) {
+    if (c < cols && seq > 0) {
+        const long long rows_full = (long long)(rows / win) * seq;
+        for (long long f = rl; f < rows_full; f += 256) {
+            const long long b = f / seq;
+            const int sq = (int)(f - b * seq) - (seq - win);
+            if (sq < 0) continue;
+            const long long r = b * win + sq;
+            float g[8], xv[8];
+            load8<T>(dy + r * cols + c, g);
+            load8<T>(x + r * cols + c, xv);
+            const float rs = rstd[r];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += g[j] * (xv[j] * rs);
+        }
+    } else if (c < cols) {
 #pragma unroll 2
         for (long long r = rl; r < rows; r += 256) {
             float g[8], xv[8];
@@ -252,7 +268,7 @@ extern "C" int egomi_rmsnorm_fwd(const void* x, const void* w, void* y, float* r
 }
 
 static int rmsnorm_bwd_impl(void* dy, const void* x, const void* w, const float* rstd, void* dx, const void* dx_add, float* dw, int rows, int cols,
-                            int row0, const float* slabs, int sk, int dtype, egomi_stream_t stream) {
+                            int row0, const float* slabs, int sk, int dtype, egomi_stream_t stream, int seq = 0, int win = 0) {
     if (!dy || !x || !w || !rstd || !dx) return EGOMI_E_BADARG;
     if (rows <= 0 || cols <= 0 || cols % 8) return EGOMI_E_SHAPE;
     if (cols > 8192) return EGOMI_E_UNSUPPORTED;
@@ -262,7 +278,7 @@ static int rmsnorm_bwd_impl(void* dy, const void* x, const void* w, const float*
     // tail the row kernel runs FIRST: it is the one that materialises dy's last rows, which the weight-gradient pass reads.
     auto dw_pass = [&]() {
         EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH(rmsnorm_dw_kernel<T>, dim3((cols + 31) / 32), dim3(1024), 0, (hipStream_t)stream,
-                                                       (const T*)dy, (const T*)x, rstd, dw, rows, cols));
+                                                       (const T*)dy, (const T*)x, rstd, dw, rows, cols, seq, win));
         return 0;
     };
     if (dw && !tail) dw_pass();
@@ -278,6 +294,14 @@ static int rmsnorm_bwd_impl(void* dy, const void* x, const void* w, const float*
 extern "C" int egomi_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx, const void* dx_add,
                                  float* dw, int rows, int cols, int dtype, egomi_stream_t stream) {
     return rmsnorm_bwd_impl(const_cast<void*>(dy), x, w, rstd, dx, dx_add, dw, rows, cols, rows, nullptr, 0, dtype, stream);
+}
+
+// compact rows: the last `win` rows of every sequence of `seq` rows only (rows = sequences * win).  dx as egomi_rmsnorm_bwd on those rows; dw summed in the
+// order of the full-layout call whose other rows have dy = 0: the same bits
+extern "C" int egomi_rmsnorm_bwd_rows(const void* dy, const void* x, const void* w, const float* rstd, void* dx, const void* dx_add,
+                                      float* dw, int rows, int cols, int seq, int win, int dtype, egomi_stream_t stream) {
+    if (seq <= 0 || win <= 0 || win > seq || rows % win) return EGOMI_E_SHAPE;
+    return rmsnorm_bwd_impl(const_cast<void*>(dy), x, w, rstd, dx, dx_add, dw, rows, cols, rows, nullptr, 0, dtype, stream, seq, win);
 }
 
 // the *_tail forms: the last rows of the input are still the K-slice slabs of the GEMM that produced it (include/egomi.h)

@@ -1581,6 +1581,13 @@ static int tile_choice(const egomi_gemm_desc* d) {
     if (t256 >= 32 && t256 < 128 && d->K >= 8192 && d->M > 512 && d->epilogue == EGOMI_EPI_NONE && d->workspace &&
         d->workspace_bytes >= (long long)((d->M + 255) / 256) * 256 * d->N * 4 * 2 + 4096 &&
         (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) return 8;
+    // whole tiles asked for (split_k = 1: no K-sliced rows) at few tiles: the 8-phase kernel, in which every element accumulates its K-tiles in the
+    // order of the 352x256 form (tests/test_gpu_gemm_tall.py).  The windowed top decoder layer (M = 8 x 153 = 1224, 80 tiles at N = 4096) asks for it
+    // so that its rows keep the bits they have in the M = 5536 products of the layers below; it is not the fastest route at this height
+    // (profiles/top_rows_gemm_shapes.txt, cold weights, N = 4096: K = 4096 + residual 88.2 vs 68.6 us on the 128x128 kernel, K = 4096 plain 71.4 vs 62.6,
+    // K = 11008 + residual 199.7 vs 136.0 and K = 22016 365.1 vs 233.7 with all rows K-sliced), which is why it is taken on request only
+    if (d->split_k == 1 && t256 >= 32 && t256 < 128 && d->K >= 2048 && d->M > 512 &&
+        (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) return 8;
     return (d->M >= 2048 && d->N >= 8192) ? 2 : 1;
 }
 

@@ -72,6 +72,11 @@ class Engine:
         # trainable decoder weights: weight gradients and data gradients on the k-major 8-phase kernel (csrc/gemm_tn.hip) — no transposed
         # copies of dY / X per product, no resident W^T that must follow every optimizer step.  EGOMI_GEMM_TN=0: the round-1/2 route (A/B)
         self.use_tn = os.environ.get("EGOMI_GEMM_TN", "1") != "0"
+        # frozen top decoder layer: everything after its attention runs on the rows the loss reads only (forward_hidden(loss_from=...)).
+        # EGOMI_TOP_ROWS=0 / use_top_rows = False: every row, as the lower layers (A/B runs, tests)
+        self.use_top_rows = os.environ.get("EGOMI_TOP_ROWS", "1") != "0"
+        self.top_rows_taken = 0             # the window R the last forward_hidden(save=True) ran the top layer on; 0 = it ran every row
+        self._top_key = None                # (B, S, R, buffer addresses) the window buffers of _top_buffers are currently valid for
         self.pb_trainer = None
         self.defer_splice_check = False     # hipGraph capture of a whole step: the marker verdict is copied to pinned memory by the graph and
         self.pending_splice = None          # looked at by the caller after the replay (check_pending_splice) instead of inside the forward pass
@@ -419,10 +424,44 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------------------------ forward
-    def forward_hidden(self, input_ids, attention_mask, point_clouds, fps_start, save=True, kv_sink=None):
+    def _top_rows(self, save, loss_from, fused, S):
+        """The query window R of the top decoder layer (0 = every row): the loss reads the final hidden state at rows >= loss_from of every
+        sample only, so below that row the top layer is needed as keys and values alone.  Holds for the TOP layer of a training step whose
+        top layer is frozen and carries no adapter, on the fused bf16 attention; everything else runs every row."""
+        if not (save and self.use_top_rows and fused and loss_from is not None and self.lora is None):
+            return 0
+        R = S - int(loss_from)
+        top = f"model.layers.{self.dims.lm.num_hidden_layers - 1}."
+        if not 0 < R < S or any(n.startswith(top) for n in self.trainable):
+            return 0
+        return R
+
+    def _top_buffers(self, B, S, R):
+        """Full-layout buffers of the windowed top layer: its attention output and LSE (rows below the window are never written: kept
+        finite, and the LSE huge so that a kernel form that does compute those rows gets P = 0), and the gradients d_ao / d_mid that
+        backward scatters the window rows into (zero below the window).  They stay valid while the window does not move; when B, S, R or
+        an allocation changes, all of them are reset."""
+        lm, T, ws = self.dims.lm, self.dtype, self.ws
+        d, H = lm.hidden_size, lm.num_attention_heads
+        ao, d_ao, d_mid = (ws.get(n, (B * S, d), T) for n in ("ao_top", "d_ao_top", "d_mid_top"))
+        lse = ws.get("lse_top", (B, H, S), torch.float32)
+        key = (B, S, R, ao.data_ptr(), d_ao.data_ptr(), d_mid.data_ptr(), lse.data_ptr())
+        if self._top_key != key:
+            ao.zero_()
+            d_ao.zero_()
+            d_mid.zero_()
+            lse.fill_(1e30)
+            self._top_key = key
+        return ao, lse, d_ao, d_mid
+
+    def forward_hidden(self, input_ids, attention_mask, point_clouds, fps_start, save=True, kv_sink=None, loss_from=None):
         """-> final-normed hidden [B*S, d]; fills self.ctx for backward when save=True.
         kv_sink(layer, qkv, B, S): optional prefill hook that receives the post-RoPE q|k|v buffer of every
-        layer (decode.Decoder copies k, v into its static cache)."""
+        layer (decode.Decoder copies k, v into its static cache).
+        loss_from (with save=True): the caller reads the result at rows >= loss_from of every sample only.  Where _top_rows() allows it,
+        the top layer then runs on those R = S - loss_from rows past its attention, and the result, ctx["x_last"] and the top layer's saved
+        tensors past its attention are COMPACT [B*R, d] (sample b's row s at b*R + s - loss_from); ctx["top_rows"] = R, and
+        backward_hidden takes the gradient in the same layout.  self.top_rows_taken reports R (0: every row ran, full layout)."""
         if not self.prepared:
             self.prepare()
         w, dims, T, ws = self.w, self.dims, self.dtype, self.ws
@@ -491,27 +530,37 @@ class Engine:
         # kernel that reads them instead of by a combine pass (EGOMI_EPI_SLABS, include/egomi.h).  EGOMI_NO_TAIL_FUSE=1: A/B switch
         defer = self.use_tail_fuse and T == torch.bfloat16
         pend = pend_res = None
-        fuse_swiglu = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and (2 * Fd) % 256 == 0 and ops.gemm_kernel_id(M, 2 * Fd, d) == 2
+        fuse_swiglu_all = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and (2 * Fd) % 256 == 0
+        fuse_swiglu = fuse_swiglu_all and ops.gemm_kernel_id(M, 2 * Fd, d) == 2
         la = self.lora_groups
+        R = self._top_rows(save, loss_from, fused, S)
+        if save:
+            self.top_rows_taken = R
         for l in range(L):
             p = f"model.layers.{l}."
             self.wait_params(l)
+            top = R > 0 and l == L - 1                         # the windowed top layer: Ml = B*R compact rows past the attention
+            Ml = B * R if top else M
             lT = {}                                            # T = x A^T of every adapted input: kept for backward
             for g, ts in la.items():
                 shp = (M, len(ts) * self.lora.r)
                 lT[g] = torch.empty(shp, dtype=T, device=self.device) if save else ws.get(f"lora_T_{g}", shp, T)
             if save:
                 lc = {"x_in": x, "rstd1": torch.empty(M, dtype=torch.float32, device=self.device),
-                      "rstd2": torch.empty(M, dtype=torch.float32, device=self.device),
+                      "rstd2": torch.empty(Ml, dtype=torch.float32, device=self.device),
                       "qkv": torch.empty(M, 3 * d, dtype=T, device=self.device),
-                      "gu": torch.empty(M, 2 * Fd, dtype=T, device=self.device)}
+                      "gu": torch.empty(Ml, 2 * Fd, dtype=T, device=self.device)}
                 keep_in = self.any_layer_trainable
                 h = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or "qkv" in la) else ws.get("h", (M, d), T)
-                ao = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or fused or "o" in la) else ws.get("ao", (M, d), T)
-                h2 = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or "gu" in la) else ws.get("h2", (M, d), T)
-                act = torch.empty(M, Fd, dtype=T, device=self.device) if (keep_in or "down" in la) else ws.get("act", (M, Fd), T)
-                x_mid = torch.empty(M, d, dtype=T, device=self.device)
-                x_out = torch.empty(M, d, dtype=T, device=self.device)
+                if top:                                        # frozen, no adapters: nothing past the attention is kept for a weight gradient
+                    ao, lse_top = self._top_buffers(B, S, R)[:2]
+                    h2, act = ws.get("h2_top", (Ml, d), T), ws.get("act_top", (Ml, Fd), T)
+                else:
+                    ao = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or fused or "o" in la) else ws.get("ao", (M, d), T)
+                    h2 = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or "gu" in la) else ws.get("h2", (M, d), T)
+                    act = torch.empty(M, Fd, dtype=T, device=self.device) if (keep_in or "down" in la) else ws.get("act", (M, Fd), T)
+                x_mid = torch.empty(Ml, d, dtype=T, device=self.device)
+                x_out = torch.empty(Ml, d, dtype=T, device=self.device)
                 qkv, gu, rstd1, rstd2 = lc["qkv"], lc["gu"], lc["rstd1"], lc["rstd2"]
             else:
                 h, ao, h2, act = ws.get("h", (M, d), T), ws.get("ao", (M, d), T), ws.get("h2", (M, d), T), ws.get("act", (M, Fd), T)
@@ -541,24 +590,39 @@ class Engine:
             if fused:
                 # fused flash-style kernel: scores never reach HBM; LSE (and the output) are kept for backward
                 Pm = None
-                lse = torch.empty(B, H, S, dtype=torch.float32, device=self.device) if save else ws.get("att_lse", (B, H, S), torch.float32)
-                ops.attn_fwd(qkv, B, S, H, hd, scale, ao, lse, causal=True, key_mask=key_mask)
+                if top:
+                    lse = lse_top
+                else:
+                    lse = torch.empty(B, H, S, dtype=torch.float32, device=self.device) if save else ws.get("att_lse", (B, H, S), torch.float32)
+                ops.attn_fwd(qkv, B, S, H, hd, scale, ao, lse, causal=True, key_mask=key_mask, q_rows=R if top else 0)
             else:
                 Pm = self._attention(qkv, B, S, H, hd, ao, True, key_mask, scale, save)
+            ao_full = ao
+            # the windowed top layer's products run whole 256x256 tiles (split_k = 1: no K-sliced rows, no deferred tail), in which every
+            # element accumulates its K-tiles in the order of the forms the M = B*S products take: the step keeps the bits of the full path
+            wt = {"split_k": 1} if top else {}
+            if top:                                            # the window rows of the attention output and of the layer input, compact
+                ao = ws.get("ao_rows_top", (Ml, d), T)
+                ao.view(B, R, d).copy_(ao_full.view(B, S, d)[:, S - R:])
+                xw = ws.get("x_rows_top", (Ml, d), T)
+                xw.view(B, R, d).copy_(x.view(B, S, d)[:, S - R:])
+                x = xw
             if defer and "o" not in la:                        # the K-sliced tail rows of the product are summed by the norm that reads them
-                _, t_o = ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x, defer_tail=True)
+                _, t_o = ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x, defer_tail=True, **wt)
                 ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, rstd=rstd2, out=h2, tail=t_o, tail_residual=x)
             else:
-                ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x)
+                ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x, **wt)
                 if "o" in la:
                     self._lora_fwd(l, "o", ao, x_mid, lT["o"])
                 ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, rstd=rstd2, out=h2)
             gu_il = l in self.wgu and self.gu_il
+            if top:
+                fuse_swiglu = fuse_swiglu_all and ops.gemm_kernel_id(Ml, 2 * Fd, d) == 2
             if gu_il:
                 if fuse_swiglu and "gu" not in la:
-                    ops.mm(h2, self.wgu[l], out=gu, swiglu_out=act)          # act leaves the GEMM epilogue; gu (interleaved-32) is kept for backward
+                    ops.mm(h2, self.wgu[l], out=gu, swiglu_out=act, **wt)    # act leaves the GEMM epilogue; gu (interleaved-32) is kept for backward
                 else:
-                    ops.mm(h2, self.wgu[l], out=gu)
+                    ops.mm(h2, self.wgu[l], out=gu, **wt)
                     if "gu" in la:
                         self._lora_fwd(l, "gu", h2, gu, lT["gu"], il=True)
                     ops.swiglu_il(gu, act)
@@ -572,22 +636,23 @@ class Engine:
                     self._lora_fwd(l, "gu", h2, gu, lT["gu"])
                 ops.swiglu(gu[:, :Fd], gu[:, Fd:], act)
             if defer and "down" not in la:                     # ... here by the NEXT layer's input norm (or the final norm)
-                _, pend = ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid, defer_tail=True)
+                _, pend = ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid, defer_tail=True, **wt)
                 pend_res = x_mid
             else:
-                ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid)
+                ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid, **wt)
                 if "down" in la:
                     self._lora_fwd(l, "down", act, x_out, lT["down"])
             if save:
-                lc.update(P=Pm, lse=lse, x_mid=x_mid, h=h, ao=ao, h2=h2, act=act, lora_T=lT, gu_il=gu_il)
+                lc.update(P=Pm, lse=lse, x_mid=x_mid, h=h, ao=ao_full, h2=h2, act=act, lora_T=lT, gu_il=gu_il)
                 ctx["layers"].append(lc)
             x = x_out
         self.wait_params("post")
-        rstd_f = torch.empty(M, dtype=torch.float32, device=self.device) if save else None
-        hn = torch.empty(M, d, dtype=T, device=self.device)
+        Mf = x.shape[0]                                        # B*R after a windowed top layer
+        rstd_f = torch.empty(Mf, dtype=torch.float32, device=self.device) if save else None
+        hn = torch.empty(Mf, d, dtype=T, device=self.device)
         ops.rmsnorm(x, w["model.norm.weight"], lm.rms_norm_eps, rstd=rstd_f, out=hn, tail=pend, tail_residual=pend_res)
         if save:
-            ctx.update(x_last=x, rstd_f=rstd_f, hn=hn, key_mask=key_mask)
+            ctx.update(x_last=x, rstd_f=rstd_f, hn=hn, key_mask=key_mask, top_rows=R)
             self.ctx = ctx
         if self.defer_splice_check:
             self.pending_splice = pending_err
@@ -730,11 +795,11 @@ class Engine:
         return ops.lora_up(self.w[bn], self.w[an], out, self.lora.scale, q_trans=True)
 
     # ------------------------------------------------------------------------------------ backward
-    def _dgrad(self, dY, name, out, residual=None):
-        """out = dY . W (+ residual).  Uses the resident W^T (tuned NT kernel) for frozen weights."""
+    def _dgrad(self, dY, name, out, residual=None, **kw):
+        """out = dY . W (+ residual).  Uses the resident W^T (tuned NT kernel) for frozen weights (kw: further ops.mm arguments on that route)."""
         wt = self.wT.get(name) if self.prepared else None
         if wt is not None:
-            return ops.mm(dY, wt, out=out, residual=residual)
+            return ops.mm(dY, wt, out=out, residual=residual, **kw)
         return self._dgrad_w(dY, self.w[name], out, residual)
 
     def _dgrad_w(self, dY, W, out, residual=None):
@@ -813,9 +878,21 @@ class Engine:
         if name in self.trainable:
             ops.colsum_(dY, self.grad_buffer(name))
 
+    def compact_loss_grad(self, d_hs):
+        """After a windowed forward (ctx["top_rows"] = R): d_hs [B*(R-1), d], the gradient at the R-1 rows of every sample that the loss
+        reads, -> the compact [B*R, d] gradient backward_hidden takes; every sample's last row (no target follows it) is zero."""
+        B, R = self.ctx["B"], self.ctx["top_rows"]
+        d = d_hs.shape[1]
+        held = self.ws.bufs.get("d_hn_top")
+        g = self.ws.get("d_hn_top", (B, R, d), self.dtype)
+        if g is not held:
+            g[:, R - 1].zero_()                               # written once: the copies below never touch that row
+        g[:, :R - 1] = d_hs.view(B, R - 1, d)
+        return g.view(B * R, d)
+
     def backward_hidden(self, d_hn):
-        """d_hn: gradient w.r.t. the final-normed hidden [M,d].  Accumulates fp32 main_grad of the
-        trainable tensors (model_arch.py:33-51 decides which)."""
+        """d_hn: gradient w.r.t. the final-normed hidden [M,d] ([B*R,d] compact after a windowed forward: forward_hidden).  Accumulates
+        fp32 main_grad of the trainable tensors (model_arch.py:33-51 decides which)."""
         ctx, w, dims, T, ws = self.ctx, self.w, self.dims, self.dtype, self.ws
         lm, pb = dims.lm, dims.pb
         B, S = ctx["B"], ctx["S"]
@@ -824,25 +901,32 @@ class Engine:
         scale = hd ** -0.5
         tr = self.trainable
         dw = self.grad_buffer("model.norm.weight") if "model.norm.weight" in tr else None
-        dx = ops.rmsnorm_bwd(d_hn, ctx["x_last"], w["model.norm.weight"], ctx["rstd_f"], dw=dw, out=ws.get("dx_a", (M, d), T))
+        R = ctx.get("top_rows", 0)                             # > 0: the top layer ran on B*R compact rows past its attention (forward_hidden)
+        sfx = "_top" if R else ""                              # ... in buffers of their own: the lower layers' keep their shape from step to step
+        dx = ops.rmsnorm_bwd(d_hn, ctx["x_last"], w["model.norm.weight"], ctx["rstd_f"], dw=dw, out=ws.get("dx_a" + sfx, ctx["x_last"].shape, T),
+                             window=(S, R) if R else None)        # (compact rows: dw still summed in the full layout's order)
         # frozen layers only: with trainable layers the wgrad products between a dgrad and its norm would reuse the slab area
         defer_b = self.use_tail_fuse and T == torch.bfloat16 and not self.any_layer_trainable
-        fuse_swiglu_bwd = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and Fd % 64 == 0 and ops.gemm_kernel_id(M, Fd, d) == 2
+        fuse_swiglu_bwd_all = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and Fd % 64 == 0
         la = self.lora_groups
         for l in reversed(range(L)):
             p = f"model.layers.{l}."
             lc = ctx["layers"][l]
             lT = lc.get("lora_T")
             gu, qkv = lc["gu"], lc["qkv"]
+            top = R > 0 and l == L - 1
+            Ml, sfx = (B * R, "_top") if top else (M, "")
+            fuse_swiglu_bwd = fuse_swiglu_bwd_all and ops.gemm_kernel_id(Ml, Fd, d) == 2
+            wt = {"split_k": 1} if top else {}                  # whole tiles, as in forward_hidden
             self._begin_direct(l)
             # ---- MLP
-            dgu = ws.get("dgu", (M, 2 * Fd), T)
+            dgu = ws.get("dgu" + sfx, (Ml, 2 * Fd), T)
             wt_down = self.wT.get(p + "mlp.down_proj.weight") if self.prepared else None
             if fuse_swiglu_bwd and wt_down is not None and l in self.wguT and "down" not in la:
                 # d(act) = dx . W_down never reaches memory: the GEMM epilogue reads gate|up and writes d(gate|up) (EGOMI_EPI_SWIGLU_BWD)
-                ops.mm(dx, wt_down, out=dgu, swiglu_bwd_gu=gu)
+                ops.mm(dx, wt_down, out=dgu, swiglu_bwd_gu=gu, **wt)
             else:
-                d_act = self._dgrad(dx, p + "mlp.down_proj.weight", ws.get("d_act", (M, Fd), T))
+                d_act = self._dgrad(dx, p + "mlp.down_proj.weight", ws.get("d_act" + sfx, (Ml, Fd), T), **wt)
                 if "down" in la:
                     self._lora_bwd(l, "down", dx, lc["act"], d_act, lT["down"])
                 if self.prepared and l in self.wguT and self.gu_il:
@@ -853,30 +937,35 @@ class Engine:
             t_h2 = None
             if self.prepared and l in self.wguT:
                 if defer_b and "gu" not in la:
-                    d_h2, t_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h", (M, d), T), defer_tail=True)
+                    d_h2, t_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h" + sfx, (Ml, d), T), defer_tail=True, **wt)
                 else:
-                    d_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h", (M, d), T))
+                    d_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h" + sfx, (Ml, d), T), **wt)
             elif self.prepared and l in self.wgu_cat:
-                d_h2 = self._dgrad_w(dgu, self.wgu_cat[l], ws.get("d_h", (M, d), T))          # one K = 2*ffn product over [Wgate;Wup] in place
+                d_h2 = self._dgrad_w(dgu, self.wgu_cat[l], ws.get("d_h" + sfx, (Ml, d), T))          # one K = 2*ffn product over [Wgate;Wup] in place
             else:
-                d_h2 = self._dgrad(dgu[:, :Fd], p + "mlp.gate_proj.weight", ws.get("d_h", (M, d), T))
+                d_h2 = self._dgrad(dgu[:, :Fd], p + "mlp.gate_proj.weight", ws.get("d_h" + sfx, (Ml, d), T))
                 self._dgrad(dgu[:, Fd:], p + "mlp.up_proj.weight", d_h2, residual=d_h2)
             if "gu" in la:
                 self._lora_bwd(l, "gu", dgu, lc["h2"], d_h2, lT["gu"], il=lc["gu_il"])
             self._wgrad_stacked([p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], dgu, lc["h2"])
             n2 = p + "post_attention_layernorm.weight"
             d_mid = ops.rmsnorm_bwd(d_h2, lc["x_mid"], w[n2], lc["rstd2"], dx_add=dx,
-                                    dw=self.grad_buffer(n2) if n2 in tr else None, out=ws.get("dx_b", (M, d), T), tail=t_h2)
+                                    dw=self.grad_buffer(n2) if n2 in tr else None, out=ws.get("dx_b" + sfx, (Ml, d), T), tail=t_h2)
             # ---- attention
-            d_ao = self._dgrad(d_mid, p + "self_attn.o_proj.weight", ws.get("d_ao", (M, d), T))
+            d_ao = self._dgrad(d_mid, p + "self_attn.o_proj.weight", ws.get("d_ao" + ("_rows_top" if top else ""), (Ml, d), T), **wt)
             if "o" in la:
                 self._lora_bwd(l, "o", d_mid, lc["ao"], d_ao, lT["o"])
             self._wgrad(p + "self_attn.o_proj.weight", d_mid, lc["ao"])
+            if top:                                            # back to all rows: d_ao and d_mid are zero below the window (_top_buffers)
+                d_ao_f, d_mid_f = self._top_buffers(B, S, R)[2:]
+                d_ao_f.view(B, S, d)[:, S - R:].copy_(d_ao.view(B, R, d))
+                d_mid_f.view(B, S, d)[:, S - R:].copy_(d_mid.view(B, R, d))
+                d_ao, d_mid = d_ao_f, d_mid_f
             dqkv = ws.get("dqkv", (M, 3 * d), T)
             if lc["lse"] is not None:
                 # dq, dk leave the kernels already rotated back (the inverse RoPE pass is fused into their epilogues)
                 ops.attn_bwd(qkv, lc["ao"], lc["lse"], d_ao, dqkv, ws.get("att_delta", (B, H, S), torch.float32), B, S, H, hd, scale,
-                             causal=True, key_mask=ctx["key_mask"], rope=(self.cos, self.sin))
+                             causal=True, key_mask=ctx["key_mask"], rope=(self.cos, self.sin), q_rows=R if top else 0)
             else:
                 self._attention_bwd(qkv, lc["P"], d_ao, dqkv, B, S, H, hd, scale)
                 ops.rope_(dqkv, self.cos, self.sin, M, S, 0, 2 * H, hd, 3 * d, inverse=True)

@@ -384,10 +384,16 @@ def rmsnorm(x, w, eps, rstd=None, out=None, tail=None, tail_residual=None):
     return out
 
 
-def rmsnorm_bwd(dy, x, w, rstd, dx_add=None, dw=None, out=None, tail=None):
-    """tail: as in rmsnorm() — dy's rows >= row0 are still the slabs of the dgrad product that made dy (egomi_rmsnorm_bwd_tail)."""
+def rmsnorm_bwd(dy, x, w, rstd, dx_add=None, dw=None, out=None, tail=None, window=None):
+    """tail: as in rmsnorm() — dy's rows >= row0 are still the slabs of the dgrad product that made dy (egomi_rmsnorm_bwd_tail).
+    window = (S, R): the operands hold the last R rows of every S-row sequence only; dw gets the bits of the full-layout call whose other
+    rows have dy = 0 (egomi_rmsnorm_bwd_rows)."""
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]
     out = torch.empty_like(x) if out is None else out
+    if window is not None:
+        call("egomi_rmsnorm_bwd_rows", P(dy), P(x), P(w), P(rstd), P(out), P(dx_add), P(dw), c_i(rows), c_i(cols), c_i(window[0]), c_i(window[1]),
+             c_i(dt(x.dtype)), S())
+        return out
     if tail is not None:
         call("egomi_rmsnorm_bwd_tail", P(dy), P(x), P(w), P(rstd), P(out), P(dx_add), P(dw), c_i(rows), c_i(cols), c_i(tail[0]), c_p(tail[2]), c_i(tail[1]),
              c_i(dt(x.dtype)), S())
@@ -597,7 +603,8 @@ class AttnDesc(ctypes.Structure):
                 ("dout", c_p), ("delta", c_p), ("dq", c_p), ("dk", c_p), ("dv", c_p), ("key_mask", c_p),
                 ("B", c_i), ("H", c_i), ("S", c_i), ("head_dim", c_i),
                 ("ld_qkv", c_i64), ("ld_o", c_i64), ("ld_dqkv", c_i64),
-                ("scale", c_f), ("causal", c_i), ("dtype", c_i), ("rope_cos", c_p), ("rope_sin", c_p)]
+                ("scale", c_f), ("causal", c_i), ("dtype", c_i), ("rope_cos", c_p), ("rope_sin", c_p),
+                ("q_rows", c_i)]
 
 
 def _attn_desc(qkv, B, Sq, H, hd, scale, causal, key_mask):
@@ -611,18 +618,22 @@ def _attn_desc(qkv, B, Sq, H, hd, scale, causal, key_mask):
     return d
 
 
-def attn_fwd(qkv, B, Sq, H, hd, scale, out, lse, causal=True, key_mask=None):
-    """qkv [B*S, 3*H*hd] (q|k|v column blocks) -> out [B*S, H*hd], lse fp32 [B,H,S]."""
+def attn_fwd(qkv, B, Sq, H, hd, scale, out, lse, causal=True, key_mask=None, q_rows=0):
+    """qkv [B*S, 3*H*hd] (q|k|v column blocks) -> out [B*S, H*hd], lse fp32 [B,H,S].
+    q_rows = R in (0, S): only rows >= S - R of out / lse are promised (include/egomi.h, egomi_attn_desc.q_rows)."""
     d = _attn_desc(qkv, B, Sq, H, hd, scale, causal, key_mask)
+    d.q_rows = int(q_rows)
     d.o, d.lse, d.ld_o = out.data_ptr(), lse.data_ptr() if lse is not None else None, out.stride(0)
     call("egomi_attn_fwd", ctypes.byref(d), S())
     return out
 
 
-def attn_bwd(qkv, out, lse, dout, dqkv, delta, B, Sq, H, hd, scale, causal=True, key_mask=None, rope=None):
+def attn_bwd(qkv, out, lse, dout, dqkv, delta, B, Sq, H, hd, scale, causal=True, key_mask=None, rope=None, q_rows=0):
     """dq|dk|dv written into the column blocks of dqkv [B*S, 3*H*hd]; delta fp32 [B,H,S] is scratch.
-    rope=(cos, sin) fp32 [>=S, hd/2]: dq and dk come out rotated back (== rope_(dqkv, inverse=True) afterwards)."""
+    rope=(cos, sin) fp32 [>=S, hd/2]: dq and dk come out rotated back (== rope_(dqkv, inverse=True) afterwards).
+    q_rows = R in (0, S): the caller promises dout == 0 at rows < S - R; dq|dk|dv are what q_rows = 0 gives, at every row."""
     d = _attn_desc(qkv, B, Sq, H, hd, scale, causal, key_mask)
+    d.q_rows = int(q_rows)
     if rope is not None:
         cos, sin = rope
         if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape[0] < Sq or cos.shape[1] != hd // 2 \

@@ -534,10 +534,16 @@ class TrajPointLLMForCausalLM(nn.Module):
         B, S = input_ids.shape
         if fps_start is None and point_clouds is not None:
             fps_start = torch.randint(0, point_clouds.shape[1], (B,), dtype=torch.long)
-        hn = eng.forward_hidden(input_ids, attention_mask, point_clouds, fps_start, save=backward)
-        d = hn.shape[1]
         Lp = int(prompt_len)
-        hs = hn.view(B, S, d)[:, Lp - 1:S - 1].reshape(-1, d)
+        # the loss reads rows [Lp-1, S-1) only: where the engine can, its top decoder layer runs on the R = S - Lp + 1 rows from Lp-1 on
+        # (a window that ends with the sequence, as the attention kernels' query window needs) and hn comes back compact [B*R, d]
+        hn = eng.forward_hidden(input_ids, attention_mask, point_clouds, fps_start, save=backward, loss_from=Lp - 1 if backward else None)
+        d = hn.shape[1]
+        R = eng.ctx.get("top_rows", 0) if backward else 0
+        if R:
+            hs = hn.view(B, R, d)[:, :R - 1].reshape(-1, d)
+        else:
+            hs = hn.view(B, S, d)[:, Lp - 1:S - 1].reshape(-1, d)
         tg = input_ids[:, Lp:].reshape(-1).contiguous()
         lg = eng.logits(hs, padded=backward)
         ls, cnt = ops.cross_entropy(lg, tg, pad_token_id, dlogits=lg if backward else None, grad_scale=grad_scale)
@@ -545,9 +551,12 @@ class TrajPointLLMForCausalLM(nn.Module):
         if backward:
             self._begin_backward(explicit=True)
             d_hs = eng.backward_logits(lg, hs)
-            d_hn = eng.ws.get("d_hn_full", (B, S, d), eng.dtype, zero=True)
-            d_hn[:, Lp - 1:S - 1] = d_hs.view(B, S - Lp, d)
-            eng.backward_hidden(d_hn.view(B * S, d))
+            if R:
+                eng.backward_hidden(eng.compact_loss_grad(d_hs))
+            else:
+                d_hn = eng.ws.get("d_hn_full", (B, S, d), eng.dtype, zero=True)
+                d_hn[:, Lp - 1:S - 1] = d_hs.view(B, S - Lp, d)
+                eng.backward_hidden(d_hn.view(B * S, d))
             self._publish_grads()
         return loss[0]
 

@@ -227,6 +227,12 @@ typedef struct egomi_attn_desc {
      * already rotated back (what egomi_rope(..., inverse=1) on the bf16 dq/dk would give, bit for bit), so the caller
      * drops that pass.  NULL = plain dq/dk. */
     const float* rope_cos; const float* rope_sin;
+    /* optional query window: 0 = every row.  0 < q_rows < S: the caller reads o and lse only at rows s >= S - q_rows of every sequence and
+     * passes dout == 0 at rows s < S - q_rows.  o and lse at rows >= S - q_rows, and dq, dk, dv at EVERY row, then equal the q_rows = 0
+     * call on the same inputs (dq is zero below the window); o and lse below the window are unspecified (written or left alone).  The
+     * kernels only skip whole (query block, key block) pairs; every delta word the dK/dV kernel reads is written by the same call.
+     * q_rows >= S behaves as 0; head_dim 64 and the first / second kernel forms may ignore it (they compute everything). */
+    int q_rows;
 } egomi_attn_desc;
 int egomi_attn_fwd(const egomi_attn_desc* desc, egomi_stream_t stream);
 int egomi_attn_bwd(const egomi_attn_desc* desc, egomi_stream_t stream);
@@ -475,6 +481,10 @@ int egomi_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int ro
                       egomi_stream_t stream);
 int egomi_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx, const void* dx_add,
                       float* dw, int rows, int cols, int dtype, egomi_stream_t stream);
+/* egomi_rmsnorm_bwd on COMPACT rows: dy, x, rstd, dx, dx_add hold only the last `win` rows of every sequence of `seq` rows (rows = sequences * win).
+ * dw is summed in the order of the full-layout call whose other rows have dy = 0, so it has that call's bits. */
+int egomi_rmsnorm_bwd_rows(const void* dy, const void* x, const void* w, const float* rstd, void* dx, const void* dx_add,
+                           float* dw, int rows, int cols, int seq, int win, int dtype, egomi_stream_t stream);
 /* Tail forms: rows >= row0 of the input (x resp. dy) are still the `slices` fp32 K-slice slabs [slices][rows - row0][cols] an
  * EGOMI_EPI_SLABS product left (egomi_gemm_tail_plan); they are summed in slice order (+ residual rows for the forward form),
  * rounded, WRITTEN to x / dy, and normalised in the same pass — bit-identical to the combine pass followed by
