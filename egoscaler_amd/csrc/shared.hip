@@ -17,6 +17,21 @@
 // Then, in the same launch, 8 lanes per query (hd / 8 dims each) continue the online softmax over the row's own suffix keys from
 // global memory and store O.  Every sum has a fixed order that does not depend on the query's slot j: a replay is bit-equal, and
 // permuting the samples of a clip permutes the output rows bit for bit.
+//
+// Row-table form (egomi_attn_decode_shared_rows; beam search on the split cache): K = beams per clip, and suffix key t of logical row r
+// lives in PHYSICAL suffix row sfx_row[r, t] of ks, vs [n_phys, H, Tmax, hd]: a beam's suffix is the path through its ancestors' rows.
+//   sfx_row [B*K, >= T_len] int32; an entry outside [0, n_phys) is a masked key (its address is clamped to row 0, its score selected away).
+//   Prompt phase: the code above, unchanged (the kernels are templated on ROWS; ROWS = false is egomi_attn_decode_shared, bit for bit).
+//   Suffix phase: the merged prompt state (m, l, O) of every query goes through LDS, and the workgroup's 32 eight-lane groups are dealt
+//       out as NS = 32 / K slices per query: group g serves query g / NS, slice g % NS (groups >= K * NS idle).  Slice s walks the keys
+//       [s * C, min((s + 1) * C, T_len)), C = ceil(T_len / NS) rounded up to 4 (consume_keys' round), so the boundaries depend on
+//       (K, T_len) only.  Each lane loads its hd / 8 dims of the key / value rows it is told by the table (the table entry is one
+//       broadcast load per group and key).  Slice 0 continues from the prompt state; slices >= 1 start empty, leave their (m, l, O) in
+//       LDS (the prompt phase's buffers, free by then), and slice 0's group merges the ceil(T_len / C) non-empty ones in slice order and
+//       stores O.  At K = 4, T_len = 160 that is 5 dependent rounds of global loads per group instead of 40.
+//   Order of the sums of a row: prompt (as above), slice 0 in key order on top of it, slices 1.. each in key order from empty, merge in
+//       slice order: a function of (K, S0, T_len), never of the slot j.  No atomics; a replay is bit-equal; permuting the beams of a clip
+//       (queries and table rows together) permutes the output rows bit for bit.
 #include "common.h"
 #include <math.h>
 
@@ -103,13 +118,87 @@ __device__ __forceinline__ void suffix_and_store(RowState<HD / 8>& st, const flo
     }
 }
 
+// Row-table suffix (see the header): sAcc [32][pitch], sM, sL [32] hold the prompt state of query qi at index qi on entry (written by
+// other threads: the caller has synchronised).  Every thread of the workgroup calls this.
+template <typename T, int HD>
+__device__ __forceinline__ void suffix_rows_and_store(float* sAcc, int pitch, float* sM, float* sL, const T* q, long long ld_q, float scale,
+                                                      const T* ks, const T* vs, const int* sfx_row, long long ld_row, int n_phys, T* out,
+                                                      long long ld_o, int b, int K, int h, int H, int Tmax, int Tlen) {
+    constexpr int DPT = HD / 8;
+    const int g = threadIdx.x >> 3, sub = threadIdx.x & 7;
+    const int NS = 32 / K, qi = g / NS, sl = g % NS;
+    const bool live = qi < K;
+    const int C = ((Tlen + NS - 1) / NS + 3) & ~3;                  // keys per slice
+    const int used = C > 0 ? (Tlen + C - 1) / C : 0;                // non-empty slices
+    const int t_lo = sl * C;
+    const int n = !live || t_lo >= Tlen ? 0 : (Tlen - t_lo < C ? Tlen - t_lo : C);
+    const long long row = (long long)b * K + (live ? qi : K - 1);
+    float qd[DPT];
+    load_chunk<T, DPT>(q + row * ld_q + (long long)h * HD + sub * DPT, qd);
+#pragma unroll
+    for (int j = 0; j < DPT; ++j) qd[j] *= scale;
+    RowState<DPT> st;
+    st.m = -INFINITY; st.l = 0.f;
+#pragma unroll
+    for (int j = 0; j < DPT; ++j) st.acc[j] = 0.f;
+    if (live && sl == 0) {
+        st.m = sM[qi]; st.l = sL[qi];
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) st.acc[j] = sAcc[qi * pitch + sub * DPT + j];
+    }
+    __syncthreads();                                                // the prompt states have been read: the buffers now hold slices
+    if (n > 0) {
+        const int* tab = sfx_row + row * ld_row + t_lo;
+        const long long hoff = (long long)h * Tmax + t_lo;
+        auto phys = [&](int key) { const int pr = tab[key]; return pr >= 0 && pr < n_phys ? pr : -1; };
+        auto at = [&](const T* base, int key) {
+            const int pr = phys(key);
+            return base + (((long long)(pr < 0 ? 0 : pr) * H) * Tmax + hoff + key) * HD + sub * DPT;
+        };
+        consume_keys<DPT>(st, qd, n,
+                          [&](int key, float (&v)[DPT]) { load_chunk<T, DPT>(at(ks, key), v); },
+                          [&](int key, float (&v)[DPT]) {
+                              load_chunk<T, DPT>(at(vs, key), v);
+                              if (phys(key) < 0) {                  // p = 0 there, and 0 * (whatever row 0 holds) must stay 0
+#pragma unroll
+                                  for (int j = 0; j < DPT; ++j) v[j] = 0.f;
+                              }
+                          },
+                          [&](int key) { return phys(key) >= 0; });
+    }
+    if (live && sl > 0 && sl < used) {
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) sAcc[g * pitch + sub * DPT + j] = st.acc[j];
+        if (sub == 0) { sM[g] = st.m; sL[g] = st.l; }
+    }
+    __syncthreads();
+    if (live && sl == 0) {
+        for (int s = 1; s < used; ++s) {
+            const float m_own = sM[g + s], l_own = sL[g + s];
+            const float m_new = fmaxf(st.m, m_own);
+            const float m_safe = m_new == -INFINITY ? 0.f : m_new;
+            const float f_old = st.m == -INFINITY ? 0.f : __expf(st.m - m_safe);
+            const float f_own = m_own == -INFINITY ? 0.f : __expf(m_own - m_safe);
+#pragma unroll
+            for (int j = 0; j < DPT; ++j) st.acc[j] = st.acc[j] * f_old + sAcc[(g + s) * pitch + sub * DPT + j] * f_own;
+            st.l = st.l * f_old + l_own * f_own;
+            st.m = m_new;
+        }
+        const float inv = st.l > 0.f ? 1.0f / st.l : 0.f;
+        T* o = out + row * ld_o + (long long)h * HD + sub * DPT;
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) Cvt<T>::st(o + j, st.l > 0.f ? st.acc[j] * inv : 0.f);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // VALU form: any dtype, hd 32 / 64 / 128.  Thread t: query t >> 3, dims (t & 7) * hd/8 ...
 // ------------------------------------------------------------------------------------------------
-template <typename T, int HD>
+template <typename T, int HD, bool ROWS>
 __global__ __launch_bounds__(256) void attn_decode_shared_valu_kernel(const T* q, long long ld_q, const T* kp, const T* vp, const uint8_t* key_mask,
-                                                                      long long ld_mask, const T* ks, const T* vs, T* out, long long ld_o, int K,
-                                                                      int H, int Sp, int S0, int Tmax, int Tlen, float scale) {
+                                                                      long long ld_mask, const T* ks, const T* vs, const int* sfx_row,
+                                                                      long long ld_row, int n_phys, T* out, long long ld_o, int K, int H, int Sp,
+                                                                      int S0, int Tmax, int Tlen, float scale) {
     constexpr int DPT = HD / 8, CPR = HD / 8;
     __shared__ __attribute__((aligned(16))) float sK[32 * HD];
     __shared__ __attribute__((aligned(16))) float sV[32 * HD];
@@ -150,7 +239,16 @@ __global__ __launch_bounds__(256) void attn_decode_shared_valu_kernel(const T* q
                           [&](int key, float (&v)[DPT]) { load_chunk<float, DPT>(sV + key * HD + sub * DPT, v); },
                           [&](int key) { return sOk[key] != 0; });
     }
-    suffix_and_store<T, HD>(st, qd, ks, vs, out, ld_o, row, h, H, Tmax, Tlen, sub, live);
+    if constexpr (ROWS) {                                           // the prompt state of query qq -> sK [32][HD], sV [0..31] (m), [32..63] (l)
+        __syncthreads();                                            // the last tile has been read
+#pragma unroll
+        for (int j = 0; j < DPT; ++j) sK[qq * HD + sub * DPT + j] = st.acc[j];
+        if (sub == 0) { sV[qq] = st.m; sV[32 + qq] = st.l; }
+        __syncthreads();
+        suffix_rows_and_store<T, HD>(sK, HD, sV, sV + 32, q, ld_q, scale, ks, vs, sfx_row, ld_row, n_phys, out, ld_o, b, K, h, H, Tmax, Tlen);
+    } else {
+        suffix_and_store<T, HD>(st, qd, ks, vs, out, ld_o, row, h, H, Tmax, Tlen, sub, live);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -182,11 +280,12 @@ template <int HD> __device__ __forceinline__ bf16x8 lds_tr8(const char* tile, in
     return r;
 }
 
-template <int HD>
+template <int HD, bool ROWS>
 __global__ __launch_bounds__(256) void attn_decode_shared_mfma_kernel(const bf16_t* q, long long ld_q, const bf16_t* kp, const bf16_t* vp,
                                                                       const uint8_t* key_mask, long long ld_mask, const bf16_t* ks,
-                                                                      const bf16_t* vs, bf16_t* out, long long ld_o, int K, int H, int Sp, int S0,
-                                                                      int Tmax, int Tlen, float scale) {
+                                                                      const bf16_t* vs, const int* sfx_row, long long ld_row, int n_phys,
+                                                                      bf16_t* out, long long ld_o, int K, int H, int Sp, int S0, int Tmax,
+                                                                      int Tlen, float scale) {
     constexpr int DPT = HD / 8, ND = HD / 32, NK = HD / 16, CPR = HD / 8, PITCH = HD + 1;
     __shared__ __attribute__((aligned(16))) char sV[4][32 * HD * 2];
     __shared__ float sAcc[32 * PITCH];
@@ -309,6 +408,10 @@ __global__ __launch_bounds__(256) void attn_decode_shared_mfma_kernel(const bf16
         __syncthreads();
     }
 
+    if constexpr (ROWS) {                                           // the merge loop's last barrier has published sAcc / sM / sL
+        suffix_rows_and_store<bf16_t, HD>(sAcc, PITCH, sM, sL, q, ld_q, scale, ks, vs, sfx_row, ld_row, n_phys, out, ld_o, b, K, h, H, Tmax, Tlen);
+        return;
+    }
     // 8 lanes per query: the prompt state, then the row's own suffix
     const int qq = threadIdx.x >> 3, sub = threadIdx.x & 7;
     const bool live = qq < K;
@@ -326,30 +429,53 @@ __global__ __launch_bounds__(256) void attn_decode_shared_mfma_kernel(const bf16
 
 }  // namespace
 
-extern "C" int egomi_attn_decode_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
-                                        int64_t ld_mask, const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H,
-                                        int hd, int Sp, int S0, int Tmax, int T_len, float scale, int dtype, egomi_stream_t stream) {
+// both entry points: sfx_row == nullptr is the own-row suffix of egomi_attn_decode_shared
+static int launch_shared(bool rows, const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
+                         int64_t ld_mask, const void* ksuffix, const void* vsuffix, const int32_t* sfx_row, int64_t ld_row, int n_phys, void* out,
+                         int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0, int Tmax, int T_len, float scale, int dtype,
+                         egomi_stream_t stream) {
     if (!q || !kprompt || !vprompt || !out) return EGOMI_E_BADARG;
     if (T_len > 0 && (!ksuffix || !vsuffix)) return EGOMI_E_BADARG;
+    if (rows && T_len > 0 && !sfx_row) return EGOMI_E_BADARG;
     if (B <= 0 || H <= 0 || K < 1 || K > 32 || S0 <= 0 || S0 > Sp || T_len < 0 || T_len > Tmax || ld_q % 8 || ld_q < (int64_t)H * hd ||
         ld_o < (int64_t)H * hd)
         return EGOMI_E_SHAPE;
+    if (rows && T_len > 0 && (ld_row < T_len || n_phys < 1)) return EGOMI_E_SHAPE;
     if (key_mask && ld_mask < S0) return EGOMI_E_SHAPE;
     if (dtype != EGOMI_BF16 && dtype != EGOMI_F32) return EGOMI_E_BADARG;
     if (hd != 32 && hd != 64 && hd != 128) return EGOMI_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
 #define SHK(KERNEL, TT)                                                                                                                 \
     EGOMI_LAUNCH((KERNEL), dim3(B * H), dim3(256), 0, s, (const TT*)q, (long long)ld_q, (const TT*)kprompt, (const TT*)vprompt, key_mask, \
-                 (long long)ld_mask, (const TT*)ksuffix, (const TT*)vsuffix, (TT*)out, (long long)ld_o, K, H, Sp, S0, Tmax, T_len, scale)
-    if (dtype == EGOMI_BF16) {
-        if (hd == 128) SHK(attn_decode_shared_mfma_kernel<128>, bf16_t);
-        else if (hd == 64) SHK(attn_decode_shared_mfma_kernel<64>, bf16_t);
-        else SHK((attn_decode_shared_valu_kernel<bf16_t, 32>), bf16_t);
-    } else {
-        if (hd == 128) SHK((attn_decode_shared_valu_kernel<float, 128>), float);
-        else if (hd == 64) SHK((attn_decode_shared_valu_kernel<float, 64>), float);
-        else SHK((attn_decode_shared_valu_kernel<float, 32>), float);
+                 (long long)ld_mask, (const TT*)ksuffix, (const TT*)vsuffix, (const int*)sfx_row, (long long)ld_row, n_phys, (TT*)out,     \
+                 (long long)ld_o, K, H, Sp, S0, Tmax, T_len, scale)
+#define SHF(ROWS)                                                                         \
+    if (dtype == EGOMI_BF16) {                                                            \
+        if (hd == 128) SHK((attn_decode_shared_mfma_kernel<128, ROWS>), bf16_t);          \
+        else if (hd == 64) SHK((attn_decode_shared_mfma_kernel<64, ROWS>), bf16_t);       \
+        else SHK((attn_decode_shared_valu_kernel<bf16_t, 32, ROWS>), bf16_t);             \
+    } else {                                                                              \
+        if (hd == 128) SHK((attn_decode_shared_valu_kernel<float, 128, ROWS>), float);    \
+        else if (hd == 64) SHK((attn_decode_shared_valu_kernel<float, 64, ROWS>), float); \
+        else SHK((attn_decode_shared_valu_kernel<float, 32, ROWS>), float);               \
     }
+    if (rows) { SHF(true) } else { SHF(false) }
+#undef SHF
 #undef SHK
     return egomi_launch_status();
+}
+
+extern "C" int egomi_attn_decode_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
+                                        int64_t ld_mask, const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H,
+                                        int hd, int Sp, int S0, int Tmax, int T_len, float scale, int dtype, egomi_stream_t stream) {
+    return launch_shared(false, q, ld_q, kprompt, vprompt, key_mask, ld_mask, ksuffix, vsuffix, nullptr, 0, 0, out, ld_o, B, K, H, hd, Sp, S0,
+                         Tmax, T_len, scale, dtype, stream);
+}
+
+extern "C" int egomi_attn_decode_shared_rows(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
+                                             int64_t ld_mask, const void* ksuffix, const void* vsuffix, const int32_t* sfx_row, int64_t ld_row,
+                                             int n_phys, void* out, int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0, int Tmax,
+                                             int T_len, float scale, int dtype, egomi_stream_t stream) {
+    return launch_shared(true, q, ld_q, kprompt, vprompt, key_mask, ld_mask, ksuffix, vsuffix, sfx_row, ld_row, n_phys, out, ld_o, B, K, H, hd,
+                         Sp, S0, Tmax, T_len, scale, dtype, stream);
 }

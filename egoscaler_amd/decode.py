@@ -140,8 +140,17 @@ def attn_decode_shared(q, ld_q, kp, vp, key_mask, ks, vs, out, B, K, H, hd, Sp, 
          c_i(dt(q.dtype)), S())
 
 
+def attn_decode_shared_rows(q, ld_q, kp, vp, key_mask, ks, vs, sfx_row, n_phys, out, B, K, H, hd, Sp, S0, Tmax, T_len, scale):
+    """attn_decode_shared with suffix key t of logical row r read from physical suffix row sfx_row[r, t] of ks / vs [n_phys, H, Tmax, hd]
+    (beam search on the split cache; entries outside [0, n_phys) are masked keys)  (include/egomi.h egomi_attn_decode_shared_rows)."""
+    call("egomi_attn_decode_shared_rows", P(q), c_i64(ld_q), P(kp), P(vp), P(key_mask), c_i64(key_mask.stride(0) if key_mask is not None else 0),
+         P(ks), P(vs), P(sfx_row), c_i64(sfx_row.stride(0) if sfx_row is not None else 0), c_i(n_phys), P(out), c_i64(out.stride(0)), c_i(B),
+         c_i(K), c_i(H), c_i(hd), c_i(Sp), c_i(S0), c_i(Tmax), c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+
+
 class Decoder:
-    def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None, weight_dtype=None, samples_per_prompt=1, max_new_tokens=None):
+    def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None, weight_dtype=None, samples_per_prompt=1, max_new_tokens=None,
+                 split_cache=False):
         """B = rows of the cache and of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...)).
         kv_dtype="fp8": the KV cache holds e4m3fn codes kc / vc uint8 [L, B, H, Smax, hd] and fp32 scales ks / vs [L, B, H, Smax], one per
         (layer, row, head, position) and tensor (csrc/kv8.hip); None: the model's dtype, as before.
@@ -152,7 +161,11 @@ class Decoder:
         row r = b * K + j.  The cache is a prompt cache kp / vp [L, B / K, H, Sp, hd] (Sp = max_len - Tmax, one row per PROMPT, filled by one
         prefill per prompt) plus a suffix cache ksfx / vsfx [L, B, H, Tmax, hd] (the tokens each row generated) instead of
         [L, B, H, max_len, hd]; step() attends over both with egomi_attn_decode_shared (csrc/shared.hip).  sample() / greedy() are unchanged:
-        same rows, same seed, same draws as the expanded decoder."""
+        same rows, same seed, same draws as the expanded decoder.
+        split_cache=True with num_beams = nb > 1 (needs max_new_tokens = Tmax): beam search on the same prompt / suffix layout, kp / vp
+        [L, B / nb, H, Sp, hd] and ksfx / vsfx [L, B, H, Tmax, hd] with kc = vc = None.  A beam's suffix is the path through its ancestors'
+        rows, so step() appends into the row's own suffix row and attends with egomi_attn_decode_shared_rows through kv_row[:, S0:]
+        (egomi_beam_update keeps that table as in the dense layout; its columns below S0 are not read).  beam() is unchanged."""
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', not {kv_dtype!r}")
         if weight_dtype not in (None, "fp8"):
@@ -173,17 +186,31 @@ class Decoder:
                 raise ValueError(f"{B} decoder rows are not a multiple of samples_per_prompt = {K}")
             if max_new_tokens is None or not 0 < int(max_new_tokens) < max_len:
                 raise ValueError("samples_per_prompt > 1 needs max_new_tokens (the suffix cache length) in 1 .. max_len - 1")
+        if split_cache:
+            if int(num_beams) <= 1:
+                raise ValueError("split_cache needs num_beams > 1 (independent samples of one prompt: samples_per_prompt)")
+            if int(num_beams) > 32:
+                raise ValueError(f"split_cache supports at most 32 beams, not {num_beams}")
+            if kv_dtype == "fp8":
+                raise NotImplementedError("split_cache with an fp8 KV cache is not built")
+            if B % int(num_beams):
+                raise ValueError(f"{B} decoder rows are not a multiple of num_beams = {num_beams}")
+            if max_new_tokens is None or not 0 < int(max_new_tokens) < max_len:
+                raise ValueError("split_cache needs max_new_tokens (the suffix cache length) in 1 .. max_len - 1")
         self.eng, self.B, self.Smax, self.nb, self.kv_dtype = engine, B, max_len, int(num_beams), kv_dtype
         self.K = K
+        self.G = K if K > 1 else int(num_beams) if split_cache else 1      # logical rows per prompt-cache row
+        self.split = self.G > 1                                            # prompt cache + suffix cache instead of the dense one
+        G = self.G
         lm = engine.dims.lm
         L, H, hd, d, Fd, V = lm.num_hidden_layers, lm.num_attention_heads, lm.head_dim, lm.hidden_size, lm.intermediate_size, lm.vocab_size
         T, dev = engine.dtype, engine.device
         self.fp8 = kv_dtype == "fp8"
-        if K > 1:
+        if self.split:
             self.Tmax = int(max_new_tokens)
             self.Sp = max_len - self.Tmax
             self.kc = self.vc = None
-            self.kp = torch.zeros(L, B // K, H, self.Sp, hd, dtype=T, device=dev)
+            self.kp = torch.zeros(L, B // G, H, self.Sp, hd, dtype=T, device=dev)
             self.vp = torch.zeros_like(self.kp)
             self.ksfx = torch.zeros(L, B, H, self.Tmax, hd, dtype=T, device=dev)
             self.vsfx = torch.zeros_like(self.ksfx)
@@ -238,12 +265,12 @@ class Decoder:
                           "down": ops.mm_w8_slabs(self.act, *q["down"], self.gws, count_only=True)}
             if not all(self.fused.values()):
                 raise ValueError(f"fp8 decode weights cannot run this model's projection shapes ({self.fused})")
-            if K > 1:
+            if self.split:
                 self.fused["qkv"] = 0
         elif T == torch.bfloat16 and os.environ.get("EGOMI_DECODE_FUSED", "1") != "0" and B <= 512:
-            # shared-prompt mode rotates at S0 + t but appends at suffix slot t; egomi_qkv_finish takes one `pos` for both, so its q|k|v
+            # the split cache rotates at S0 + t but appends at suffix slot t; egomi_qkv_finish takes one `pos` for both, so its q|k|v
             # product keeps the unfused mm + rope_ + kv_append path
-            self.fused["qkv"] = 0 if K > 1 else ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
+            self.fused["qkv"] = 0 if self.split else ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
             self.fused["o"] = ops.mm_slabs(self.ao, w["model.layers.0.self_attn.o_proj.weight"], self.x_mid, self.gws, count_only=True)
             self.fused["down"] = ops.mm_slabs(self.act, w["model.layers.0.mlp.down_proj.weight"], self.x, self.gws, count_only=True)
 
@@ -302,7 +329,7 @@ class Decoder:
             raise ValueError("prompt + new tokens exceed the decoder's cache length")
         if B * nb != self.B:
             raise ValueError(f"{B} prompts x {nb} beams do not fill the decoder's {self.B} rows")
-        if self.K > 1 and (S0 > self.Sp or total_new > self.Tmax):
+        if self.split and (S0 > self.Sp or total_new > self.Tmax):
             raise ValueError(f"prompt length {S0} / {total_new} new tokens exceed the decoder's prompt cache ({self.Sp}) / suffix cache ({self.Tmax})")
         if nb > 1:
             input_ids, mask = input_ids.repeat_interleave(nb, 0), mask.repeat_interleave(nb, 0)
@@ -318,12 +345,12 @@ class Decoder:
         self._append(l, None, qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), B, Sq, 0)
 
     def _append(self, l, b, k, v, ld, B, Sq, pos0, suffix=False):
-        """k / v rows -> layer l of the cache (all rows, or row b alone) at positions pos0 .. pos0 + Sq - 1.  Shared-prompt mode: the
-        prompt cache (prefill: rows are prompts), or with suffix=True the suffix cache (step: rows are samples, pos0 = suffix slot)."""
+        """k / v rows -> layer l of the cache (all rows, or row b alone) at positions pos0 .. pos0 + Sq - 1.  Split cache: the prompt
+        cache (prefill: rows are prompts), or with suffix=True the suffix cache (step: rows are samples / beams, pos0 = suffix slot)."""
         lm = self.eng.dims.lm
         H, hd = lm.num_attention_heads, lm.head_dim
         sel = (l,) if b is None else (l, b)
-        if self.K > 1:
+        if self.split:
             kc, vc, Smax = (self.ksfx, self.vsfx, self.Tmax) if suffix else (self.kp, self.vp, self.Sp)
             kv_append(k, v, ld, kc[sel], vc[sel], B, Sq, H, hd, Smax, pos0)
             return
@@ -334,14 +361,19 @@ class Decoder:
 
     def _attend(self, l, pos):
         """Attention of this step's queries (self.qkv[:, :d]) over layer l of the cache, keys 0 .. pos, into self.ao: the read side of
-        _append.  Shared-prompt mode: prompt cache + the row's suffix; otherwise the dense or fp8 cache, each row's own physical row or,
-        in beam mode, the rows that self.kv_row names."""
+        _append.  Split cache: prompt cache + the row's suffix (beam mode: the suffix rows that self.kv_row[:, S0:] names); otherwise the
+        dense or fp8 cache, each row's own physical row or, in beam mode, the rows that self.kv_row names."""
         lm = self.eng.dims.lm
         B, H, hd = self.B, lm.num_attention_heads, lm.head_dim
         ld_q, scale = 3 * lm.hidden_size, hd ** -0.5
-        if self.K > 1:
-            attn_decode_shared(self.qkv, ld_q, self.kp[l], self.vp[l], self.mask[::self.K], self.ksfx[l], self.vsfx[l], self.ao, B // self.K,
-                               self.K, H, hd, self.Sp, self.S0, self.Tmax, pos - self.S0 + 1, scale)
+        if self.split:
+            G = self.G
+            geom = (self.ao, B // G, G, H, hd, self.Sp, self.S0, self.Tmax, pos - self.S0 + 1, scale)
+            if self.kv_row is None:
+                attn_decode_shared(self.qkv, ld_q, self.kp[l], self.vp[l], self.mask[::G], self.ksfx[l], self.vsfx[l], *geom)
+            else:
+                attn_decode_shared_rows(self.qkv, ld_q, self.kp[l], self.vp[l], self.mask[::G], self.ksfx[l], self.vsfx[l],
+                                        self.kv_row[:, self.S0:], B, *geom)
             return
         cache = (self.kc[l], self.vc[l], self.ks[l], self.vs[l]) if self.fp8 else (self.kc[l], self.vc[l])
         if self.kv_row is None:
@@ -366,10 +398,12 @@ class Decoder:
         return self._share_logits(B, S0)
 
     def _share_logits(self, B, S0):
-        """Shared-prompt mode: every sample of a prompt starts from the prompt's step-0 logits (HF prefills K identical rows)."""
+        """Shared-prompt mode: every sample of a prompt starts from the prompt's step-0 logits (HF prefills K identical rows).  Beams read
+        their item's row themselves (egomi_beam_rows' lg_div)."""
+        if self.split:
+            self.S0 = S0
         if self.K == 1:
             return self.lg[:B]
-        self.S0 = S0
         self.lg.copy_(self.lg[:B].repeat_interleave(self.K, 0))
         return self.lg
 
@@ -422,7 +456,7 @@ class Decoder:
                 else:
                     ops.mm(self.h, self.wqkv[l], out=self.qkv, workspace=self.gws)
                 ops.rope_(self.qkv, eng.cos, eng.sin, B, 1, pos, 2 * H, hd, 3 * d)
-                if self.K > 1:
+                if self.split:
                     self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos - self.S0, suffix=True)
                 else:
                     self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos)

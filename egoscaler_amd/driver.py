@@ -185,7 +185,7 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
         batch = data.batch(idx, device, args.max_traj_token)
         prompts, tokens = batch["prompts"], batch["tokens"]
         max_new = tokens.shape[1] - prompts.shape[1]
-        beam = {} if num_beams == 1 else {"num_beams": num_beams}
+        beam = {} if num_beams == 1 else {"num_beams": num_beams, "kv_cache_layout": getattr(args, "kv_cache_layout", None)}
         if K > 1:
             beam = {"num_return_sequences": K, "share_prompt": True}
         out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"], max_length=max_new,
@@ -420,6 +420,9 @@ def parse_args(argv=None):
                     help="validate with greedy decoding instead of the reference's sampling defaults (model_arch.py:82-88)")
     ap.add_argument("--num_beams", type=int, default=1,
                     help="eval mode: beam search with N beams (beam sampling unless --val_greedy); the dump keeps the best hypothesis per image")
+    ap.add_argument("--kv_cache_layout", default="dense", choices=["dense", "split"],
+                    help="KV cache of beam search (--num_beams > 1) in validation / eval: one full-length row per beam (dense), or one "
+                         "prompt row per clip plus one suffix row per beam (split)")
     ap.add_argument("--num_samples", type=int, default=1,
                     help="validation / eval: K sampled trajectories per clip from one prefill and one cached prompt per clip; adds best-of-K "
                          "minADE / minFDE to the record and keeps all K in the dump (not with --val_greedy or --num_beams > 1)")

@@ -564,7 +564,7 @@ class TrajPointLLMForCausalLM(nn.Module):
     def generate(self, input_ids=None, attention_mask=None, point_clouds=None, max_length=20, temperature=1.0, top_k=50,
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
                  eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
-                 decode_weight_dtype=None, share_prompt=False, **kwargs):
+                 decode_weight_dtype=None, share_prompt=False, kv_cache_layout=None, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -599,11 +599,34 @@ class TrajPointLLMForCausalLM(nn.Module):
         for its K samples (decode.Decoder(samples_per_prompt=K), csrc/shared.hip).  The draws of row r are those of the default path (same
         seed, same row numbering), but the attention sums in another order, so logits differ in their last bits and a sampled token can
         differ at a near-tie; hence the default stays False.  1 <= K <= 32 (K = 1 is the default path); not with num_beams > 1, a list of
-        ragged clouds or kv_cache_dtype="fp8"; decode_weight_dtype="fp8" and LoRA adapters work as in the default path."""
+        ragged clouds or kv_cache_dtype="fp8"; decode_weight_dtype="fp8" and LoRA adapters work as in the default path.
+
+        kv_cache_layout: None or "dense" = one cache row of S0 + max_length keys per beam (only the items' rows ever hold prompt keys);
+        "split" with num_beams > 1 = the prompt / suffix layout of share_prompt for beam search: one prompt cache row per item
+        [L, B, H, S0, hd] plus one suffix row of max_length keys per beam [L, B*num_beams, H, max_length, hd]
+        (decode.Decoder(split_cache=True)), and every step's attention reads an item's prompt K/V once for all its beams and the suffix
+        through the beam row table (egomi_attn_decode_shared_rows, csrc/shared.hip).  Same outputs, fields and shapes; the attention sums
+        in another order, so scores differ in their last bits.  Not with num_beams == 1 (see share_prompt), kv_cache_dtype="fp8", a list
+        of ragged clouds or more than 32 beams; decode_weight_dtype="fp8" and LoRA adapters work as in the dense layout."""
+        if kv_cache_layout not in (None, "dense", "split"):
+            raise ValueError(f"`kv_cache_layout` must be None, 'dense' or 'split', but is {kv_cache_layout!r}")
+        split = kv_cache_layout == "split"
+        if split:
+            if int(num_beams) == 1:
+                raise ValueError("kv_cache_layout='split' needs num_beams > 1; for independent samples of one prompt use share_prompt=True")
+            if kv_cache_dtype == "fp8":
+                raise NotImplementedError("kv_cache_layout='split' with kv_cache_dtype='fp8' is not built")
+            if isinstance(point_clouds, (list, tuple)):
+                raise NotImplementedError("kv_cache_layout='split' with a list of ragged clouds is not built")
+            if int(num_beams) > 32:
+                raise ValueError(f"kv_cache_layout='split' supports at most 32 beams, not {num_beams}")
+            if int(max_length) < 1:
+                raise ValueError("kv_cache_layout='split' needs max_length >= 1")
         share = bool(share_prompt) and int(num_return_sequences) > 1
         if share_prompt:
             if int(num_beams) > 1:
-                raise NotImplementedError("share_prompt=True with num_beams > 1 is not built (beam search already prefills each prompt once)")
+                raise NotImplementedError("share_prompt=True with num_beams > 1 is not built (beam search already prefills each prompt once; "
+                                          "kv_cache_layout='split' gives it the prompt / suffix cache)")
             if isinstance(point_clouds, (list, tuple)):
                 raise NotImplementedError("share_prompt=True with a list of ragged clouds is not built")
             if kv_cache_dtype == "fp8":
@@ -635,7 +658,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                 raise NotImplementedError("num_beams > 1 with a list of ragged clouds is not built")
             return self._generate_beam(ids, attention_mask, point_clouds, fps_start, int(max_length), nb, n_ret, float(length_penalty),
                                        early_stopping, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id,
-                                       seed, kwargs.get("use_graph", True), kv, wd)
+                                       seed, kwargs.get("use_graph", True), kv, wd, split)
         if n_ret > 1 and not share:                        # HF expands every input n times (generation/utils.py _expand_inputs_for_generation)
             if isinstance(point_clouds, (list, tuple)):
                 raise NotImplementedError("num_return_sequences > 1 with a list of ragged clouds is not built")
@@ -681,11 +704,12 @@ class TrajPointLLMForCausalLM(nn.Module):
         sc = sc[:stop].clone()                              # the decoder's buffers are static (and the decoder may be reused by the next call):
         return GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
 
-    def _decoder(self, B, max_len, nb=1, kv=None, wd=None, share=None):
+    def _decoder(self, B, max_len, nb=1, kv=None, wd=None, share=None, split=None):
         """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER
         prepare(): load_state_dict() / _apply() leave the engine unprepared (or replace it), and a decoder made before them holds stacked
         copies of the old weights and the old RoPE tables.  It also holds the KV dtype and the decode weight dtype: a bf16 and an fp8 decoder never
-        stand in for each other.  share = (K, Tmax): the shared-prompt decoder of K samples per prompt; the key holds the mode and K."""
+        stand in for each other.  share = (K, Tmax): the shared-prompt decoder of K samples per prompt; the key holds the mode and K.
+        split = Tmax: the beam decoder on the prompt / suffix cache layout; the key holds the layout and Tmax."""
         from ..decode import Decoder
         eng = self.engine
         if not eng.prepared:
@@ -693,12 +717,16 @@ class TrajPointLLMForCausalLM(nn.Module):
         key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv, wd, eng.lora_key())     # adapters: merged decode copies of their values
         if share is not None:
             key = key + ("share",) + tuple(share)
+        if split is not None:
+            key = key + ("split", split)
         cache = self.__dict__.setdefault("_decoders", {})
         reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
         dec = cache.get(key) if reuse else None
         if dec is None:
             if share is not None:
                 dec = Decoder(eng, B, max_len, kv_dtype=kv, weight_dtype=wd, samples_per_prompt=share[0], max_new_tokens=share[1])
+            elif split is not None:
+                dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv, weight_dtype=wd, split_cache=True, max_new_tokens=split)
             else:
                 dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv, weight_dtype=wd)
             if reuse:
@@ -708,7 +736,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         return dec
 
     def _generate_beam(self, ids, attention_mask, point_clouds, fps_start, T, nb, n_ret, length_penalty, early_stopping, do_sample, temperature,
-                       top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph, kv=None, wd=None):
+                       top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph, kv=None, wd=None, split=False):
         dev = self.engine.device
         B, S0 = ids.shape
         if isinstance(eos_token_id, str):
@@ -720,7 +748,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                 raise ValueError(f"`{name}` has to be a strictly positive float, but is {v}")
         if top_p is not None and not (0 < float(top_p) <= 1.0):
             raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
-        dec = self._decoder(B, S0 + T, nb, kv=kv, wd=wd)
+        dec = self._decoder(B, S0 + T, nb, kv=kv, wd=wd, split=T if split else None)
         chunk = 16
         if B > chunk:
             dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=chunk, nb=nb)

@@ -335,6 +335,19 @@ int egomi_attn_decode_rows(const void* q, int64_t ld_q, const void* kcache, cons
 int egomi_attn_decode_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask, int64_t ld_mask,
                              const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0,
                              int Tmax, int T_len, float scale, int dtype, egomi_stream_t stream);
+/* egomi_attn_decode_shared with the suffix read through a row table: beam search on the prompt / suffix cache layout.  K = beams per clip,
+ * logical row r = b * K + j; suffix key t of row r lives in physical suffix row sfx_row[r * ld_row + t] of ksuffix, vsuffix
+ * [n_phys, H, Tmax, hd] (a beam's suffix is the path through its ancestors' rows; egomi_beam_update keeps the table).  An entry outside
+ * [0, n_phys) is a masked key: its address is clamped and its score selected away, never dereferenced (the convention of
+ * egomi_attn_decode_rows_fp8).  sfx_row [B*K, ld_row >= T_len] int32 (T_len = 0: may be NULL).  Every other argument, the result, the
+ * layouts, dtypes and head dims are those of egomi_attn_decode_shared, and so is the prompt phase; each query's suffix keys are split
+ * into contiguous slices over the workgroup's idle lane groups and merged in slice order (csrc/shared.hip).  Every sum has a fixed order
+ * given by (K, S0, T_len): no atomics, replays are bit-equal, and permuting the beams of a clip (queries and table rows together)
+ * permutes the output rows bit for bit. */
+int egomi_attn_decode_shared_rows(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask, int64_t ld_mask,
+                                  const void* ksuffix, const void* vsuffix, const int32_t* sfx_row, int64_t ld_row, int n_phys, void* out,
+                                  int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0, int Tmax, int T_len, float scale, int dtype,
+                                  egomi_stream_t stream);
 
 /* FP8 (OCP e4m3fn) KV cache (csrc/kv8.hip; attention: csrc/attn_decode.hip): codes uint8 [B, H, Smax, hd] per layer (the bf16 cache's layout), scales fp32 [B, H, Smax]
  * per layer; hd in {32, 64, 128} (EGOMI_E_UNSUPPORTED otherwise); codes 8-B (attention: 16-B) aligned, scales 4-B aligned.  Per (row, head, position)

@@ -3,7 +3,9 @@
 max_traj_token=160), as tools/debug/validation_throughput.py), 152 new tokens, num_beams 4; against greedy at B=8 and greedy at B=32
 (the same 32 rows as 8 x 4 beams, but 32 unshared prompts).  Each loop is one hipGraph; the time is the replay of all 152 steps.
 Prints one JSON line: ms per step and tokens/s of each, and the step's modelled bytes (weights + K/V read; the beam step reads each
-prompt's K/V once per item).  GPU box only:  python tools/bench_beam.py [--layers N] [--steps 152]"""
+prompt's K/V once per item).  --kv_cache_layout split: the beam decoder on the prompt / suffix cache (Decoder(split_cache=True));
+both: the dense and the split decoder side by side, their loops timed alternately (--reps rounds), with each arm's cache bytes.
+GPU box only:  python tools/bench_beam.py [--layers N] [--steps 152] [--kv_cache_layout dense|split|both]"""
 import argparse, json, os, sys, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -51,12 +53,24 @@ def timed(fn, reps=2):
     return min(ms)
 
 
+def timed_once(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=None)
     ap.add_argument("--steps", type=int, default=152)
     ap.add_argument("--beams", type=int, default=4)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--kv_cache_layout", default="dense", choices=["dense", "split", "both"])
+    ap.add_argument("--reps", type=int, default=2, help="timed replays per arm (both: alternating rounds)")
+    ap.add_argument("--no_greedy", action="store_true", help="skip the greedy arms")
     a = ap.parse_args()
     m, dims = model_7b(a.layers)
     eng, lm = m.engine, dims.lm
@@ -67,19 +81,35 @@ def main():
     st = torch.zeros(B, dtype=torch.int32, device="cuda")
     out = {"prompt_len": Lp, "new_tokens": T, "batch": B, "num_beams": nb, "layers": lm.num_hidden_layers}
 
-    dec = Decoder(eng, B * nb, Lp + T, num_beams=nb)
-    dec.prefill(ids, mask, pcs, st, T, nb=nb)
-    lg0 = dec.lg.clone()
+    arms = {}
+    for layout in (("dense", "split") if a.kv_cache_layout == "both" else (a.kv_cache_layout,)):
+        dec = Decoder(eng, B * nb, Lp + T, num_beams=nb, **(dict(split_cache=True, max_new_tokens=T) if layout == "split" else {}))
+        dec.prefill(ids, mask, pcs, st, T, nb=nb)
+        lg0 = dec.lg.clone()
 
-    def beam():
-        dec.lg.copy_(lg0)
-        dec.pos = Lp
-        return dec.beam(T, length_penalty=1.0, eos=None, pad=dims.tok.pad)
-    ms_beam = timed(beam)
-    out["beam"] = {"ms_per_step": round(ms_beam / T, 3), "tokens_per_s": round(B * nb * T / (ms_beam * 1e-3), 1), "ms_total": round(ms_beam, 1),
-                   "iterations": int(dec.ctl[1])}
-    del dec
-    for Bg in (B, B * nb):
+        def beam(dec=dec, lg0=lg0):
+            dec.lg.copy_(lg0)
+            dec.pos = Lp
+            return dec.beam(T, length_penalty=1.0, eos=None, pad=dims.tok.pad)
+        caches = (dec.kp, dec.vp, dec.ksfx, dec.vsfx) if dec.kc is None else (dec.kc, dec.vc)
+        arms[layout] = (dec, beam, sum(c.numel() * c.element_size() for c in caches))
+    for _, beam, _ in arms.values():                                      # capture + first replay of every arm
+        beam()
+    torch.cuda.synchronize()
+    runs = {k: [] for k in arms}
+    for _ in range(a.reps):                                               # the arms alternate: one replay each per round
+        for k, (_, beam, _) in arms.items():
+            runs[k].append(timed_once(beam))
+    for k, (dec, _, cache_bytes) in arms.items():
+        ms_beam = min(runs[k])
+        name = "beam" if k == a.kv_cache_layout or (a.kv_cache_layout == "both" and k == "dense") else "beam_" + k
+        out[name] = {"layout": k, "ms_per_step": round(ms_beam / T, 3), "tokens_per_s": round(B * nb * T / (ms_beam * 1e-3), 1),
+                     "ms_total": round(ms_beam, 1), "ms_per_step_runs": [round(x / T, 3) for x in runs[k]], "iterations": int(dec.ctl[1]),
+                     "cache_GB": round(cache_bytes / 1e9, 3)}
+    if "split" in arms and "dense" in arms:
+        out["split_over_dense"] = round(out["beam_split"]["ms_per_step"] / out["beam"]["ms_per_step"], 4)
+    del arms, dec, beam
+    for Bg in (() if a.no_greedy else (B, B * nb)):
         rep = Bg // B
         d2 = Decoder(eng, Bg, Lp + T)
         d2.prefill(ids.repeat(rep, 1), mask.repeat(rep, 1), pcs.repeat(rep, 1, 1), st.repeat(rep), T)
@@ -103,8 +133,11 @@ def main():
         "beam": round((p_llm + B * Lp * row_kv + B * nb * (mid - Lp) * row_kv) / 1e9, 3),
         "greedy_b%d" % B: round((p_llm + B * mid * row_kv) / 1e9, 3),
         "greedy_b%d" % (B * nb): round((p_llm + B * nb * mid * row_kv) / 1e9, 3)}
-    out["beam_over_greedy_b%d" % B] = round(out["beam"]["ms_per_step"] / out[f"greedy_b{B}"]["ms_per_step"], 3)
-    out["beam_over_greedy_b%d" % (B * nb)] = round(out["beam"]["ms_per_step"] / out[f"greedy_b{B * nb}"]["ms_per_step"], 3)
+    if not a.no_greedy:
+        for name in ("beam", "beam_split"):
+            if name in out:
+                out[name + "_over_greedy_b%d" % B] = round(out[name]["ms_per_step"] / out[f"greedy_b{B}"]["ms_per_step"], 3)
+                out[name + "_over_greedy_b%d" % (B * nb)] = round(out[name]["ms_per_step"] / out[f"greedy_b{B * nb}"]["ms_per_step"], 3)
     print(json.dumps(out))
 
 
