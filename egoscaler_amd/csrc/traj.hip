@@ -5,7 +5,8 @@
 //   models/pointllm/utils/utils.py:47-104 str_to_float (rt2, 6-DoF): split on <tsep>, first run of six
 //       <p*> tokens per segment, unmatched segments repeat the previous step
 //   models/pointllm/dataset.py:16-19,150-194 sequence layout  <ts> (p*6 <tsep>)*T <te> eos pad...
-//   models/utils/metrics.py:7-55          ADE / FDE (documented [T,D] form); best-of-K minima of them (minADE_K / minFDE_K)
+//   models/utils/metrics.py:7-55          ADE / FDE (documented [T,D] form); best-of-K minima of them (minADE_K / minFDE_K); the medoid of
+//       K samples under the same displacement (metrics.py:38-55 between two samples instead of a sample and the ground truth)
 // The bin edges are computed once on the host in float64 exactly as numpy.linspace does and passed in.
 #include "common.h"
 #include <math.h>
@@ -134,6 +135,63 @@ __global__ __launch_bounds__(64) void traj_metrics_min_kernel(const float* gen, 
     best[b] = bi;
 }
 
+// medoid of K: gen [B, K, Tmax, D], n_gen [B, K] or NULL (= Tmax); sample j is valid when n_gen > 0 (traj_metrics_min_kernel's rule).
+// d(j, i) = mean over t < max(n_j, n_i) of ||g_j[min(t, n_j - 1)] - g_i[min(t, n_i - 1)]||_2 over all D dims: each sample padded with its
+// own last step, as traj_metrics_kernel pads (bit-symmetric in j, i).  cost[b, j] = mean of d(j, i) over the valid i != j, float64, summed in
+// index order; one valid sample: 0; invalid j: NaN.  pick[b] = arg-min of cost over the valid samples (lowest index on ties), none: -1.
+// One workgroup per clip, one thread per sample j.
+#define MED_THREADS 256
+#define MED_MAXK 1024
+__global__ __launch_bounds__(MED_THREADS) void traj_medoid_kernel(const float* gen, const int32_t* n_gen, int K, int Tmax, int D, double* cost,
+                                                                  int32_t* pick) {
+    __shared__ double cs[MED_MAXK];
+    const int b = blockIdx.x;
+    const float* gb = gen + (long long)b * K * Tmax * D;
+    for (int j = threadIdx.x; j < K; j += MED_THREADS) {
+        int nj = n_gen ? n_gen[(long long)b * K + j] : Tmax;
+        nj = nj > Tmax ? Tmax : nj;
+        double c = NAN;
+        if (nj > 0) {
+            const float* gj = gb + (long long)j * Tmax * D;
+            double tot = 0.0;
+            int others = 0;
+            for (int i = 0; i < K; ++i) {
+                int ni = n_gen ? n_gen[(long long)b * K + i] : Tmax;
+                ni = ni > Tmax ? Tmax : ni;
+                if (i == j || ni <= 0) continue;
+                const float* gi = gb + (long long)i * Tmax * D;
+                const int n = nj > ni ? nj : ni;
+                double acc = 0.0;
+                for (int t = 0; t < n; ++t) {
+                    const int tj = t < nj ? t : nj - 1, ti = t < ni ? t : ni - 1;
+                    double s = 0.0;
+                    for (int d = 0; d < D; ++d) {
+                        const double df = (double)gj[(long long)tj * D + d] - (double)gi[(long long)ti * D + d];
+                        s += df * df;
+                    }
+                    acc += sqrt(s);
+                }
+                tot += acc / n;
+                ++others;
+            }
+            c = others ? tot / others : 0.0;
+        }
+        cs[j] = c;
+        cost[(long long)b * K + j] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int bi = -1;
+        double bc = 0.0;
+        for (int j = 0; j < K; ++j) {
+            const double c = cs[j];
+            if (c != c) continue;                                            // invalid sample
+            if (bi < 0 || c < bc) { bc = c; bi = j; }
+        }
+        pick[b] = bi;
+    }
+}
+
 extern "C" int egomi_traj_tokenize(const float* traj, const int32_t* steps, int B, int Tmax, const double* bins, int num_bins, int64_t p0,
                                    int64_t ts, int64_t tsep, int64_t te, int64_t eos, int64_t pad, int L, int64_t* ids, uint8_t* mask,
                                    int32_t* err, egomi_stream_t stream) {
@@ -165,5 +223,14 @@ extern "C" int egomi_traj_metrics_min(const float* gen, const int32_t* n_gen, co
     if (B <= 0 || K <= 0 || Tmax <= 0 || D <= 0) return EGOMI_E_SHAPE;
     EGOMI_LAUNCH(traj_metrics_min_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, gen, n_gen, gt, n_gt, B, K, Tmax, D, min_ade,
                  min_fde, best);
+    return egomi_launch_status();
+}
+
+extern "C" int egomi_traj_medoid(const float* gen, const int32_t* n_gen, int B, int K, int Tmax, int D, double* cost, int32_t* pick,
+                                 egomi_stream_t stream) {
+    if (!gen || !cost || !pick) return EGOMI_E_BADARG;
+    if (B <= 0 || K <= 0 || Tmax <= 0 || D <= 0) return EGOMI_E_SHAPE;
+    if (K > MED_MAXK) return EGOMI_E_UNSUPPORTED;
+    EGOMI_LAUNCH(traj_medoid_kernel, dim3(B), dim3(MED_THREADS), 0, (hipStream_t)stream, gen, n_gen, K, Tmax, D, cost, pick);
     return egomi_launch_status();
 }

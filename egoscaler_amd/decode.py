@@ -99,6 +99,26 @@ def sample_rows(logits, scores, seq, pos, rep_from, ids, done, repetition_penalt
          c_i64(0 if pad is None else int(pad)), c_i(dt(logits.dtype)), S())
 
 
+def token_logprob(logits, tok, eos, live, tok_lp, col, sum_lp, n_tok):
+    """The log-prob of this step's chosen token under the RAW logits, per row (include/egomi.h egomi_token_logprob): tok_lp[:, col], and the
+    running sum_lp / n_tok; live (int32 [R] or None) stops a row's count after its eos."""
+    R, V = logits.shape
+    call("egomi_token_logprob", P(logits), c_i64(logits.stride(0)), c_i(R), c_i(V), P(tok), c_i64(-1 if eos is None else int(eos)), P(live),
+         P(tok_lp), c_i64(tok_lp.stride(0)), c_i(col), P(sum_lp), P(n_tok), c_i(dt(logits.dtype)), S())
+
+
+def seq_rank(sum_lp, n_tok, B, K, length_penalty=1.0):
+    """Per clip, the K rows b * K + j by descending sum_lp / n_tok ** length_penalty (include/egomi.h egomi_seq_rank):
+    -> (score fp32 [B, K], order int32 [B, K])."""
+    sum_lp, n_tok = sum_lp.to(torch.float32).contiguous(), n_tok.to(torch.int32).contiguous()
+    if sum_lp.numel() != B * K or n_tok.numel() != B * K:
+        raise ValueError(f"sum_lp / n_tok must hold B * K = {B * K} rows")
+    score = torch.empty(B, K, dtype=torch.float32, device=sum_lp.device)
+    order = torch.empty(B, K, dtype=torch.int32, device=sum_lp.device)
+    call("egomi_seq_rank", P(sum_lp), P(n_tok), c_i(B), c_i(K), c_f(float(length_penalty)), P(score), P(order), S())
+    return score, order
+
+
 def beam_rows(logits, lg_div, R, nb, scores, seq, pos, repetition_penalty, temperature, top_k, top_p, min_keep, do_sample, rng, draw, run_score,
               cand_key, cand_score, cand_tok, ctl):
     """One beam step's row pass (include/egomi.h egomi_beam_rows): processed log-probs (HF's `.scores`) + each row's K best candidates."""
@@ -232,6 +252,7 @@ class Decoder:
         self.rng = z(2, dtype=torch.int64)
         self.done_buf = z(B, dtype=torch.int32)
         self._graphs, self._scores = {}, {}
+        self.lp_tok = self.lp_sum = self.lp_n = self.lp_live = None      # sample() / greedy() with logprobs=True: made on first use (_lp_buffers)
         self.kv_row = None                                  # beam mode: [B, Smax] int32, physical cache row of every key of every logical row
         if self.nb > 1:
             self._beam_buffers()
@@ -273,6 +294,19 @@ class Decoder:
             self.fused["qkv"] = 0 if self.split else ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
             self.fused["o"] = ops.mm_slabs(self.ao, w["model.layers.0.self_attn.o_proj.weight"], self.x_mid, self.gws, count_only=True)
             self.fused["down"] = ops.mm_slabs(self.act, w["model.layers.0.mlp.down_proj.weight"], self.x, self.gws, count_only=True)
+
+    def _lp_buffers(self):
+        """Static buffers of sample(logprobs=True) / greedy(logprobs=True), made on first use: lp_tok [B, max_len] (column t = step t),
+        lp_sum [B], lp_n [B], lp_live [B]."""
+        if self.lp_tok is None:
+            dev = self.eng.device
+            self.lp_tok = torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev)
+            self.lp_sum = torch.zeros(self.B, dtype=torch.float32, device=dev)
+            self.lp_n = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.lp_live = torch.ones(self.B, dtype=torch.int32, device=dev)
+        self.lp_sum.zero_()
+        self.lp_n.zero_()
+        self.lp_live.fill_(1)
 
     def _merge_lora(self):
         """LoRA: the decode steps multiply merged copies W + s B A of the adapted projections (one fp32 sum, rounded once; csrc/lora.hip);
@@ -489,11 +523,14 @@ class Decoder:
         ops.mm(self.hn, w["lm_head.weight"], out=self.lg)
 
     def sample(self, T_new, do_sample=True, temperature=1.0, top_k=50, top_p=0.95, repetition_penalty=1.0, eos=None, pad=None, seed=None,
-               use_graph=True):
+               use_graph=True, logprobs=False):
         """After prefill(): T_new steps of HF generate's token loop (model_arch.py:82-108 -> GenerationMixin: logits processors, warpers,
         multinomial / arg-max, eos bookkeeping), every step one egomi_sample_rows launch + one cached decode step, all of them captured
         into ONE hipGraph (the draw counter and `pos` are launch constants, seed and done flags live in device memory).
-        Returns (sequences [B, S0+T_new], processed scores fp32 [T_new, B, V]); rows that emitted `eos` continue with `pad`."""
+        Returns (sequences [B, S0+T_new], processed scores fp32 [T_new, B, V]); rows that emitted `eos` continue with `pad`.
+        logprobs=True: every step also runs one egomi_token_logprob launch on the raw logits, after the token kernel: self.lp_tok[:, t] is
+        the chosen token's log-prob (0 once the row has finished), self.lp_sum / self.lp_n the row's sum and token count (its eos counted,
+        the pads not).  A graph of its own (the flag is part of the key); with False the loop has the launches it had."""
         S0, dev = self.pos, self.eng.device
         V = self.lg.shape[1]
         sc_buf = self._scores.get(T_new)
@@ -504,12 +541,17 @@ class Decoder:
         self.rng.copy_(torch.tensor([int(seed), 0], dtype=torch.int64))
         self.done_buf.zero_()
         self.done = self.done_buf if eos is not None else None
+        if logprobs:
+            self._lp_buffers()
+        lp_live = self.lp_live if logprobs and eos is not None else None
         kw = dict(repetition_penalty=float(repetition_penalty or 1.0), temperature=float(temperature or 1.0), top_k=int(top_k or 0),
                   top_p=float(1.0 if top_p is None else top_p), do_sample=bool(do_sample), rng=self.rng, eos=eos, pad=pad)
 
         def steps():
             for t in range(T_new):
                 sample_rows(self.lg, sc_buf[t], self.seq, S0 + t, 0, self.tok.view(-1), self.done, draw=t, **kw)
+                if logprobs:
+                    token_logprob(self.lg, self.tok.view(-1), eos, lp_live, self.lp_tok, t, self.lp_sum, self.lp_n)
                 if t + 1 < T_new:
                     self.step(S0 + t)
         if not use_graph:
@@ -518,6 +560,8 @@ class Decoder:
             # the captured loop depends on the prompt length, the number of steps and the sampling parameters only (every buffer it touches is
             # static, the seed and the eos flags are device memory): a later call with the same key replays it
             key = (S0, T_new, kw["repetition_penalty"], kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], eos, pad)
+            if logprobs:
+                key = key + ("logprobs",)
             g = self._graphs.get(key)
             if g is None:
                 g = torch.cuda.CUDAGraph()
@@ -529,15 +573,20 @@ class Decoder:
         self.pos = S0 + T_new
         return self.seq, sc_buf
 
-    def greedy(self, T_new, use_graph=True, keep_scores=True):
-        """After prefill(): T_new greedy tokens.  Returns (sequences [B,S0+T], scores list or None)."""
+    def greedy(self, T_new, use_graph=True, keep_scores=True, logprobs=False):
+        """After prefill(): T_new greedy tokens.  Returns (sequences [B,S0+T], scores list or None).  logprobs=True: one egomi_token_logprob
+        launch per step after the arg-max, into self.lp_tok / lp_sum / lp_n as in sample() (no eos here: every row counts every step)."""
         S0 = self.pos
         scores = [] if keep_scores else None
+        if logprobs:
+            self._lp_buffers()
         if not use_graph:
             for t in range(T_new):
                 if keep_scores:
                     scores.append(self.lg.float().clone())
                 argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
+                if logprobs:
+                    token_logprob(self.lg, self.tok.view(-1), None, None, self.lp_tok, t, self.lp_sum, self.lp_n)
                 if t + 1 < T_new:
                     self.step(S0 + t)
             self.pos = S0 + T_new
@@ -549,6 +598,8 @@ class Decoder:
                 if keep_scores:
                     ops.cast(self.lg, torch.float32, out=sc_buf[t])
                 argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
+                if logprobs:
+                    token_logprob(self.lg, self.tok.view(-1), None, None, self.lp_tok, t, self.lp_sum, self.lp_n)
                 if t + 1 < T_new:
                     self.step(S0 + t)
         g.replay()

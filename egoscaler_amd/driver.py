@@ -141,7 +141,7 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
 
 
 @torch.no_grad()
-def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None):
+def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None):
     """Generation + metrics on the rank's shard (train.py:207-264, evaluate.py:104-154): prompts up to the first <tsep>,
     `generate` of the remaining positions (sampling with the reference's defaults top_k 50 / top_p 0.95 / T 1.0 unless
     args.val_sample is False -> greedy), cut at eos, de-tokenise, de-normalise (dataset.denorm), pad with the last step,
@@ -157,16 +157,28 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     (generate(num_return_sequences=K, share_prompt=True)); sampling only, not with num_beams > 1.  'ADE' / 'FDE' / 'ADE_as_called' / 'GD' /
     'n' are those of sample 0 of every clip, computed as with K = 1; the record gains 'minADE' / 'minFDE' (best-of-K, T.metrics_best_of;
     means over the 'n_min' clips with at least one parsed sample) and 'K', and the dump holds the K trajectories per image id (None for
-    an unparsed one).  K = 1 is the single-draw path unchanged."""
+    an unparsed one).  K = 1 is the single-draw path unchanged.
+
+    select (default: args.select, else "none") with K > 1: which of the K a user without the ground truth would keep, chosen on the device.
+    "logprob" = the sample the model finds most probable (generate(output_logprobs=True).rank[:, 0]: highest mean token log-prob under the
+    raw logits); "medoid" = the most central sample (T.select_medoid: smallest mean ADE to the other parsed samples).  The record gains
+    'ADE_sel' / 'FDE_sel' (T.metrics_selected; means over the 'n_sel' clips whose pick parsed) and 'select'; the dump gains one key,
+    "selected": {image id: picked sample index}.  "none" leaves the record and the dump as they are."""
     dims = model.dims
     K = int(num_samples if num_samples is not None else (getattr(args, "num_samples", 1) or 1))
     if K < 1:
         raise ValueError(f"num_samples has to be a strictly positive integer, but is {K}")
     if K > 1 and (num_beams != 1 or not bool(getattr(args, "val_sample", True))):
         raise ValueError("num_samples > 1 draws samples: it cannot be combined with --val_greedy or --num_beams > 1")
+    select = str(select if select is not None else (getattr(args, "select", "none") or "none"))
+    if select not in ("none", "logprob", "medoid"):
+        raise ValueError(f"select must be none, logprob or medoid, not {select!r}")
+    if select != "none" and K < 2:
+        raise ValueError("--select chooses among samples: it needs --num_samples K > 1")
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
     sample = bool(getattr(args, "val_sample", True))
+    sel_sums, picked = np.zeros(3), {}                   # ADE_sel, FDE_sel, n_sel
     per = micro_batch_per_rank(args.bs, 1, world)
     model.eval()
     sums = np.zeros(8)                                   # ADE, FDE, ADE_as_called, GD, n; best-of-K: minADE, minFDE, n_min
@@ -188,6 +200,8 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
         beam = {} if num_beams == 1 else {"num_beams": num_beams, "kv_cache_layout": getattr(args, "kv_cache_layout", None)}
         if K > 1:
             beam = {"num_return_sequences": K, "share_prompt": True}
+            if select == "logprob":
+                beam["output_logprobs"] = True
         out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"], max_length=max_new,
                              do_sample=sample, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device),
                              kv_cache_dtype=getattr(args, "kv_cache_dtype", None),
@@ -229,10 +243,19 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
                 if best[j] >= 0:
                     sums[5:8] += [made[j], mfde[j], 1.0]
                 dump[int(ids_h[j])] = [gen[j * K + i].tolist() if n_h[j * K + i] > 0 else None for i in range(K)]
+            if select != "none":
+                gen_k, n_k = gen_d.view(len(idx), K, Tn, -1), (n > 0).to(torch.int32).view(len(idx), K) * Tn
+                pick = out.rank[:, 0].contiguous() if select == "logprob" else T.select_medoid(gen_k, n_k)[0]
+                sade, sfde = T.metrics_selected(gen_k, n_k, gt, None, pick)
+                sade, sfde, pick = sade.cpu().numpy(), sfde.cpu().numpy(), pick.cpu().numpy()
+                for j in range(len(idx)):
+                    picked[int(ids_h[j])] = int(pick[j])
+                    if not np.isnan(sade[j]):
+                        sel_sums += [sade[j], sfde[j], 1.0]
     if world > 1:
-        t = torch.from_numpy(sums).to(device)
+        t = torch.from_numpy(np.concatenate([sums, sel_sums])).to(device)
         dist.all_reduce(t)
-        sums = t.cpu().numpy()
+        sums, sel_sums = t.cpu().numpy()[:8], t.cpu().numpy()[8:]
     model.train()
     k = max(sums[4], 1.0)
     nan = float("nan")
@@ -241,6 +264,10 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     if K > 1:
         rec.update({"minADE": float(sums[5] / sums[7]) if sums[7] else nan, "minFDE": float(sums[6] / sums[7]) if sums[7] else nan,
                     "n_min": int(sums[7]), "K": K})
+    if select != "none":
+        rec.update({"ADE_sel": float(sel_sums[0] / sel_sums[2]) if sel_sums[2] else nan,
+                    "FDE_sel": float(sel_sums[1] / sel_sums[2]) if sel_sums[2] else nan, "n_sel": int(sel_sums[2]), "select": select})
+        dump["selected"] = picked
     return rec, dump
 
 
@@ -376,12 +403,14 @@ def evaluate(args, model, data, split="test", device="cuda"):
     if norm is not None and norm.mode == "standard" and norm.mean is None:
         norm.load(args.checkpoint_dir)
     metrics, dump = run_validation(model, data, args, device, num_beams=int(getattr(args, "num_beams", 1)),
-                                   num_samples=int(getattr(args, "num_samples", 1) or 1))
+                                   num_samples=int(getattr(args, "num_samples", 1) or 1), select=getattr(args, "select", "none"))
     rank, world = _rank_world()
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, dump)
-        dump = {k: v for p in parts for k, v in p.items()}
+        dump = {k: v for p in parts for k, v in p.items() if k != "selected"}
+        if any("selected" in p for p in parts):             # --select: the ranks' picks, merged like the trajectories
+            dump["selected"] = {k: v for p in parts for k, v in p.get("selected", {}).items()}
     if rank == 0:
         with open(os.path.join(args.checkpoint_dir, f"{split}_gen_trajs.json"), "w") as f:
             json.dump(dump, f)
@@ -426,6 +455,10 @@ def parse_args(argv=None):
     ap.add_argument("--num_samples", type=int, default=1,
                     help="validation / eval: K sampled trajectories per clip from one prefill and one cached prompt per clip; adds best-of-K "
                          "minADE / minFDE to the record and keeps all K in the dump (not with --val_greedy or --num_beams > 1)")
+    ap.add_argument("--select", default="none", choices=["none", "logprob", "medoid"],
+                    help="validation / eval with --num_samples K > 1: also pick one of the K without the ground truth, on the device (logprob: "
+                         "highest mean token log-prob under the raw logits; medoid: smallest mean ADE to the other samples); adds ADE_sel / "
+                         "FDE_sel to the record and the picked index per image id to the dump")
     ap.add_argument("--kv_cache_dtype", default="auto", choices=["auto", "fp8"],
                     help="KV cache of every generate() call in validation / eval: the model's dtype (auto) or e4m3fn codes with per-(token, head) scales")
     ap.add_argument("--decode_weight_dtype", default="auto", choices=["auto", "fp8"],

@@ -142,6 +142,12 @@ class CausalLMOutput:
 class GenerateOutput:
     sequences: torch.Tensor
     scores: Tuple[torch.Tensor, ...]
+    # generate(output_logprobs=True) only (None otherwise)
+    token_logprobs: Optional[torch.Tensor] = None       # fp32 [rows, T']: log-prob of every generated token under the raw logits, 0 after a row finished
+    sequences_logprobs: Optional[torch.Tensor] = None   # fp32 [rows]: their sum per row
+    sequences_lengths: Optional[torch.Tensor] = None    # int32 [rows]: tokens counted (the eos included, the pads after it not)
+    sample_scores: Optional[torch.Tensor] = None        # num_return_sequences = K > 1: fp32 [B, K], sum / length ** rank_length_penalty
+    rank: Optional[torch.Tensor] = None                 # int32 [B, K]: the clip's sample indices by descending sample_scores
 
 
 @dataclass
@@ -564,7 +570,7 @@ class TrajPointLLMForCausalLM(nn.Module):
     def generate(self, input_ids=None, attention_mask=None, point_clouds=None, max_length=20, temperature=1.0, top_k=50,
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
                  eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
-                 decode_weight_dtype=None, share_prompt=False, kv_cache_layout=None, **kwargs):
+                 decode_weight_dtype=None, share_prompt=False, kv_cache_layout=None, output_logprobs=False, rank_length_penalty=1.0, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -607,7 +613,20 @@ class TrajPointLLMForCausalLM(nn.Module):
         (decode.Decoder(split_cache=True)), and every step's attention reads an item's prompt K/V once for all its beams and the suffix
         through the beam row table (egomi_attn_decode_shared_rows, csrc/shared.hip).  Same outputs, fields and shapes; the attention sums
         in another order, so scores differ in their last bits.  Not with num_beams == 1 (see share_prompt), kv_cache_dtype="fp8", a list
-        of ragged clouds or more than 32 beams; decode_weight_dtype="fp8" and LoRA adapters work as in the dense layout."""
+        of ragged clouds or more than 32 beams; decode_weight_dtype="fp8" and LoRA adapters work as in the dense layout.
+
+        output_logprobs=True (num_beams == 1; HF: output_logits=True + compute_transition_scores): the output also carries the log-probability
+        of every generated token under the RAW model distribution -- not under the processed `scores`, where top-k / top-p leave -inf holes --
+        computed on the device inside the token loop (one egomi_token_logprob launch per step, csrc/logprob.hip; no raw logits are kept):
+        token_logprobs fp32 [rows, T'] (T' = the columns `sequences` keeps; 0 after a row's eos), sequences_logprobs fp32 [rows] (their sum),
+        sequences_lengths int32 [rows] (the eos counted, the pads not); with num_return_sequences = K > 1 also sample_scores fp32 [B, K] =
+        sum / length ** rank_length_penalty (HF's beam convention: 1.0 = mean log-prob, 0.0 = the sum) and rank int32 [B, K], the clip's
+        sample indices by descending score (egomi_seq_rank): rows[b * K + rank[b, 0]] is the sample the model finds most probable.  Every
+        other field, the row order and the drawn tokens are those of the call without it; no row is dropped.  Works in every non-beam mode;
+        num_beams > 1 raises ValueError (beams return sequences_scores)."""
+        if output_logprobs and int(num_beams) > 1:
+            raise ValueError("output_logprobs=True is for num_beams == 1; beam search returns `sequences_scores` (length-penalised sums of "
+                             "the beams' log-probs)")
         if kv_cache_layout not in (None, "dense", "split"):
             raise ValueError(f"`kv_cache_layout` must be None, 'dense' or 'split', but is {kv_cache_layout!r}")
         split = kv_cache_layout == "split"
@@ -695,14 +714,22 @@ class TrajPointLLMForCausalLM(nn.Module):
         if not do_sample:                                  # HF applies the warpers (temperature / top-k / top-p) in sampling mode only
             temperature, top_k, top_p = 1.0, 0, 1.0
         seq, sc = dec.sample(T, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                             eos=eos_token_id, pad=pad_token_id, seed=seed, use_graph=kwargs.get("use_graph", True))
+                             eos=eos_token_id, pad=pad_token_id, seed=seed, use_graph=kwargs.get("use_graph", True),
+                             logprobs=bool(output_logprobs))
         stop = T
         if eos_token_id is not None and T > 0:             # HF leaves the loop after the step at which the last unfinished row emitted eos
             hit = seq[:, S0:] == eos_token_id
             first = torch.where(hit.any(1), hit.int().argmax(1), torch.full((B,), T - 1, device=dev))
             stop = int(first.max()) + 1
         sc = sc[:stop].clone()                              # the decoder's buffers are static (and the decoder may be reused by the next call):
-        return GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
+        out = GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
+        if output_logprobs:
+            out.token_logprobs = dec.lp_tok[:, :stop].clone()
+            out.sequences_logprobs, out.sequences_lengths = dec.lp_sum.clone(), dec.lp_n.clone()
+            if n_ret > 1:
+                from ..decode import seq_rank
+                out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B // n_ret, n_ret, float(rank_length_penalty))
+        return out
 
     def _decoder(self, B, max_len, nb=1, kv=None, wd=None, share=None, split=None):
         """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER

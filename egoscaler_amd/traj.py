@@ -98,6 +98,40 @@ def metrics_best_of(gen, n_gen, gt, n_gt=None):
     return min_ade, min_fde, best
 
 
+def select_medoid(gen, n_gen=None):
+    """The most central of K samples per clip, on the device (egomi_traj_medoid): gen [B, K, T, D], n_gen [B, K] or None ->
+    (pick [B] int32, cost [B, K] float64).  cost[b, j] = mean over the other parsed samples i of the mean displacement between samples j
+    and i (each padded with its own last step, as metrics_batch pads); a sample with n_gen <= 0 takes no part (cost NaN); pick = arg-min
+    of cost (lowest index on ties), -1 when no sample is left; a single parsed sample is picked at cost 0.  Needs neither the ground
+    truth nor model scores, so it also serves trajectories that did not come from generate()."""
+    gen = gen.to(torch.float32).contiguous()
+    if gen.dim() != 4 or gen.shape[1] < 1:
+        raise ValueError("gen must be [B,K,T,D] with K >= 1")
+    B, K, Tn, D = gen.shape
+    if n_gen is not None and tuple(n_gen.shape) != (B, K):
+        raise ValueError("n_gen must be [B,K]")
+    dev = gen.device
+    cost = torch.empty(B, K, dtype=torch.float64, device=dev)
+    pick = torch.empty(B, dtype=torch.int32, device=dev)
+    ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
+    call("egomi_traj_medoid", P(gen), P(ng), c_i(B), c_i(K), c_i(Tn), c_i(D), P(cost), P(pick), S())
+    return pick, cost
+
+
+def metrics_selected(gen, n_gen, gt, n_gt, pick):
+    """ADE / FDE (float64 [B]) of the sample pick[b] of every clip: metrics_batch on the gathered rows gen[b, pick[b]] (bit-equal to it);
+    pick[b] < 0 (nothing to pick) gives NaN.  gen [B, K, T, D], n_gen [B, K] or None, gt [B, T, D], n_gt [B] or None, pick [B]."""
+    B, K = gen.shape[:2]
+    pick = pick.to(gen.device).long()
+    ok = pick >= 0
+    idx = torch.arange(B, device=gen.device), pick.clamp(min=0)
+    g = gen[idx]
+    ng = None if n_gen is None else n_gen[idx]
+    ade, fde = metrics_batch(g, ng, gt, n_gt)
+    nan = torch.full_like(ade, float("nan"))
+    return torch.where(ok, ade, nan), torch.where(ok, fde, nan)
+
+
 # ------------------------------------------------------------------------------------------ host
 def discretize_action(action_vector, num_bins=256):
     """utils/utils.py:13-16."""

@@ -292,6 +292,28 @@ int egomi_sample_rows(const void* logits, int64_t ld, int B, int V, float* score
                       int pos, int rep_from, int64_t* ids, int* done, float repetition_penalty, float temperature, int top_k,
                       float top_p, int do_sample, const uint64_t* rng, int draw, int64_t eos_id, int64_t pad_id, int dtype,
                       egomi_stream_t stream);
+/* token_logprob / seq_rank: which of K sampled sequences the model itself finds most probable (csrc/logprob.hip).  Replaces
+ * transformers/generation/utils.py compute_transition_scores on generate(output_logits=True): log_softmax of the RAW logits of every
+ * step, gathered at the chosen token and summed per sequence -- without keeping [T, rows, V] raw logits or leaving the captured loop.
+ *   token_logprob: one launch per decode step, after sample_rows / argmax_rows wrote tok; reads the logits they read (bf16 or fp32 [R, V],
+ *                row stride ld >= V).  Per row r: live != NULL and live[r] == 0 -> tok_lp[r*ld_lp + col] = 0, nothing else.  Otherwise
+ *                m = max x, s = sum exp(x - m) (fp32, in an order that depends on V only: a row's bits do not depend on R, its slot or its
+ *                alignment), lp = (x[tok[r]] - m) - log s (accurate expf / logf); tok_lp[r*ld_lp + col] = lp, sum_lp[r] += lp,
+ *                n_tok[r] += 1; then, with live != NULL, eos_id >= 0 and tok[r] == eos_id, live[r] = 0: the eos is counted, the pads after
+ *                it are not, also when pad == eos (the kernel does not read sample_rows' `done`, already set for this step).
+ *                live == NULL: every row counts at every step.  The caller zeroes sum_lp / n_tok and sets live = 1 before step 0.
+ *                tok[r] outside [0, V) is device data, so no code reports it: the row's lp is NaN (x[clamp(tok)] is what is read; the
+ *                NaN reaches tok_lp, sum_lp and every score ranked from it).  `col` is a launch constant; no atomics; a replay is bit-equal.
+ *                Returns BADARG (NULL logits / tok / tok_lp / sum_lp / n_tok, unknown dtype), SHAPE (R, V <= 0, ld < V, col outside
+ *                [0, ld_lp)), UNSUPPORTED (logits not aligned to their element size).
+ *   seq_rank   : sum_lp, n_tok [B*K] -> score[b*K + j] = sum_lp / powf(n_tok, length_penalty) (HF's beam convention: 1 = mean
+ *                log-prob, 0 = the sum; n_tok == 0 -> -inf) and order[b, :] = the clip's K indices by descending score, ties -> lower
+ *                index, -inf rows last in index order (a NaN score ranks as -inf).  BADARG (NULL, NaN penalty), SHAPE (B, K <= 0),
+ *                UNSUPPORTED (K > 1024). */
+int egomi_token_logprob(const void* logits, int64_t ld, int R, int V, const int64_t* tok, int64_t eos_id, int32_t* live, float* tok_lp,
+                        int64_t ld_lp, int col, float* sum_lp, int32_t* n_tok, int dtype, egomi_stream_t stream);
+int egomi_seq_rank(const float* sum_lp, const int32_t* n_tok, int B, int K, float length_penalty, float* score, int32_t* order,
+                   egomi_stream_t stream);
 /* Beam search / beam sampling (num_beams > 1): HF GenerationMixin._beam_search, transformers 5.15 generation/utils.py:3208-3560.
  * Logical rows r = b * nb + j (item b, beam j), R = B * nb.  Every step is one beam_rows + one beam_update launch; ctl (int32 [6], device)
  * holds the loop-open flag [0] and the iteration count [1]: once a step closes the loop, both return at once, so T captured steps
@@ -441,6 +463,15 @@ int egomi_traj_metrics(const float* gen, const int32_t* n_gen, const float* gt, 
  *              left (or n_gt <= 0): NaN, NaN, -1. */
 int egomi_traj_metrics_min(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int K, int Tmax, int D,
                            double* min_ade, double* min_fde, int32_t* best, egomi_stream_t stream);
+/* medoid     : the most central of K samples, a choice that needs neither the ground truth nor model scores (the displacement of
+ *              models/utils/metrics.py:38-55 between two samples).  gen f32 [B,K,Tmax,D], n_gen i32 [B,K] (NULL = Tmax; values above Tmax
+ *              count as Tmax); sample j is valid when n_gen > 0.  d(j,i) = mean over t < max(n_j, n_i) of ||g_j[min(t,n_j-1)] -
+ *              g_i[min(t,n_i-1)]||_2 over all D dims (each padded with its own last step, as `metrics` pads).  cost[b,j] float64 = mean of
+ *              d(j,i) over the valid i != j, summed in index order; one valid sample: 0; invalid j: NaN.  pick[b] i32 = arg-min of cost
+ *              over the valid samples (lowest index on ties), none: -1.  BADARG (NULL gen / cost / pick), SHAPE (a size <= 0),
+ *              UNSUPPORTED (K > 1024). */
+int egomi_traj_medoid(const float* gen, const int32_t* n_gen, int B, int K, int Tmax, int D, double* cost, int32_t* pick,
+                      egomi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Trainable point backbone (--unfreeze_pc_encoder, models/pointllm/model_arch.py:33-36): the backward
