@@ -9,14 +9,13 @@ on static buffers.  Every length is a launch argument, so T steps are captured i
 (BASELINE.json config 5) and replayed with a single launch; token ids never leave the device.
 """
 import contextlib
-import ctypes
 import gc
 import os
 
 import torch
 
 from . import lora, ops
-from ._lib import c_p, c_i, c_f, c_i64, call
+from ._lib import c_i, c_f, c_i64, call
 from .ops import P, S, dt
 
 
@@ -168,24 +167,133 @@ def attn_decode_shared_rows(q, ld_q, kp, vp, key_mask, ks, vs, sfx_row, n_phys, 
          c_i(K), c_i(H), c_i(hd), c_i(Sp), c_i(S0), c_i(Tmax), c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
 
 
+class DenseCache:
+    """The KV cache of B decoder rows in the model's dtype: kc / vc [L, B, H, Smax, hd], one row of Smax keys per decoder row.
+
+    The three cache classes are what Decoder knows about a layout.  Each owns its tensors (tensors()) and has
+      G, fused_qkv          decoder rows per prompt row; whether qkv_finish() exists
+      begin(S0, total_new)  a prefill of S0 prompt tokens and then total_new steps start (raises if they do not fit)
+      append_prompt(l, qkv, B, Sq, row=None)   prefill: k | v of B * Sq post-RoPE q|k|v rows -> positions 0 .. Sq-1 of layer l, of prompt
+                            rows 0 .. B-1 or (B = 1) of prompt row `row`
+      append_step(l, qkv, pos)                 step: k | v of the B rows' q|k|v -> position pos
+      qkv_finish(l, ws, n, qkv, cos, sin, pos) the fused sum of n slabs + RoPE(pos) + append_step (egomi_qkv_finish*)
+      attend(l, pos, qkv, mask, out, kv_row, nb)   the B queries in qkv over keys 0 .. pos of layer l -> out; kv_row (beam mode, nb beams
+                            per item): key t of row r lives in physical row kv_row[r, t]"""
+    G, fused_qkv, names = 1, True, ("kc", "vc")
+    _append_op, _attend_op, _attend_rows_op, _finish_op = map(staticmethod, (kv_append, attn_decode, attn_decode_rows, ops.qkv_finish))
+
+    def __init__(self, lm, B, Smax, dtype, dev):
+        self.B, self.H, self.hd, self.Smax = B, lm.num_attention_heads, lm.head_dim, Smax
+        self.kc = torch.zeros(lm.num_hidden_layers, B, self.H, Smax, self.hd, dtype=dtype, device=dev)
+        self.vc = torch.zeros_like(self.kc)
+
+    def tensors(self):
+        return tuple(getattr(self, n) for n in self.names)
+
+    def begin(self, S0, total_new):
+        pass
+
+    def _append(self, sel, qkv, B, Sq, pos0):
+        d = self.H * self.hd
+        self._append_op(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), *(t[sel] for t in self.tensors()), B, Sq, self.H, self.hd, self.Smax, pos0)
+
+    def append_prompt(self, l, qkv, B, Sq, row=None):
+        self._append((l,) if row is None else (l, row), qkv, B, Sq, 0)
+
+    def append_step(self, l, qkv, pos):
+        self._append((l,), qkv, self.B, 1, pos)
+
+    def qkv_finish(self, l, ws, n, qkv, cos, sin, pos):
+        self._finish_op(ws, n, qkv, cos, sin, pos, *(t[l] for t in self.tensors()), self.B, self.H, self.hd, self.Smax)
+
+    def attend(self, l, pos, qkv, mask, out, kv_row, nb):
+        B, tail = self.B, (self.H, self.hd, self.Smax, pos + 1, self.hd ** -0.5)
+        kv = tuple(t[l] for t in self.tensors())
+        if kv_row is None:
+            self._attend_op(qkv, qkv.stride(0), *kv, mask, out, B, *tail)
+        else:
+            self._attend_rows_op(qkv, qkv.stride(0), *kv, kv_row, B, mask, out, B, nb, *tail)
+
+
+class Fp8Cache(DenseCache):
+    """DenseCache in e4m3fn codes kc / vc uint8 [L, B, H, Smax, hd] with fp32 scales ks / vs [L, B, H, Smax], one per (layer, row, head,
+    position) and tensor (csrc/kv8.hip).  The fp8 entry points take the scales right after the codes: the order of `names`."""
+    names = ("kc", "vc", "ks", "vs")
+    _append_op, _attend_op, _attend_rows_op, _finish_op = map(staticmethod, (kv_append_fp8, attn_decode_fp8, attn_decode_rows_fp8, ops.qkv_finish_fp8))
+
+    def __init__(self, lm, B, Smax, dtype, dev):
+        super().__init__(lm, B, Smax, torch.uint8, dev)
+        self.ks = torch.zeros(lm.num_hidden_layers, B, self.H, Smax, dtype=torch.float32, device=dev)
+        self.vs = torch.zeros_like(self.ks)
+
+
+class SplitCache:
+    """Prompt cache kp / vp [L, B / G, H, Sp, hd] (Sp = Smax - Tmax, one row per PROMPT, filled by one prefill per prompt) plus suffix
+    cache ksfx / vsfx [L, B, H, Tmax, hd] (the tokens each of the B rows generated); row r = b * G + j is sample / beam j of prompt b
+    (csrc/shared.hip).  A step rotates at pos = S0 + t but appends at suffix slot t; egomi_qkv_finish takes one `pos` for both, so this
+    layout has no fused finish.  Interface: DenseCache."""
+    fused_qkv = False
+
+    def __init__(self, lm, B, G, Smax, Tmax, dtype, dev):
+        self.B, self.G, self.H, self.hd, self.Tmax, self.Sp, self.S0 = B, G, lm.num_attention_heads, lm.head_dim, Tmax, Smax - Tmax, 0
+        self.kp = torch.zeros(lm.num_hidden_layers, B // G, self.H, self.Sp, self.hd, dtype=dtype, device=dev)
+        self.vp = torch.zeros_like(self.kp)
+        self.ksfx = torch.zeros(lm.num_hidden_layers, B, self.H, Tmax, self.hd, dtype=dtype, device=dev)
+        self.vsfx = torch.zeros_like(self.ksfx)
+
+    def tensors(self):
+        return (self.kp, self.vp, self.ksfx, self.vsfx)
+
+    def begin(self, S0, total_new):
+        if S0 > self.Sp or total_new > self.Tmax:
+            raise ValueError(f"prompt length {S0} / {total_new} new tokens exceed the decoder's prompt cache ({self.Sp}) / suffix cache ({self.Tmax})")
+        self.S0 = S0
+
+    def append_prompt(self, l, qkv, B, Sq, row=None):
+        d, sel = self.H * self.hd, (l,) if row is None else (l, row)
+        kv_append(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), self.kp[sel], self.vp[sel], B, Sq, self.H, self.hd, self.Sp, 0)
+
+    def append_step(self, l, qkv, pos):
+        d = self.H * self.hd
+        kv_append(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), self.ksfx[l], self.vsfx[l], self.B, 1, self.H, self.hd, self.Tmax, pos - self.S0)
+
+    def attend(self, l, pos, qkv, mask, out, kv_row, nb):
+        B, G, S0 = self.B, self.G, self.S0
+        head = (qkv, qkv.stride(0), self.kp[l], self.vp[l], mask[::G], self.ksfx[l], self.vsfx[l])
+        tail = (out, B // G, G, self.H, self.hd, self.Sp, S0, self.Tmax, pos - S0 + 1, self.hd ** -0.5)
+        if kv_row is None:
+            attn_decode_shared(*head, *tail)
+        else:                                               # the suffix rows that kv_row[:, S0:] names (its columns below S0 are not read)
+            attn_decode_shared_rows(*head, kv_row[:, S0:], B, *tail)
+
+
+def _group_spec(flag, rows, G, B, kv_dtype, max_new_tokens, max_len):
+    """The checks of a constructor flag that asks for the prompt / suffix cache with G decoder rows per prompt (`rows`: what G counts)."""
+    if kv_dtype == "fp8":
+        raise NotImplementedError(f"{flag} with an fp8 KV cache is not built")
+    if B % G:
+        raise ValueError(f"{B} decoder rows are not a multiple of {rows} = {G}")
+    if max_new_tokens is None or not 0 < int(max_new_tokens) < max_len:
+        raise ValueError(f"{flag} needs max_new_tokens (the suffix cache length) in 1 .. max_len - 1")
+    return G
+
+
 class Decoder:
     def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None, weight_dtype=None, samples_per_prompt=1, max_new_tokens=None,
                  split_cache=False):
-        """B = rows of the cache and of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...)).
-        kv_dtype="fp8": the KV cache holds e4m3fn codes kc / vc uint8 [L, B, H, Smax, hd] and fp32 scales ks / vs [L, B, H, Smax], one per
-        (layer, row, head, position) and tensor (csrc/kv8.hip); None: the model's dtype, as before.
+        """B = rows of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...)).
+        self.cache is the KV cache, one object per layout (DenseCache, Fp8Cache, SplitCache above); its tensors also read as self.kc / vc /
+        ks / vs / kp / vp / ksfx / vsfx, None where the layout has none.
+        kv_dtype="fp8": Fp8Cache instead of DenseCache; None: the model's dtype.
         weight_dtype="fp8": step() runs the four projections of every layer (q|k|v, o_proj, gate|up, down_proj) on e4m3fn codes with one fp32
         scale per output row (W8A16, csrc/w8.hip; self.w8); lm_head, the embeddings and the norms keep the model's dtype, and prefill runs
-        on the bf16 weights.  bf16 engines and B <= 512 only; None: the model's weights, as before.
+        on the bf16 weights.  bf16 engines and B <= 512 only; None: the model's weights.
         samples_per_prompt = K > 1 (best-of-K sampling; needs max_new_tokens = Tmax): the B rows are K samples of each of B / K prompts,
-        row r = b * K + j.  The cache is a prompt cache kp / vp [L, B / K, H, Sp, hd] (Sp = max_len - Tmax, one row per PROMPT, filled by one
-        prefill per prompt) plus a suffix cache ksfx / vsfx [L, B, H, Tmax, hd] (the tokens each row generated) instead of
-        [L, B, H, max_len, hd]; step() attends over both with egomi_attn_decode_shared (csrc/shared.hip).  sample() / greedy() are unchanged:
-        same rows, same seed, same draws as the expanded decoder.
-        split_cache=True with num_beams = nb > 1 (needs max_new_tokens = Tmax): beam search on the same prompt / suffix layout, kp / vp
-        [L, B / nb, H, Sp, hd] and ksfx / vsfx [L, B, H, Tmax, hd] with kc = vc = None.  A beam's suffix is the path through its ancestors'
-        rows, so step() appends into the row's own suffix row and attends with egomi_attn_decode_shared_rows through kv_row[:, S0:]
-        (egomi_beam_update keeps that table as in the dense layout; its columns below S0 are not read).  beam() is unchanged."""
+        row r = b * K + j, on a SplitCache with G = K; step() attends over prompt and suffix with egomi_attn_decode_shared.  sample() /
+        greedy() are unchanged: same rows, same seed, same draws as the expanded decoder.
+        split_cache=True with num_beams = nb > 1 (needs max_new_tokens = Tmax): beam search on a SplitCache with G = nb.  A beam's suffix is
+        the path through its ancestors' rows, so step() appends into the row's own suffix row and attends with
+        egomi_attn_decode_shared_rows through kv_row[:, S0:] (egomi_beam_update keeps that table as in the dense layout).  beam() is unchanged."""
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', not {kv_dtype!r}")
         if weight_dtype not in (None, "fp8"):
@@ -194,55 +302,28 @@ class Decoder:
             raise ValueError(f"fp8 decode weights need a bf16 model, not {engine.dtype}")
         if weight_dtype == "fp8" and B > 512:
             raise ValueError(f"fp8 decode weights support at most 512 decoder rows, not {B}")
-        K = int(samples_per_prompt)
+        K, nb, G = int(samples_per_prompt), int(num_beams), 1               # G: decoder rows per prompt-cache row
         if K != 1:
             if not 1 < K <= 32:
                 raise ValueError(f"samples_per_prompt must be between 1 and 32, not {samples_per_prompt}")
-            if int(num_beams) != 1:
+            if nb != 1:
                 raise NotImplementedError("samples_per_prompt > 1 with num_beams > 1 is not built")
-            if kv_dtype == "fp8":
-                raise NotImplementedError("samples_per_prompt > 1 with an fp8 KV cache is not built")
-            if B % K:
-                raise ValueError(f"{B} decoder rows are not a multiple of samples_per_prompt = {K}")
-            if max_new_tokens is None or not 0 < int(max_new_tokens) < max_len:
-                raise ValueError("samples_per_prompt > 1 needs max_new_tokens (the suffix cache length) in 1 .. max_len - 1")
+            G = _group_spec("samples_per_prompt > 1", "samples_per_prompt", K, B, kv_dtype, max_new_tokens, max_len)
         if split_cache:
-            if int(num_beams) <= 1:
+            if nb <= 1:
                 raise ValueError("split_cache needs num_beams > 1 (independent samples of one prompt: samples_per_prompt)")
-            if int(num_beams) > 32:
+            if nb > 32:
                 raise ValueError(f"split_cache supports at most 32 beams, not {num_beams}")
-            if kv_dtype == "fp8":
-                raise NotImplementedError("split_cache with an fp8 KV cache is not built")
-            if B % int(num_beams):
-                raise ValueError(f"{B} decoder rows are not a multiple of num_beams = {num_beams}")
-            if max_new_tokens is None or not 0 < int(max_new_tokens) < max_len:
-                raise ValueError("split_cache needs max_new_tokens (the suffix cache length) in 1 .. max_len - 1")
-        self.eng, self.B, self.Smax, self.nb, self.kv_dtype = engine, B, max_len, int(num_beams), kv_dtype
-        self.K = K
-        self.G = K if K > 1 else int(num_beams) if split_cache else 1      # logical rows per prompt-cache row
-        self.split = self.G > 1                                            # prompt cache + suffix cache instead of the dense one
-        G = self.G
+            G = _group_spec("split_cache", "num_beams", nb, B, kv_dtype, max_new_tokens, max_len)
+        self.eng, self.B, self.Smax, self.nb, self.K, self.kv_dtype = engine, B, max_len, nb, K, kv_dtype
         lm = engine.dims.lm
-        L, H, hd, d, Fd, V = lm.num_hidden_layers, lm.num_attention_heads, lm.head_dim, lm.hidden_size, lm.intermediate_size, lm.vocab_size
+        L, d, Fd, V = lm.num_hidden_layers, lm.hidden_size, lm.intermediate_size, lm.vocab_size
         T, dev = engine.dtype, engine.device
-        self.fp8 = kv_dtype == "fp8"
-        if self.split:
-            self.Tmax = int(max_new_tokens)
-            self.Sp = max_len - self.Tmax
-            self.kc = self.vc = None
-            self.kp = torch.zeros(L, B // G, H, self.Sp, hd, dtype=T, device=dev)
-            self.vp = torch.zeros_like(self.kp)
-            self.ksfx = torch.zeros(L, B, H, self.Tmax, hd, dtype=T, device=dev)
-            self.vsfx = torch.zeros_like(self.ksfx)
-            self.S0 = 0
-        else:
-            self.kc = torch.zeros(L, B, H, max_len, hd, dtype=torch.uint8 if self.fp8 else T, device=dev)
-            self.vc = torch.zeros_like(self.kc)
-        self.ks = torch.zeros(L, B, H, max_len, dtype=torch.float32, device=dev) if self.fp8 else None
-        self.vs = torch.zeros_like(self.ks) if self.fp8 else None
+        self.cache = SplitCache(lm, B, G, max_len, int(max_new_tokens), T, dev) if G > 1 else \
+            (Fp8Cache if kv_dtype == "fp8" else DenseCache)(lm, B, max_len, T, dev)
         z = lambda *s, dtype=T: torch.zeros(*s, dtype=dtype, device=dev)
         self.x, self.h, self.qkv, self.ao, self.x_mid, self.h2 = z(B, d), z(B, d), z(B, 3 * d), z(B, d), z(B, d), z(B, d)
-        self.gu, self.act, self.x_out, self.hn, self.lg = z(B, 2 * Fd), z(B, Fd), z(B, d), z(B, d), z(B, V)
+        self.gu, self.act, self.hn, self.lg = z(B, 2 * Fd), z(B, Fd), z(B, d), z(B, V)
         self.tok = z(B, 1, dtype=torch.int64)
         self.gws = torch.empty(128 << 20, dtype=torch.uint8, device=dev)      # split-K slabs of the skinny decode GEMMs
         # sequences, key mask, generator state and eos flags live in STATIC buffers, so that a captured token loop can be replayed by a later
@@ -286,14 +367,12 @@ class Decoder:
                           "down": ops.mm_w8_slabs(self.act, *q["down"], self.gws, count_only=True)}
             if not all(self.fused.values()):
                 raise ValueError(f"fp8 decode weights cannot run this model's projection shapes ({self.fused})")
-            if self.split:
-                self.fused["qkv"] = 0
         elif T == torch.bfloat16 and os.environ.get("EGOMI_DECODE_FUSED", "1") != "0" and B <= 512:
-            # the split cache rotates at S0 + t but appends at suffix slot t; egomi_qkv_finish takes one `pos` for both, so its q|k|v
-            # product keeps the unfused mm + rope_ + kv_append path
-            self.fused["qkv"] = 0 if self.split else ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
+            self.fused["qkv"] = ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
             self.fused["o"] = ops.mm_slabs(self.ao, w["model.layers.0.self_attn.o_proj.weight"], self.x_mid, self.gws, count_only=True)
             self.fused["down"] = ops.mm_slabs(self.act, w["model.layers.0.mlp.down_proj.weight"], self.x, self.gws, count_only=True)
+        if not self.cache.fused_qkv:                        # the q|k|v product keeps the unfused mm + rope_ + append_step path
+            self.fused["qkv"] = 0
 
     def _lp_buffers(self):
         """Static buffers of sample(logprobs=True) / greedy(logprobs=True), made on first use: lp_tok [B, max_len] (column t = step t),
@@ -363,8 +442,7 @@ class Decoder:
             raise ValueError("prompt + new tokens exceed the decoder's cache length")
         if B * nb != self.B:
             raise ValueError(f"{B} prompts x {nb} beams do not fill the decoder's {self.B} rows")
-        if self.split and (S0 > self.Sp or total_new > self.Tmax):
-            raise ValueError(f"prompt length {S0} / {total_new} new tokens exceed the decoder's prompt cache ({self.Sp}) / suffix cache ({self.Tmax})")
+        self.cache.begin(S0, total_new)
         if nb > 1:
             input_ids, mask = input_ids.repeat_interleave(nb, 0), mask.repeat_interleave(nb, 0)
         self.mask_buf.fill_(1)
@@ -374,96 +452,39 @@ class Decoder:
         self.seq_buf[:, :S0] = input_ids
         self.seq = self.seq_buf[:, :S0 + total_new]
 
-    def _sink(self, l, qkv, B, Sq):
-        d = self.eng.dims.lm.hidden_size
-        self._append(l, None, qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), B, Sq, 0)
-
-    def _append(self, l, b, k, v, ld, B, Sq, pos0, suffix=False):
-        """k / v rows -> layer l of the cache (all rows, or row b alone) at positions pos0 .. pos0 + Sq - 1.  Split cache: the prompt
-        cache (prefill: rows are prompts), or with suffix=True the suffix cache (step: rows are samples / beams, pos0 = suffix slot)."""
-        lm = self.eng.dims.lm
-        H, hd = lm.num_attention_heads, lm.head_dim
-        sel = (l,) if b is None else (l, b)
-        if self.split:
-            kc, vc, Smax = (self.ksfx, self.vsfx, self.Tmax) if suffix else (self.kp, self.vp, self.Sp)
-            kv_append(k, v, ld, kc[sel], vc[sel], B, Sq, H, hd, Smax, pos0)
-            return
-        if self.fp8:
-            kv_append_fp8(k, v, ld, self.kc[sel], self.vc[sel], self.ks[sel], self.vs[sel], B, Sq, H, hd, self.Smax, pos0)
-        else:
-            kv_append(k, v, ld, self.kc[sel], self.vc[sel], B, Sq, H, hd, self.Smax, pos0)
-
-    def _attend(self, l, pos):
-        """Attention of this step's queries (self.qkv[:, :d]) over layer l of the cache, keys 0 .. pos, into self.ao: the read side of
-        _append.  Split cache: prompt cache + the row's suffix (beam mode: the suffix rows that self.kv_row[:, S0:] names); otherwise the
-        dense or fp8 cache, each row's own physical row or, in beam mode, the rows that self.kv_row names."""
-        lm = self.eng.dims.lm
-        B, H, hd = self.B, lm.num_attention_heads, lm.head_dim
-        ld_q, scale = 3 * lm.hidden_size, hd ** -0.5
-        if self.split:
-            G = self.G
-            geom = (self.ao, B // G, G, H, hd, self.Sp, self.S0, self.Tmax, pos - self.S0 + 1, scale)
-            if self.kv_row is None:
-                attn_decode_shared(self.qkv, ld_q, self.kp[l], self.vp[l], self.mask[::G], self.ksfx[l], self.vsfx[l], *geom)
-            else:
-                attn_decode_shared_rows(self.qkv, ld_q, self.kp[l], self.vp[l], self.mask[::G], self.ksfx[l], self.vsfx[l],
-                                        self.kv_row[:, self.S0:], B, *geom)
-            return
-        cache = (self.kc[l], self.vc[l], self.ks[l], self.vs[l]) if self.fp8 else (self.kc[l], self.vc[l])
-        if self.kv_row is None:
-            (attn_decode_fp8 if self.fp8 else attn_decode)(self.qkv, ld_q, *cache, self.mask, self.ao, B, H, hd, self.Smax, pos + 1, scale)
-        else:
-            (attn_decode_rows_fp8 if self.fp8 else attn_decode_rows)(self.qkv, ld_q, *cache, self.kv_row, B, self.mask, self.ao, B, self.nb, H, hd,
-                                                                     self.Smax, pos + 1, scale)
-
-    def prefill(self, input_ids, attention_mask, point_clouds, fps_start, total_new, nb=1):
+    def prefill(self, input_ids, attention_mask, point_clouds, fps_start, total_new, nb=1, chunk=None):
         """nb > 1 (beam mode): the B prompts run ONCE each; their K/V land in physical cache rows 0..B-1 and their logits in rows 0..B-1 of
-        self.lg, which every beam of the item reads at step 0 (HF expands to B * nb identical rows and prefills them all)."""
+        self.lg, which every beam of the item reads at step 0 (HF expands to B * nb identical rows and prefills them all).
+        chunk=None: one prompt pass over the whole batch; chunk=n: prefill_chunked()."""
         B, S0 = input_ids.shape
-        dev = self.eng.device
+        eng, dev = self.eng, self.eng.device
         if self.K > 1:
             nb = self.K
         mask = torch.ones(B, S0, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
         self._set_inputs(input_ids, mask, total_new, nb)
-        hn = self.eng.forward_hidden(input_ids, mask, point_clouds, fps_start, save=False, kv_sink=self._sink)
-        self.pos = S0
-        last = hn.view(B, S0, -1)[:, -1].contiguous()
-        ops.mm(last, self.eng.w["lm_head.weight"], out=self.lg[:B])
-        return self._share_logits(B, S0)
+        for b0 in range(0, B, chunk or B):
+            b1 = min(B, b0 + (chunk or B))
 
-    def _share_logits(self, B, S0):
-        """Shared-prompt mode: every sample of a prompt starts from the prompt's step-0 logits (HF prefills K identical rows).  Beams read
-        their item's row themselves (egomi_beam_rows' lg_div)."""
-        if self.split:
-            self.S0 = S0
-        if self.K == 1:
+            def sink(l, qkv, Bc, Sq, b0=b0):
+                if chunk is None:                 # the whole batch: one append
+                    return self.cache.append_prompt(l, qkv, Bc, Sq)
+                for i in range(Bc):               # a batch slice of the [L,B,H,Smax,hd] cache is not contiguous over samples: one append each
+                    self.cache.append_prompt(l, qkv[i * Sq:(i + 1) * Sq], 1, Sq, row=b0 + i)
+            cut = lambda a: None if a is None else a[b0:b1]
+            hn = eng.forward_hidden(input_ids[b0:b1], mask[b0:b1], cut(point_clouds), cut(fps_start), save=False, kv_sink=sink)
+            last = hn.view(b1 - b0, S0, -1)[:, -1].contiguous()
+            ops.mm(last, eng.w["lm_head.weight"], out=self.lg[b0:b1])
+        self.pos = S0
+        if self.K == 1:                                     # beams read their item's row themselves (egomi_beam_rows' lg_div)
             return self.lg[:B]
+        # every sample of a prompt starts from the prompt's step-0 logits (HF prefills K identical rows)
         self.lg.copy_(self.lg[:B].repeat_interleave(self.K, 0))
         return self.lg
 
     def prefill_chunked(self, input_ids, attention_mask, point_clouds, fps_start, total_new, chunk=16, nb=1):
         """prefill() for large batches (config 5: bs=256): the prompt pass runs `chunk` samples at a time (its activations are
         what limits the batch, not the cache) and every chunk appends its K/V rows to its own slice of the static cache."""
-        B, S0 = input_ids.shape
-        eng, dev = self.eng, self.eng.device
-        d = eng.dims.lm.hidden_size
-        if self.K > 1:
-            nb = self.K
-        mask = torch.ones(B, S0, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
-        self._set_inputs(input_ids, mask, total_new, nb)
-        for b0 in range(0, B, chunk):
-            b1 = min(B, b0 + chunk)
-
-            def sink(l, qkv, Bc, Sq, b0=b0):
-                for i in range(Bc):               # a batch slice of the [L,B,H,Smax,hd] cache is not contiguous over samples: one append each
-                    self._append(l, b0 + i, qkv[i * Sq:(i + 1) * Sq, d:2 * d], qkv[i * Sq:(i + 1) * Sq, 2 * d:], qkv.stride(0), 1, Sq, 0)
-            pcs = None if point_clouds is None else point_clouds[b0:b1]
-            st = None if fps_start is None else fps_start[b0:b1]
-            hn = eng.forward_hidden(input_ids[b0:b1], mask[b0:b1], pcs, st, save=False, kv_sink=sink)
-            last = hn.view(b1 - b0, S0, -1)[:, -1].contiguous()
-            ops.mm(last, eng.w["lm_head.weight"], out=self.lg[b0:b1])
-        self.pos = S0
-        return self._share_logits(B, S0)
+        return self.prefill(input_ids, attention_mask, point_clouds, fps_start, total_new, nb, chunk)
 
     # -- one decode step on static buffers: consumes self.tok, leaves logits in self.lg ---------------------
     def step(self, pos):
@@ -480,21 +501,15 @@ class Decoder:
                 ops.rmsnorm(x, w[p + "input_layernorm.weight"], lm.rms_norm_eps, out=self.h)
             if fq:
                 n = self._slabs(l, "qkv", self.h, self.qkv, self.wqkv[l])
-                if self.fp8:
-                    ops.qkv_finish_fp8(self.gws, n, self.qkv, eng.cos, eng.sin, pos, self.kc[l], self.vc[l], self.ks[l], self.vs[l], B, H, hd, self.Smax)
-                else:
-                    ops.qkv_finish(self.gws, n, self.qkv, eng.cos, eng.sin, pos, self.kc[l], self.vc[l], B, H, hd, self.Smax)
+                self.cache.qkv_finish(l, self.gws, n, self.qkv, eng.cos, eng.sin, pos)
             else:
-                if self.w8 is not None:                     # (shared-prompt mode: the only unfused q|k|v product on fp8 weights)
+                if self.w8 is not None:                     # (prompt / suffix cache: the only unfused q|k|v product on fp8 weights)
                     ops.mm_w8(self.h, *self.w8[l]["qkv"], out=self.qkv, workspace=self.gws)
                 else:
                     ops.mm(self.h, self.wqkv[l], out=self.qkv, workspace=self.gws)
                 ops.rope_(self.qkv, eng.cos, eng.sin, B, 1, pos, 2 * H, hd, 3 * d)
-                if self.split:
-                    self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos - self.S0, suffix=True)
-                else:
-                    self._append(l, None, self.qkv[:, d:2 * d], self.qkv[:, 2 * d:], 3 * d, B, 1, pos)
-            self._attend(l, pos)
+                self.cache.append_step(l, self.qkv, pos)
+            self.cache.attend(l, pos, self.qkv, self.mask, self.ao, self.kv_row, self.nb)
             if fo:
                 n = self._slabs(l, "o", self.ao, self.x_mid, self._w(l, "o"))
                 ops.slabs_rmsnorm(self.gws, n, x, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, self.x_mid, self.h2)
@@ -522,6 +537,34 @@ class Decoder:
             ops.rmsnorm(x, w["model.norm.weight"], lm.rms_norm_eps, out=self.hn)
         ops.mm(self.hn, w["lm_head.weight"], out=self.lg)
 
+    # -- token loops ---------------------------------------------------------------------------------
+    def _run(self, steps, use_graph, key=None):
+        """Runs the token loop steps(): eagerly, or as ONE hipGraph.  The captured loop depends only on what the caller puts into `key`
+        (every buffer it touches is static; the seed, the eos flags and the loop-open flag are device memory), so a later call with the
+        same key replays the graph kept in self._graphs; key=None captures afresh and keeps nothing."""
+        if not use_graph:
+            return steps()
+        g = self._graphs.get(key) if key is not None else None
+        if g is None:
+            g = torch.cuda.CUDAGraph()
+            with _capture(g):
+                steps()
+            if key is not None:
+                self._graphs[key] = g
+        g.replay()
+        self.graph = g
+
+    def _seed(self, seed):
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())            # the CPU default generator: torch.manual_seed() makes a run repeatable
+        self.rng.copy_(torch.tensor([int(seed), 0], dtype=torch.int64))
+
+    def _score_buf(self, T_new):
+        """The static [T_new, B, V] fp32 buffer of the processed scores."""
+        if T_new not in self._scores:
+            self._scores[T_new] = torch.empty(T_new, self.B, self.lg.shape[1], dtype=torch.float32, device=self.eng.device)
+        return self._scores[T_new]
+
     def sample(self, T_new, do_sample=True, temperature=1.0, top_k=50, top_p=0.95, repetition_penalty=1.0, eos=None, pad=None, seed=None,
                use_graph=True, logprobs=False):
         """After prefill(): T_new steps of HF generate's token loop (model_arch.py:82-108 -> GenerationMixin: logits processors, warpers,
@@ -531,14 +574,8 @@ class Decoder:
         logprobs=True: every step also runs one egomi_token_logprob launch on the raw logits, after the token kernel: self.lp_tok[:, t] is
         the chosen token's log-prob (0 once the row has finished), self.lp_sum / self.lp_n the row's sum and token count (its eos counted,
         the pads not).  A graph of its own (the flag is part of the key); with False the loop has the launches it had."""
-        S0, dev = self.pos, self.eng.device
-        V = self.lg.shape[1]
-        sc_buf = self._scores.get(T_new)
-        if sc_buf is None:
-            sc_buf = self._scores[T_new] = torch.empty(T_new, self.B, V, dtype=torch.float32, device=dev)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())            # the CPU default generator: torch.manual_seed() makes a run repeatable
-        self.rng.copy_(torch.tensor([int(seed), 0], dtype=torch.int64))
+        S0, sc_buf = self.pos, self._score_buf(T_new)
+        self._seed(seed)
         self.done_buf.zero_()
         self.done = self.done_buf if eos is not None else None
         if logprobs:
@@ -554,22 +591,8 @@ class Decoder:
                     token_logprob(self.lg, self.tok.view(-1), eos, lp_live, self.lp_tok, t, self.lp_sum, self.lp_n)
                 if t + 1 < T_new:
                     self.step(S0 + t)
-        if not use_graph:
-            steps()
-        else:
-            # the captured loop depends on the prompt length, the number of steps and the sampling parameters only (every buffer it touches is
-            # static, the seed and the eos flags are device memory): a later call with the same key replays it
-            key = (S0, T_new, kw["repetition_penalty"], kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], eos, pad)
-            if logprobs:
-                key = key + ("logprobs",)
-            g = self._graphs.get(key)
-            if g is None:
-                g = torch.cuda.CUDAGraph()
-                with _capture(g):
-                    steps()
-                self._graphs[key] = g
-            g.replay()
-            self.graph = g
+        key = (S0, T_new, kw["repetition_penalty"], kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], eos, pad)
+        self._run(steps, use_graph, key + ("logprobs",) if logprobs else key)
         self.pos = S0 + T_new
         return self.seq, sc_buf
 
@@ -577,35 +600,26 @@ class Decoder:
         """After prefill(): T_new greedy tokens.  Returns (sequences [B,S0+T], scores list or None).  logprobs=True: one egomi_token_logprob
         launch per step after the arg-max, into self.lp_tok / lp_sum / lp_n as in sample() (no eos here: every row counts every step)."""
         S0 = self.pos
-        scores = [] if keep_scores else None
+        scores = None                                       # eager: fp32 clones; captured: views of one buffer the graph writes
+        if keep_scores:
+            scores = list(torch.zeros(T_new, self.B, self.lg.shape[1], dtype=torch.float32, device=self.eng.device)) if use_graph else []
         if logprobs:
             self._lp_buffers()
-        if not use_graph:
+
+        def steps():
             for t in range(T_new):
-                if keep_scores:
+                if keep_scores and use_graph:
+                    ops.cast(self.lg, torch.float32, out=scores[t])
+                elif keep_scores:
                     scores.append(self.lg.float().clone())
                 argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
                 if logprobs:
                     token_logprob(self.lg, self.tok.view(-1), None, None, self.lp_tok, t, self.lp_sum, self.lp_n)
                 if t + 1 < T_new:
                     self.step(S0 + t)
-            self.pos = S0 + T_new
-            return self.seq, scores
-        sc_buf = torch.zeros(T_new, self.B, self.lg.shape[1], dtype=torch.float32, device=self.eng.device) if keep_scores else None
-        g = torch.cuda.CUDAGraph()
-        with _capture(g):
-            for t in range(T_new):
-                if keep_scores:
-                    ops.cast(self.lg, torch.float32, out=sc_buf[t])
-                argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
-                if logprobs:
-                    token_logprob(self.lg, self.tok.view(-1), None, None, self.lp_tok, t, self.lp_sum, self.lp_n)
-                if t + 1 < T_new:
-                    self.step(S0 + t)
-        g.replay()
-        self.graph = g
+        self._run(steps, use_graph)                         # a fresh capture per call
         self.pos = S0 + T_new
-        return self.seq, ([sc_buf[t] for t in range(T_new)] if keep_scores else None)
+        return self.seq, scores
 
     # -- beam search / beam sampling ---------------------------------------------------------------
     def _beam_buffers(self):
@@ -632,9 +646,7 @@ class Decoder:
         K = max(2, 1 + n_eos) * nb                                            # beams_to_keep
         max_len = S0 + T_new
         fill = (pad or eos) if eos is not None else -1                         # HF's output_fill_value
-        sc_buf = self._scores.get(T_new)
-        if sc_buf is None:
-            sc_buf = self._scores[T_new] = torch.empty(T_new, R, V, dtype=torch.float32, device=dev)
+        sc_buf = self._score_buf(T_new)
         cands = self._cands.get(K)
         if cands is None:
             cands = self._cands[K] = (torch.empty(R, K, dtype=torch.float32, device=dev), torch.empty(R, K, dtype=torch.float32, device=dev),
@@ -653,9 +665,7 @@ class Decoder:
         self.ctl[0] = 1
         self.kv_row.zero_()
         self.kv_row[:, :S0] = (torch.arange(R, device=dev, dtype=torch.int32) // nb)[:, None]     # every beam reads its item's prompt row
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.rng.copy_(torch.tensor([int(seed), 0], dtype=torch.int64))
+        self._seed(seed)
         if not do_sample:                                                      # HF applies the warpers in sampling mode only
             temperature, top_k, top_p = 1.0, 0, 1.0
         kw = dict(repetition_penalty=float(repetition_penalty or 1.0), temperature=float(temperature or 1.0), top_k=int(top_k or 0),
@@ -671,18 +681,7 @@ class Decoder:
                             self.tok.view(-1), self.ctl)
                 if t + 1 < T_new:
                     self.step(S0 + t)
-        if not use_graph:
-            steps()
-        else:
-            key = ("beam", S0, T_new, nb, float(length_penalty), es, eos, pad, tuple(sorted(kw.items())))
-            g = self._graphs.get(key)
-            if g is None:
-                g = torch.cuda.CUDAGraph()
-                with _capture(g):
-                    steps()
-                self._graphs[key] = g
-            g.replay()
-            self.graph = g
+        self._run(steps, use_graph, ("beam", S0, T_new, nb, float(length_penalty), es, eos, pad, tuple(sorted(kw.items()))))
         self.pos = S0 + T_new
         n_iter = int(self.ctl[1])
         nrs = int(num_return_sequences)
@@ -690,3 +689,8 @@ class Decoder:
         bidx = self.fin_bidx[rows, :T_new]
         lgen = int((bidx >= 0).sum(1).max()) if T_new > 0 else 0              # :3520, the longest returned hypothesis
         return (self.fin_seq[rows, :S0 + lgen].clone(), self.fin_score[rows].clone(), sc_buf[:n_iter].clone(), bidx[:, :lgen].long())
+
+
+Decoder.split = property(lambda self: self.cache.G > 1, doc="prompt cache + suffix cache instead of the dense one")
+for _n in ("kc", "vc", "ks", "vs", "kp", "vp", "ksfx", "vsfx"):           # the cache's tensors under their names; None where the layout has none
+    setattr(Decoder, _n, property(lambda self, _n=_n: getattr(self.cache, _n, None)))

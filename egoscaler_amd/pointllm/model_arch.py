@@ -689,24 +689,13 @@ class TrajPointLLMForCausalLM(nn.Module):
         T = int(max_length)
         if share and T < 1:
             raise ValueError("share_prompt=True needs max_length >= 1")
-        if isinstance(eos_token_id, str):
-            eos_token_id = self.dims.tok.eos
-        if eos_token_id is not None and pad_token_id is None:
-            pad_token_id = self.dims.tok.pad if self.dims.tok.pad is not None else eos_token_id     # HF: pad defaults to eos when the config has none
-        for name, v in (("temperature", temperature), ("repetition_penalty", repetition_penalty)):
-            if v is not None and not float(v) > 0:
-                raise ValueError(f"`{name}` has to be a strictly positive float, but is {v}")               # logits_process.py:239,307
-        if top_p is not None and not (0 < float(top_p) <= 1.0):
-            raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+        eos_token_id, pad_token_id = self._sampling_args(eos_token_id, pad_token_id, temperature, repetition_penalty, top_p)
         # one Decoder (static KV cache + captured token loops) per geometry, kept while the decoder layers it holds stacked copies of cannot
         # change: frozen-LLM mode, same prepared weights.  run_validation / evaluate (train.py:207-264, evaluate.py:104-154) call generate()
         # once per batch: without this every batch re-allocated the cache and re-captured a graph of (new tokens x ~300) kernels
         if share:                                          # B prompts, B * n_ret decoder rows: one prefill and one cached K/V per prompt
             dec = self._decoder(B * n_ret, S0 + T, kv=kv, wd=wd, share=(n_ret, T))
-            if B > 16:
-                dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=16)
-            else:
-                dec.prefill(ids, attention_mask, point_clouds, fps_start, T)
+            self._prefill_prompts(dec, ids, attention_mask, point_clouds, fps_start, T)
             B = B * n_ret
         else:
             dec = self._decoder(B, S0 + T, kv=kv, wd=wd)
@@ -731,6 +720,26 @@ class TrajPointLLMForCausalLM(nn.Module):
                 out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B // n_ret, n_ret, float(rank_length_penalty))
         return out
 
+    def _sampling_args(self, eos_token_id, pad_token_id, temperature, repetition_penalty, top_p):
+        """-> (eos, pad) as HF resolves them: eos "config" = the config's, pad defaults to the config's or, when it has none, to eos; raises
+        on a temperature, repetition penalty or top_p that HF's processors reject (logits_process.py:239,307)."""
+        if isinstance(eos_token_id, str):
+            eos_token_id = self.dims.tok.eos
+        if eos_token_id is not None and pad_token_id is None:
+            pad_token_id = self.dims.tok.pad if self.dims.tok.pad is not None else eos_token_id
+        for name, v in (("temperature", temperature), ("repetition_penalty", repetition_penalty)):
+            if v is not None and not float(v) > 0:
+                raise ValueError(f"`{name}` has to be a strictly positive float, but is {v}")
+        if top_p is not None and not (0 < float(top_p) <= 1.0):
+            raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+        return eos_token_id, pad_token_id
+
+    def _prefill_prompts(self, dec, ids, attention_mask, point_clouds, fps_start, T, nb=1):
+        """Prefill of a decoder whose prompts are fewer than its rows (beams, shared prompt): more than 16 prompts run chunked."""
+        if ids.shape[0] > 16:
+            return dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=16, nb=nb)
+        return dec.prefill(ids, attention_mask, point_clouds, fps_start, T, nb=nb)
+
     def _decoder(self, B, max_len, nb=1, kv=None, wd=None, share=None, split=None):
         """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER
         prepare(): load_state_dict() / _apply() leave the engine unprepared (or replace it), and a decoder made before them holds stacked
@@ -750,12 +759,12 @@ class TrajPointLLMForCausalLM(nn.Module):
         reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
         dec = cache.get(key) if reuse else None
         if dec is None:
+            kw = dict(kv_dtype=kv, weight_dtype=wd)
             if share is not None:
-                dec = Decoder(eng, B, max_len, kv_dtype=kv, weight_dtype=wd, samples_per_prompt=share[0], max_new_tokens=share[1])
+                kw.update(samples_per_prompt=share[0], max_new_tokens=share[1])
             elif split is not None:
-                dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv, weight_dtype=wd, split_cache=True, max_new_tokens=split)
-            else:
-                dec = Decoder(eng, B * nb, max_len, num_beams=nb, kv_dtype=kv, weight_dtype=wd)
+                kw.update(split_cache=True, max_new_tokens=split)
+            dec = Decoder(eng, B * nb, max_len, num_beams=nb, **kw)
             if reuse:
                 while len(cache) >= 2:                     # the full batch and the split's short last one; a cache is 2 * L * B * H * Smax * hd elements
                     cache.pop(next(iter(cache)))
@@ -764,23 +773,10 @@ class TrajPointLLMForCausalLM(nn.Module):
 
     def _generate_beam(self, ids, attention_mask, point_clouds, fps_start, T, nb, n_ret, length_penalty, early_stopping, do_sample, temperature,
                        top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, seed, use_graph, kv=None, wd=None, split=False):
-        dev = self.engine.device
         B, S0 = ids.shape
-        if isinstance(eos_token_id, str):
-            eos_token_id = self.dims.tok.eos
-        if eos_token_id is not None and pad_token_id is None:
-            pad_token_id = self.dims.tok.pad if self.dims.tok.pad is not None else eos_token_id
-        for name, v in (("temperature", temperature), ("repetition_penalty", repetition_penalty)):
-            if v is not None and not float(v) > 0:
-                raise ValueError(f"`{name}` has to be a strictly positive float, but is {v}")
-        if top_p is not None and not (0 < float(top_p) <= 1.0):
-            raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+        eos_token_id, pad_token_id = self._sampling_args(eos_token_id, pad_token_id, temperature, repetition_penalty, top_p)
         dec = self._decoder(B, S0 + T, nb, kv=kv, wd=wd, split=T if split else None)
-        chunk = 16
-        if B > chunk:
-            dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=chunk, nb=nb)
-        else:
-            dec.prefill(ids, attention_mask, point_clouds, fps_start, T, nb=nb)
+        self._prefill_prompts(dec, ids, attention_mask, point_clouds, fps_start, T, nb=nb)
         seq, ss, sc, bidx = dec.beam(T, num_return_sequences=n_ret, length_penalty=length_penalty, early_stopping=early_stopping,
                                      do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                                      eos=eos_token_id, pad=pad_token_id, seed=seed, use_graph=use_graph)

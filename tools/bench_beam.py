@@ -91,8 +91,7 @@ def main():
             dec.lg.copy_(lg0)
             dec.pos = Lp
             return dec.beam(T, length_penalty=1.0, eos=None, pad=dims.tok.pad)
-        caches = (dec.kp, dec.vp, dec.ksfx, dec.vsfx) if dec.kc is None else (dec.kc, dec.vc)
-        arms[layout] = (dec, beam, sum(c.numel() * c.element_size() for c in caches))
+        arms[layout] = (dec, beam, sum(c.numel() * c.element_size() for c in dec.cache.tensors()))
     for _, beam, _ in arms.values():                                      # capture + first replay of every arm
         beam()
     torch.cuda.synchronize()

@@ -96,7 +96,6 @@ def main():
             rep = lambda x: x.repeat_interleave(K, 0)
             pre = lambda: dec.prefill(rep(ids), rep(mask), rep(pcs), rep(st), T)
         ms_pre = timed(pre)
-        caches = [getattr(dec, n, None) for n in ("kc", "vc", "kp", "vp", "ksfx", "vsfx")]
         mid = T // 2
         if a.mode == "shared":
             kv_step = B * Lp * row_kv + B * K * mid * row_kv
@@ -104,7 +103,7 @@ def main():
             kv_step = B * K * (Lp + mid) * row_kv
         out["K"][str(K)] = {"prefill_ms": round(ms_pre, 2), "ms_per_step": round(ms_loop / max(1, T - 1), 4), "loop_ms": round(ms_loop, 2),
                             "generate_ms": round(ms_gen, 2), "tokens_per_s": round(B * K * T / (ms_gen * 1e-3), 1),
-                            "cache_GB": round(sum(t.numel() * t.element_size() for t in caches if t is not None) / 1e9, 3),
+                            "cache_GB": round(sum(t.numel() * t.element_size() for t in dec.cache.tensors()) / 1e9, 3),
                             "modelled_GB_per_step_mid": {"weights": round(p_llm / 1e9, 2), "kv": round(kv_step / 1e9, 3)},
                             "modelled_GBps": round((p_llm + kv_step) / (ms_loop / max(1, T - 1) * 1e-3) / 1e9, 1)}
         del dec

@@ -109,8 +109,7 @@ def run(batch=256, steps=32, layers=None, reps=5, prefill_chunk=16, err_batch=8)
                                         "algorithmic_GB": round(alg / 1e9, 2), "kv_GB": round(kv_bytes / 1e9, 2),
                                         "frac_8TBs": round(alg / (ms * 1e-3) / 8e12, 4), "ms_all": [round(x, 2) for x in a["ms"]],
                                         "deterministic_replay": bool(torch.equal(a["seq0"], a["dec"].seq)),
-                                        "cache_GB": round(sum(t.numel() * t.element_size() for t in (a["dec"].kc, a["dec"].vc, a["dec"].ks, a["dec"].vs)
-                                                              if t is not None) / 1e9, 2)}
+                                        "cache_GB": round(sum(t.numel() * t.element_size() for t in a["dec"].cache.tensors()) / 1e9, 2)}
         del a["dec"]
     torch.cuda.empty_cache()
     if err_batch:
