@@ -83,6 +83,42 @@ def w8_quantize(w):
     return (w / s[:, None]).to(torch.float8_e4m3fn).view(torch.uint8), s
 
 
+W4_GROUP = 128                                       # columns per scale group of the int4 decode weights
+
+
+def w4_quantize(w):
+    """The int4 decode weights' numerics restated in torch on the host (csrc/w4.hip header): rows w [N, K], K % 32 == 0 -> (packed uint8
+    [N, K / 2], scales fp32 [NG, N]).  Group g = columns [128 g, min(K, 128 g + 128)), NG = ceil(K / 128); s[g, n] = amax / 7 (1 where
+    amax == 0), code = clamp(round(w / s), -7, 7) (torch.round: ties to even), stored as the nibble code + 8 in the natural order: byte b
+    of a row holds column 2 b in its low nibble and column 2 b + 1 in its high nibble.
+    egomi_quantize_rows_int4 is bit-equal to it (run it on the host: a device's division need not be correctly rounded)."""
+    w = w.float()
+    N, K = w.shape
+    if K % 32:
+        raise ValueError(f"w4_quantize: K = {K} is not a multiple of 32")
+    NG = -(-K // W4_GROUP)
+    wp = torch.zeros(N, NG * W4_GROUP, dtype=torch.float32, device=w.device)
+    wp[:, :K] = w
+    s = wp.view(N, NG, W4_GROUP).abs().amax(2) / 7.0
+    s = torch.where(s == 0, torch.ones_like(s), s)
+    codes = torch.round(wp.view(N, NG, W4_GROUP) / s[:, :, None]).clamp_(-7, 7).view(N, -1)[:, :K]
+    nib = codes.to(torch.int32) + 8
+    packed = (nib[:, 0::2] | (nib[:, 1::2] << 4)).to(torch.uint8)
+    return packed.contiguous(), s.t().contiguous()
+
+
+def w4_unpack(packed, K):
+    """packed uint8 [N, K / 2] -> the codes int8 [N, K] (-7 .. 7; nibble - 8) in column order: w4_quantize's packing undone."""
+    b = packed[:, :K // 2].to(torch.int32)
+    return (torch.stack([b & 15, b >> 4], 2).view(packed.shape[0], K) - 8).to(torch.int8)
+
+
+def w4_dequantize(packed, scales, K):
+    """code * s[group, row], fp32 [N, K]."""
+    s = scales.t().repeat_interleave(W4_GROUP, 1)[:, :K]
+    return w4_unpack(packed, K).float() * s
+
+
 def argmax_rows(logits, ids, seq=None, pos=0):
     B, V = logits.shape
     call("egomi_argmax_rows", P(logits), c_i64(logits.stride(0)), c_i(B), c_i(V), P(ids), P(seq), c_i64(seq.stride(0) if seq is not None else 0),
@@ -288,6 +324,10 @@ class Decoder:
         weight_dtype="fp8": step() runs the four projections of every layer (q|k|v, o_proj, gate|up, down_proj) on e4m3fn codes with one fp32
         scale per output row (W8A16, csrc/w8.hip; self.w8); lm_head, the embeddings and the norms keep the model's dtype, and prefill runs
         on the bf16 weights.  bf16 engines and B <= 512 only; None: the model's weights.
+        weight_dtype="int4": the same four projections on 4-bit codes -7 .. 7 with one fp32 scale per output row and 128-column group,
+        s = amax / 7 (W4A16, csrc/w4.hip; self.w4: per layer (packed uint8 [N, K / 2], scales fp32 [NG, N])): 0.53 of the fp8 bytes at
+        about 4.5 times the weight error.  Same limits and the same bf16 parts as "fp8".  self.wq is the codes step() multiplies (self.w8
+        or self.w4, None on the model's weights) and self.qmm = (product, slab product) their kernels.
         samples_per_prompt = K > 1 (best-of-K sampling; needs max_new_tokens = Tmax): the B rows are K samples of each of B / K prompts,
         row r = b * K + j, on a SplitCache with G = K; step() attends over prompt and suffix with egomi_attn_decode_shared.  sample() /
         greedy() are unchanged: same rows, same seed, same draws as the expanded decoder.
@@ -296,12 +336,12 @@ class Decoder:
         egomi_attn_decode_shared_rows through kv_row[:, S0:] (egomi_beam_update keeps that table as in the dense layout).  beam() is unchanged."""
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', not {kv_dtype!r}")
-        if weight_dtype not in (None, "fp8"):
-            raise ValueError(f"weight_dtype must be None or 'fp8', not {weight_dtype!r}")
-        if weight_dtype == "fp8" and engine.dtype != torch.bfloat16:
-            raise ValueError(f"fp8 decode weights need a bf16 model, not {engine.dtype}")
-        if weight_dtype == "fp8" and B > 512:
-            raise ValueError(f"fp8 decode weights support at most 512 decoder rows, not {B}")
+        if weight_dtype not in (None, "fp8", "int4"):
+            raise ValueError(f"weight_dtype must be None, 'fp8' or 'int4', not {weight_dtype!r}")
+        if weight_dtype is not None and engine.dtype != torch.bfloat16:
+            raise ValueError(f"{weight_dtype} decode weights need a bf16 model, not {engine.dtype}")
+        if weight_dtype is not None and B > 512:
+            raise ValueError(f"{weight_dtype} decode weights support at most 512 decoder rows, not {B}")
         K, nb, G = int(samples_per_prompt), int(num_beams), 1               # G: decoder rows per prompt-cache row
         if K != 1:
             if not 1 < K <= 32:
@@ -358,15 +398,20 @@ class Decoder:
         # round trip of each product through HBM fewer per layer.  Slice counts are the library's plan for these shapes (0 =
         # it would not split: that projection keeps the plain path).  EGOMI_DECODE_FUSED=0 switches the whole thing off (A/B).
         self.fused = {"qkv": 0, "o": 0, "down": 0}
-        self.w8 = None
-        if weight_dtype == "fp8":                           # the fp8 products always leave slabs: their only path
-            self.w8 = self._fp8_weights()
-            q = self.w8[0]
-            self.fused = {"qkv": ops.mm_w8_slabs(self.h, *q["qkv"], self.gws, count_only=True),
-                          "o": ops.mm_w8_slabs(self.ao, *q["o"], self.gws, count_only=True),
-                          "down": ops.mm_w8_slabs(self.act, *q["down"], self.gws, count_only=True)}
+        self.w8 = self.w4 = self.wq = self.qmm = None
+        if weight_dtype is not None:                        # the quantized products always leave slabs: their only path
+            if weight_dtype == "fp8":
+                self.wq = self.w8 = self._fp8_weights()
+                self.qmm = (ops.mm_w8, ops.mm_w8_slabs)
+            else:
+                self.wq = self.w4 = self._int4_weights()
+                self.qmm = (ops.mm_w4, ops.mm_w4_slabs)
+            q, slabs = self.wq[0], self.qmm[1]
+            self.fused = {"qkv": slabs(self.h, *q["qkv"], self.gws, count_only=True),
+                          "o": slabs(self.ao, *q["o"], self.gws, count_only=True),
+                          "down": slabs(self.act, *q["down"], self.gws, count_only=True)}
             if not all(self.fused.values()):
-                raise ValueError(f"fp8 decode weights cannot run this model's projection shapes ({self.fused})")
+                raise ValueError(f"{weight_dtype} decode weights cannot run this model's projection shapes ({self.fused})")
         elif T == torch.bfloat16 and os.environ.get("EGOMI_DECODE_FUSED", "1") != "0" and B <= 512:
             self.fused["qkv"] = ops.mm_slabs(self.h, self.wqkv[0], self.qkv, self.gws, count_only=True)
             self.fused["o"] = ops.mm_slabs(self.ao, w["model.layers.0.self_attn.o_proj.weight"], self.x_mid, self.gws, count_only=True)
@@ -410,14 +455,21 @@ class Decoder:
         """Per layer {"qkv", "o", "gu", "down": (codes uint8 [N, K], scales fp32 [N])} of the stacked forms step() multiplies ([Wq;Wk;Wv],
         [Wgate;Wup] in its interleaved-32 order when engine.gu_il).  Frozen layers: one copy per engine and prepare_epoch, shared by every
         decoder (Engine.prepared = False drops it); trainable layers change under every optimizer step, so each decoder quantizes afresh."""
+        return self._quantized("w8", ops.quantize_rows_fp8)
+
+    def _int4_weights(self):
+        """_fp8_weights for the int4 form: (packed uint8 [N, K / 2], scales fp32 [NG, N]) per projection, cached as engine.w4."""
+        return self._quantized("w4", ops.quantize_rows_int4)
+
+    def _quantized(self, attr, quantize):
         eng = self.eng
-        if eng.w8 is not None and eng.w8[0] == eng.weights_key() and not eng.any_layer_trainable:
-            return eng.w8[1]
-        q = [{"qkv": ops.quantize_rows_fp8(self.wqkv[l]), "o": ops.quantize_rows_fp8(self._w(l, "o")),
-              "gu": ops.quantize_rows_fp8(self.wgu[l]), "down": ops.quantize_rows_fp8(self._w(l, "down"))}
+        held = getattr(eng, attr)
+        if held is not None and held[0] == eng.weights_key() and not eng.any_layer_trainable:
+            return held[1]
+        q = [{"qkv": quantize(self.wqkv[l]), "o": quantize(self._w(l, "o")), "gu": quantize(self.wgu[l]), "down": quantize(self._w(l, "down"))}
              for l in range(len(self.wqkv))]
         if not eng.any_layer_trainable:
-            eng.w8 = (eng.weights_key(), q)
+            setattr(eng, attr, (eng.weights_key(), q))
         return q
 
     def _w(self, l, name):
@@ -428,9 +480,9 @@ class Decoder:
         return self.eng.w[f"model.layers.{l}." + ("self_attn.o_proj.weight" if name == "o" else "mlp.down_proj.weight")]
 
     def _slabs(self, l, name, a, out_like, weight):
-        """The split-K slabs of one projection (fp8 or model-dtype weights) at the start of self.gws; -> their number."""
-        if self.w8 is not None:
-            return ops.mm_w8_slabs(a, *self.w8[l][name], self.gws)
+        """The split-K slabs of one projection (fp8, int4 or model-dtype weights) at the start of self.gws; -> their number."""
+        if self.wq is not None:
+            return self.qmm[1](a, *self.wq[l][name], self.gws)
         return ops.mm_slabs(a, weight, out_like, self.gws)
 
     # -- prefill -------------------------------------------------------------------------------------
@@ -503,8 +555,8 @@ class Decoder:
                 n = self._slabs(l, "qkv", self.h, self.qkv, self.wqkv[l])
                 self.cache.qkv_finish(l, self.gws, n, self.qkv, eng.cos, eng.sin, pos)
             else:
-                if self.w8 is not None:                     # (prompt / suffix cache: the only unfused q|k|v product on fp8 weights)
-                    ops.mm_w8(self.h, *self.w8[l]["qkv"], out=self.qkv, workspace=self.gws)
+                if self.wq is not None:                     # (prompt / suffix cache: the only unfused q|k|v product on quantized weights)
+                    self.qmm[0](self.h, *self.wq[l]["qkv"], out=self.qkv, workspace=self.gws)
                 else:
                     ops.mm(self.h, self.wqkv[l], out=self.qkv, workspace=self.gws)
                 ops.rope_(self.qkv, eng.cos, eng.sin, B, 1, pos, 2 * H, hd, 3 * d)
@@ -516,8 +568,8 @@ class Decoder:
             else:
                 ops.mm(self.ao, self._w(l, "o"), out=self.x_mid, residual=x, workspace=self.gws)
                 ops.rmsnorm(self.x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, out=self.h2)
-            if self.w8 is not None:
-                ops.mm_w8(self.h2, *self.w8[l]["gu"], out=self.gu, workspace=self.gws)
+            if self.wq is not None:
+                self.qmm[0](self.h2, *self.wq[l]["gu"], out=self.gu, workspace=self.gws)
             else:
                 ops.mm(self.h2, self.wgu[l], out=self.gu, workspace=self.gws)
             if eng.gu_il:

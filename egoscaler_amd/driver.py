@@ -461,9 +461,10 @@ def parse_args(argv=None):
                          "FDE_sel to the record and the picked index per image id to the dump")
     ap.add_argument("--kv_cache_dtype", default="auto", choices=["auto", "fp8"],
                     help="KV cache of every generate() call in validation / eval: the model's dtype (auto) or e4m3fn codes with per-(token, head) scales")
-    ap.add_argument("--decode_weight_dtype", default="auto", choices=["auto", "fp8"],
-                    help="weights of the decode-step projections of every generate() call in validation / eval: the model's (auto) or "
-                         "e4m3fn codes with per-output-row scales (bf16 models; prefill stays bf16)")
+    ap.add_argument("--decode_weight_dtype", default="auto", choices=["auto", "fp8", "int4"],
+                    help="weights of the decode-step projections of every generate() call in validation / eval: the model's (auto), "
+                         "e4m3fn codes with per-output-row scales (fp8) or 4-bit codes with per-row scales over 128-column groups (int4); "
+                         "bf16 models, prefill stays bf16")
     ap.add_argument("--root_dir", default=None, help="EgoScaler data root (pcrgbs/, trajs/ ...: dataset.py:36, dataset_base.py:68-103)")
     ap.add_argument("--data_dir", default=None, help="directory of the split files {train,val,test}.json (dataset.py:37)")
     ap.add_argument("--smooth_traj", action="store_true", help="smoothing_traj on the resampled tracks (dataset.py:39 reads this attribute)")

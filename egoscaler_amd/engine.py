@@ -47,6 +47,7 @@ class Engine:
         self.dims, self.w, self.device, self.dtype = dims, params, device, dtype
         self.ws = Workspace(device)
         self.w8 = None                 # (prepare_epoch, fp8 codes / scales of the decode projections): decode.Decoder(weight_dtype="fp8")
+        self.w4 = None                 # the same for the int4 codes / group scales: decode.Decoder(weight_dtype="int4")
         self.prepared = False
         self.prepare_epoch = 0         # bumped by prepare(): holders of derived weight copies (decode.Decoder caches) key on it
         self.lm_wT, self.lm_wT_stale, self.lm_wT_ver = None, True, None     # padded transpose of lm_head for its dgrad (backward_logits)
@@ -188,7 +189,7 @@ class Engine:
     def prepared(self, v):
         self._prepared = v
         if not v:
-            self.w8 = None             # every path that marks the weights stale drops the fp8 copies derived from them
+            self.w8 = self.w4 = None   # every path that marks the weights stale drops the fp8 / int4 copies derived from them
 
     def prepare(self):
         """One-time derived weights: BatchNorm fold (fold_batchnorm), resident transposes / stacks of the decoder weights, RoPE tables."""

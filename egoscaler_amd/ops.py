@@ -363,6 +363,52 @@ def mm_w8_slabs(x, codes, scales, workspace, count_only=False):
     return n
 
 
+# ------------------------------------------------------------------------------------------ int4 weights (decode projections)
+def quantize_rows_int4(w):
+    """bf16 rows w [N, K], K % 32 == 0 -> (packed uint8 [N, K / 2], scales fp32 [ceil(K / 128), N]): per row and 128-column group
+    s = amax / 7 (1 where amax == 0), code = clamp(round(w / s), -7, 7), two codes per byte (column 2 b low, 2 b + 1 high)
+    (egomi_quantize_rows_int4; bit-equal to decode.w4_quantize run on the host)."""
+    if w.dtype != torch.bfloat16:
+        raise TypeError("quantize_rows_int4 takes bf16 rows")
+    N, K = w.shape
+    packed = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(-(-K // 128), N, dtype=torch.float32, device=w.device)
+    call("egomi_quantize_rows_int4", P(w), c_i64(_ld(w)), c_i(N), c_i(K), P(packed), c_i64(K // 2), P(scales), S())
+    return packed, scales
+
+
+def _w4(x, packed, scales, out, residual, workspace, epilogue):
+    M, K = x.shape
+    N = packed.shape[0]
+    if x.dtype != torch.bfloat16 or packed.dtype != torch.uint8 or scales.dtype != torch.float32 or packed.shape[1] * 2 != K \
+            or scales.shape != (-(-K // 128), N) or not scales.is_contiguous():
+        raise TypeError("mm_w4: x bf16 [M, K], packed uint8 [N, K / 2], scales fp32 [ceil(K / 128), N] contiguous")
+    call("egomi_gemm_w4", P(x), c_i64(_ld(x)), P(packed), c_i64(_ld(packed)), P(scales), P(out), c_i64(_ld(out) if out is not None else 0),
+         P(residual), c_i64(_ld(residual) if residual is not None else 0), c_i(M), c_i(N), c_i(K), c_i(epilogue), P(workspace),
+         c_i64(workspace.numel() * workspace.element_size() if workspace is not None else 0), S())
+
+
+def mm_w4(x, packed, scales, out=None, residual=None, workspace=None):
+    """out = bf16(x . dequantized(packed, scales)^T (+ residual)): x bf16 [M, K] with M <= 512, int4 weights from quantize_rows_int4
+    (egomi_gemm_w4, EGOMI_EPI_NONE; `workspace` lets the library split K)."""
+    if out is None:
+        out = torch.empty(x.shape[0], packed.shape[0], dtype=torch.bfloat16, device=x.device)
+    _w4(x, packed, scales, out, residual, workspace, 0)
+    return out
+
+
+def mm_w4_slabs(x, packed, scales, workspace, count_only=False):
+    """mm_w4's product as UNSUMMED fp32 K-slice slabs [slices, M, N] at the start of `workspace` (egomi_gemm_w4, EGOMI_EPI_SLABS);
+    returns the number of slices (count_only: without launching; 0 = the library cannot run this shape)."""
+    M, K = x.shape
+    N = packed.shape[0]
+    n = _lib.lib().egomi_gemm_w4_slab_count(c_i(M), c_i(N), c_i(K), c_i64(workspace.numel() * workspace.element_size()))
+    if count_only:
+        return n
+    _w4(x, packed, scales, None, None, workspace, 2)
+    return n
+
+
 # ------------------------------------------------------------------------------------------ rows
 def layernorm(x, w, b, eps=1e-5, add=None, sum_out=None, out=None):
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]

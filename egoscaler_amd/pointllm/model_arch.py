@@ -268,7 +268,7 @@ class TrajPointLLMForCausalLM(nn.Module):
 
     def _adapters_changed(self):
         self.engine.lora_version += 1
-        self.engine.w8 = None
+        self.engine.w8 = self.engine.w4 = None
 
     def save_lora(self, path):
         """The adapters in PEFT's save_pretrained layout: adapter_config.json and adapter_model.safetensors (keys
@@ -597,7 +597,10 @@ class TrajPointLLMForCausalLM(nn.Module):
         (decode.Decoder(weight_dtype="fp8"), csrc/w8.hip): half the weight bytes every decode step streams.  lm_head, the embeddings and the
         norms keep the model's dtype.  Applies to every mode and either kv_cache_dtype; bf16 models with at most 512 decoder rows
         (batch x num_beams) only.  The prefill runs on the bf16 weights, so the prefill logits (step 0) are those of the bf16 run; only
-        the later steps read the fp8 weights.
+        the later steps read the fp8 weights.  "int4" = the same four projections on symmetric 4-bit codes (-7 .. 7) with one fp32 scale per
+        output row and 128-column group, s = amax / 7, W4A16 (decode.Decoder(weight_dtype="int4"), csrc/w4.hip): 0.53 of the fp8 form's
+        weight bytes per step, with about 4.5 times its weight error (11.7 % against 2.6 % on Gaussian weights; the accuracy on a trained
+        checkpoint is not measured).  Accepted wherever "fp8" is, under the same limits.
 
         share_prompt=True with num_return_sequences = K > 1 and num_beams == 1 (best-of-K sampling): same outputs, shapes and row order
         (row b * K + j = sample j of prompt b) as the default, but every prompt is prefilled ONCE and its K/V are kept once: the decoder holds
@@ -655,9 +658,9 @@ class TrajPointLLMForCausalLM(nn.Module):
         if kv_cache_dtype not in (None, "auto", "fp8"):
             raise ValueError(f"`kv_cache_dtype` must be None, 'auto' or 'fp8', but is {kv_cache_dtype!r}")
         kv = "fp8" if kv_cache_dtype == "fp8" else None
-        if decode_weight_dtype not in (None, "auto", "fp8"):
-            raise ValueError(f"`decode_weight_dtype` must be None, 'auto' or 'fp8', but is {decode_weight_dtype!r}")
-        wd = "fp8" if decode_weight_dtype == "fp8" else None
+        if decode_weight_dtype not in (None, "auto", "fp8", "int4"):
+            raise ValueError(f"`decode_weight_dtype` must be None, 'auto', 'fp8' or 'int4', but is {decode_weight_dtype!r}")
+        wd = decode_weight_dtype if decode_weight_dtype in ("fp8", "int4") else None
         eng = self.engine
         eng.wait_param_updates()                           # the decoder reads the weights outside the engine's forward pass
         dev = eng.device

@@ -413,6 +413,24 @@ int egomi_gemm_w8(const void* x, int64_t ldx, const uint8_t* codes, int64_t ldw,
                   egomi_stream_t stream);
 int egomi_gemm_w8_slab_count(int M, int N, int K, int64_t workspace_bytes);
 
+/* Int4 weights with group scales of the single-token decode projections, W4A16 (csrc/w4.hip; its header is the normative statement).
+ * Replaces the same bf16 products as the fp8 form above (HF LlamaAttention / LlamaMLP forward, modeling_llama.py:243-281,174-176, in the
+ * generate() step of models/pointllm/model_arch.py:77-108 / pointllm/model/pointllm.py:255-275).  Group g of a row is its columns
+ * [128 g, min(K, 128 g + 128)), NG = ceil(K / 128); s[g,n] = amax / 7.0f (1 when amax == 0), code = clamp(rintf(W / s), -7, 7), stored as
+ * the nibble code + 8: byte b of a row holds column 2 b in its low nibble and column 2 b + 1 in its high nibble (16 bytes per 32 columns).
+ *   quantize_rows_int4: bf16 rows w [N, K] (row stride ldw, K % 32 == 0) -> packed codes uint8 [N, K / 2] (row stride ldc bytes, ldc % 4
+ *                      == 0), scales fp32 [NG, N] (group-major, contiguous); bit-equal to decode.w4_quantize on the host.
+ *   gemm_w4          : y[m,n] = sum_g s[g,n] * (sum_{k in g} x[m,k] * code[n,k]); x bf16 [M, K] (ldx % 8 == 0, 16-B aligned), packed codes
+ *                      (ldw bytes, ldw % 16 == 0, 16-B aligned), scales 16-B aligned; fp32 accumulation in a fixed order, a group's sum is
+ *                      finished before its scale is applied.  Shapes, epilogues (EGOMI_EPI_NONE with optional residual and workspace,
+ *                      EGOMI_EPI_SLABS), the slabs' layout and the error codes are egomi_gemm_w8's; a repeated call writes the same bits.
+ *   gemm_w4_slab_count: the number of slabs egomi_gemm_w4 writes with EGOMI_EPI_SLABS for this shape and workspace (0: it cannot run it). */
+int egomi_quantize_rows_int4(const void* w, int64_t ldw, int N, int K, uint8_t* codes, int64_t ldc, float* scales, egomi_stream_t stream);
+int egomi_gemm_w4(const void* x, int64_t ldx, const uint8_t* codes, int64_t ldw, const float* scales, void* out, int64_t ldo,
+                  const void* residual, int64_t ldr, int M, int N, int K, int epilogue, void* workspace, int64_t workspace_bytes,
+                  egomi_stream_t stream);
+int egomi_gemm_w4_slab_count(int M, int N, int K, int64_t workspace_bytes);
+
 /* LoRA adapters on the decoder projections (csrc/lora.hip): the low-rank products of PEFT's lora.Linear.forward (peft/tuners/lora/layer.py:
  * result = base_layer(x) + lora_B(lora_A(x)) * scaling, scaling = lora_alpha / r; no dropout, no bias) and of its backward.  For one adapted
  * projection with A [r, K], B [N, r] and s = lora_alpha / r: T = x A^T, y += s T B^T; U = dY B, dX += s U A, dA = s U^T x, dB = s dY^T T;
