@@ -23,14 +23,15 @@
 // G at 24 |sum x| instead of |G|: on the tiny model one such flipped bf16 rounding in o_proj moved the logits by 2.5e-3 against a bf16
 // decoder on the dequantized weights, where this form is bit-equal to it.)
 //
-// gemm_w4_kernel: gemm_w8_kernel's structure.  A block = 4 waves on the same 64 weight rows and 16 * MT activation rows (MT = 1 for
+// wq_w4_kernel: wq_w8_kernel's structure (w8.hip).  A block = 4 waves on the same 64 weight rows and 16 * MT activation rows (MT = 1 for
 // M <= 16, else 2: an M-chunk); the K range is cut over splitk slices x 4 waves in steps of 128 = one scale group, so slot boundaries are
 // group boundaries.  Per step a lane reads ONE 16-byte block of each of its 4 weight rows (the 4 lanes of a row: 64 contiguous bytes) and
 // the 16 bytes of its rows' scales straight into registers, with the next step's loads in flight under the current MFMAs.  Lane group
 // grp = lane >> 4 owns unit 4 c + grp of step c: columns 128 c + 32 grp + 8 p + e meet element e of MFMA p in the weight and in the
 // activation fragment alike.  The last slot takes the K % 128 tail as one more step in which lane groups past the tail multiply zeros.
 // The 4 waves meet in LDS (fixed order) and the block writes bf16 rows (+ residual) or its fp32 K-slice slab.
-#include "common.h"
+// The arguments, the plan, the slab count, the reduce kernel of a planned split and the host entry are wq_gemm.h's, shared with w8.hip.
+#include "wq_gemm.h"
 #include <math.h>
 
 // ------------------------------------------------------------------------------------------------
@@ -77,15 +78,6 @@ extern "C" int egomi_quantize_rows_int4(const void* w, int64_t ldw, int N, int K
 // ------------------------------------------------------------------------------------------------
 // gemm_w4
 // ------------------------------------------------------------------------------------------------
-#define W4_BN 64
-
-struct W4Args {
-    const bf16_t* x; const uint8_t* w; const float* s; bf16_t* out; const bf16_t* res; float* ws;
-    long long ldx, ldw, ldo, ldr;
-    int M, N, K;
-    int splitk, mch, items, per_xcd;
-};
-
 // one packed word -> its 8 columns as bf16 (exact), in column order
 __device__ __forceinline__ bf16x8 w4_decode8(uint32_t c) {
     const uint32_t ev = c & 0x0F0F0F0Fu, od = (c >> 4) & 0x0F0F0F0Fu;   // bytes = the nibbles of columns 0, 2, 4, 6 / 1, 3, 5, 7
@@ -100,8 +92,8 @@ __device__ __forceinline__ bf16x8 w4_decode8(uint32_t c) {
 }
 
 template <int MT>
-__global__ __launch_bounds__(256) void gemm_w4_kernel(W4Args g) {
-    __shared__ float red[4][W4_BN][16 * MT + 1];
+__global__ __launch_bounds__(256) void wq_w4_kernel(WqArgs g) {
+    __shared__ float red[4][WQ_BN][16 * MT + 1];
     const int item = (int)(blockIdx.x & 7) * g.per_xcd + (int)(blockIdx.x >> 3);    // dispatch round-robins XCDs: item-major per XCD
     if (item >= g.items) return;
     const int mc = item % g.mch, rest = item / g.mch;
@@ -109,7 +101,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(W4Args g) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nl = lane & 15, grp = lane >> 4;
-    const int n0 = nt * W4_BN, m0 = mc * 16 * MT;
+    const int n0 = nt * WQ_BN, m0 = mc * 16 * MT;
     const int U = g.K >> 5, C = U >> 2;                                  // 32-deep units, whole 128-deep steps = whole groups
     const int slot = slice * 4 + wave, nslots = g.splitk * 4;
     // slots own whole steps; the last one also takes the ragged last group (U % 4 units)
@@ -230,81 +222,16 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(W4Args g) {
     }
 }
 
-// planned split of an EGOMI_EPI_NONE product: out = bf16(sum of the slabs in slice order (+ residual))
-__global__ __launch_bounds__(256) void gemm_w4_reduce_kernel(W4Args g) {
-    const long long total = (long long)g.M * (g.N / 4);
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int m = (int)(e / (g.N / 4)), n = (int)(e % (g.N / 4)) * 4;
-        f32x4 v = *reinterpret_cast<const f32x4*>(g.ws + (long long)m * g.N + n);
-        for (int s2 = 1; s2 < g.splitk; ++s2) v += *reinterpret_cast<const f32x4*>(g.ws + ((long long)s2 * g.M + m) * g.N + n);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float y = g.res ? v[k] + bf2f(g.res[(long long)m * g.ldr + n + k]) : v[k];
-            g.out[(long long)m * g.ldo + n + k] = f2bf(y);
-        }
-    }
-}
+struct W4Codec {
+    static constexpr int CODES_PER_BYTE = 2;
+    static constexpr uintptr_t SCALE_ALIGN_MASK = 15;                    // the scales are read 16 bytes at a time
+    static constexpr auto kernel1 = &wq_w4_kernel<1>, kernel2 = &wq_w4_kernel<2>;
+};
 
-struct W4Plan { int mt, mch, tiles_n, splitk; };
-
-// The one plan of a product: egomi_gemm_w4_slab_count and egomi_gemm_w4 both read it, so the count a caller is told is the count the
-// launch writes.  -> EGOMI_OK or EGOMI_E_UNSUPPORTED.
-static int w4_plan(int M, int N, int K, int epilogue, int64_t ws_bytes, W4Plan& p) {
-    if (M < 1 || M > 512 || N < 4 || (N & 3) || K < 32 || (K & 31)) return EGOMI_E_UNSUPPORTED;
-    p.mt = M <= 16 ? 1 : 2;
-    p.mch = (M + 16 * p.mt - 1) / (16 * p.mt);
-    p.tiles_n = (N + W4_BN - 1) / W4_BN;
-    const long long blocks = (long long)p.tiles_n * p.mch;
-    // ~700 blocks of 4 waves (gemm_w8's plan), every wave at least one 128-deep step
-    int sk = (int)((704 + blocks / 2) / blocks);
-    const int sk_max = (K / 32) / 16;
-    if (sk > sk_max) sk = sk_max;
-    if (sk < 1) sk = 1;
-    const long long per_slab = (long long)M * N * 4;
-    if ((long long)sk * per_slab > ws_bytes) sk = (int)(ws_bytes / per_slab);
-    if (epilogue == EGOMI_EPI_SLABS) {
-        if (sk < 1) return EGOMI_E_UNSUPPORTED;                          // not even one slab fits the workspace
-    } else if (sk < 2) {
-        sk = 1;                                                          // no split: no workspace needed
-    }
-    if ((long long)p.tiles_n * sk * p.mch > 0x7FFFFFF8ll) return EGOMI_E_UNSUPPORTED;
-    p.splitk = sk;
-    return EGOMI_OK;
-}
-
-extern "C" int egomi_gemm_w4_slab_count(int M, int N, int K, int64_t workspace_bytes) {
-    W4Plan p;
-    return w4_plan(M, N, K, EGOMI_EPI_SLABS, workspace_bytes, p) == EGOMI_OK ? p.splitk : 0;
-}
+extern "C" int egomi_gemm_w4_slab_count(int M, int N, int K, int64_t workspace_bytes) { return wq_slab_count(M, N, K, workspace_bytes); }
 
 extern "C" int egomi_gemm_w4(const void* x, int64_t ldx, const uint8_t* codes, int64_t ldw, const float* scales, void* out, int64_t ldo,
                              const void* residual, int64_t ldr, int M, int N, int K, int epilogue, void* workspace, int64_t workspace_bytes,
                              egomi_stream_t stream) {
-    if (!x || !codes || !scales) return EGOMI_E_BADARG;
-    if (epilogue != EGOMI_EPI_NONE && epilogue != EGOMI_EPI_SLABS) return EGOMI_E_UNSUPPORTED;
-    if (epilogue == EGOMI_EPI_NONE && !out) return EGOMI_E_BADARG;
-    if (epilogue == EGOMI_EPI_SLABS && (!workspace || residual)) return EGOMI_E_BADARG;
-    if (M <= 0 || N <= 0 || K <= 0 || ldx < K || ldw < K / 2 || workspace_bytes < 0) return EGOMI_E_SHAPE;
-    if (epilogue == EGOMI_EPI_NONE && (ldo < N || (residual && ldr < N))) return EGOMI_E_SHAPE;
-    if (((uintptr_t)x & 15) || (ldx & 7) || ((uintptr_t)codes & 15) || (ldw & 15) || ((uintptr_t)scales & 15) || ((uintptr_t)workspace & 15))
-        return EGOMI_E_SHAPE;
-    W4Plan p;
-    if (const int rc = w4_plan(M, N, K, epilogue, workspace ? workspace_bytes : 0, p)) return rc;
-    W4Args g;
-    g.x = (const bf16_t*)x; g.w = codes; g.s = scales; g.out = (bf16_t*)out; g.res = (const bf16_t*)residual;
-    g.ws = (epilogue == EGOMI_EPI_SLABS || p.splitk > 1) ? (float*)workspace : nullptr;
-    g.ldx = ldx; g.ldw = ldw; g.ldo = ldo; g.ldr = ldr;
-    g.M = M; g.N = N; g.K = K;
-    g.splitk = p.splitk; g.mch = p.mch;
-    g.items = p.tiles_n * p.splitk * p.mch;
-    g.per_xcd = (g.items + 7) / 8;
-    hipStream_t st = (hipStream_t)stream;
-    if (p.mt == 1) EGOMI_LAUNCH(gemm_w4_kernel<1>, dim3(8 * g.per_xcd), dim3(256), 0, st, g);
-    else EGOMI_LAUNCH(gemm_w4_kernel<2>, dim3(8 * g.per_xcd), dim3(256), 0, st, g);
-    if (epilogue == EGOMI_EPI_NONE && p.splitk > 1) {
-        const long long total = (long long)M * (N / 4);
-        const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        EGOMI_LAUNCH(gemm_w4_reduce_kernel, dim3(grid), dim3(256), 0, st, g);
-    }
-    return egomi_launch_status();
+    return wq_gemm<W4Codec>(x, ldx, codes, ldw, scales, out, ldo, residual, ldr, M, N, K, epilogue, workspace, workspace_bytes, stream);
 }

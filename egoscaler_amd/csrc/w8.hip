@@ -9,14 +9,15 @@
 // to the scaled product).  Every e4m3fn value is exact in bf16, so the codes are decoded to bf16 in registers (v_cvt_pk_f32_fp8, then
 // v_cvt_pk_bf16_f32) and multiplied on v_mfma_f32_16x16x32_bf16: every product is exact, as in the bf16 kernel.
 //
-// gemm_w8_kernel: gemv_m16_kernel's structure (gemm_fast.hip) with byte-wide weights.  A block = 4 waves on the same 64 weight rows and
+// wq_w8_kernel: gemv_m16_kernel's structure (gemm_fast.hip) with byte-wide weights.  A block = 4 waves on the same 64 weight rows and
 // 16 * MT activation rows (MT = 1 for M <= 16, else 2: an M-chunk); the K range is cut over splitk slices x 4 waves in steps of 128.  Per
 // 128-deep step a lane reads 2 x 16 B of each of its 4 weight rows (the 4 lanes of a row: 64 contiguous bytes per load instruction)
 // straight into registers, with the next step's loads in flight under the current MFMAs.  A lane's K positions within a step are
 // {16 grp .. 16 grp + 15} and {64 + 16 grp .. 64 + 16 grp + 15}; the activation fragment uses the same map, so every k meets its own k.
 // The 4 waves meet in LDS (fixed order) and the block writes bf16 rows (+ residual) or its fp32 K-slice slab.  M > 16: the blocks of one
 // weight tile (its M-chunks) are consecutive work items on one XCD, so the tile crosses HBM once and the other chunks read it from L2.
-#include "common.h"
+// The arguments, the plan, the slab count, the reduce kernel of a planned split and the host entry are wq_gemm.h's, shared with w4.hip.
+#include "wq_gemm.h"
 #include "fp8.h"
 #include <math.h>
 
@@ -46,15 +47,6 @@ extern "C" int egomi_quantize_rows_fp8(const void* w, int64_t ldw, int N, int K,
 // ------------------------------------------------------------------------------------------------
 // gemm_w8
 // ------------------------------------------------------------------------------------------------
-#define W8_BN 64
-
-struct W8Args {
-    const bf16_t* x; const uint8_t* w; const float* s; bf16_t* out; const bf16_t* res; float* ws;
-    long long ldx, ldw, ldo, ldr;
-    int M, N, K;
-    int splitk, mch, items, per_xcd;
-};
-
 // 8 codes -> 8 bf16 (exact)
 __device__ __forceinline__ bf16x8 w8_decode8(uint32_t lo, uint32_t hi) {
     float f[8];
@@ -67,8 +59,8 @@ __device__ __forceinline__ bf16x8 w8_decode8(uint32_t lo, uint32_t hi) {
 }
 
 template <int MT>
-__global__ __launch_bounds__(256) void gemm_w8_kernel(W8Args g) {
-    __shared__ float red[4][W8_BN][16 * MT + 1];
+__global__ __launch_bounds__(256) void wq_w8_kernel(WqArgs g) {
+    __shared__ float red[4][WQ_BN][16 * MT + 1];
     const int item = (int)(blockIdx.x & 7) * g.per_xcd + (int)(blockIdx.x >> 3);    // dispatch round-robins XCDs: item-major per XCD
     if (item >= g.items) return;
     const int mc = item % g.mch, rest = item / g.mch;
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(256) void gemm_w8_kernel(W8Args g) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nl = lane & 15, grp = lane >> 4;
-    const int n0 = nt * W8_BN, m0 = mc * 16 * MT;
+    const int n0 = nt * WQ_BN, m0 = mc * 16 * MT;
     const int U = g.K >> 5, C = U >> 2;                                  // 32-deep units, whole 128-deep steps
     const int slot = slice * 4 + wave, nslots = g.splitk * 4;
     // slots own whole steps; the last one also takes the U % 4 single units
@@ -185,80 +177,16 @@ __global__ __launch_bounds__(256) void gemm_w8_kernel(W8Args g) {
     }
 }
 
-// planned split of an EGOMI_EPI_NONE product: out = bf16(sum of the slabs in slice order (+ residual))
-__global__ __launch_bounds__(256) void gemm_w8_reduce_kernel(W8Args g) {
-    const long long total = (long long)g.M * (g.N / 4);
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int m = (int)(e / (g.N / 4)), n = (int)(e % (g.N / 4)) * 4;
-        f32x4 v = *reinterpret_cast<const f32x4*>(g.ws + (long long)m * g.N + n);
-        for (int s2 = 1; s2 < g.splitk; ++s2) v += *reinterpret_cast<const f32x4*>(g.ws + ((long long)s2 * g.M + m) * g.N + n);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float y = g.res ? v[c] + bf2f(g.res[(long long)m * g.ldr + n + c]) : v[c];
-            g.out[(long long)m * g.ldo + n + c] = f2bf(y);
-        }
-    }
-}
+struct W8Codec {
+    static constexpr int CODES_PER_BYTE = 1;
+    static constexpr uintptr_t SCALE_ALIGN_MASK = 0;                     // the scales are read one float at a time
+    static constexpr auto kernel1 = &wq_w8_kernel<1>, kernel2 = &wq_w8_kernel<2>;
+};
 
-struct W8Plan { int mt, mch, tiles_n, splitk; };
-
-// The one plan of a product: egomi_gemm_w8_slab_count and egomi_gemm_w8 both read it, so the count a caller is told is the count the
-// launch writes.  -> EGOMI_OK or EGOMI_E_UNSUPPORTED.
-static int w8_plan(int M, int N, int K, int epilogue, int64_t ws_bytes, W8Plan& p) {
-    if (M < 1 || M > 512 || N < 4 || (N & 3) || K < 32 || (K & 31)) return EGOMI_E_UNSUPPORTED;
-    p.mt = M <= 16 ? 1 : 2;
-    p.mch = (M + 16 * p.mt - 1) / (16 * p.mt);
-    p.tiles_n = (N + W8_BN - 1) / W8_BN;
-    const long long blocks = (long long)p.tiles_n * p.mch;
-    // ~700 blocks of 4 waves (gemv_m16_kernel's measured sweet spot at M = 8), every wave at least one 128-deep step
-    int sk = (int)((704 + blocks / 2) / blocks);
-    const int sk_max = (K / 32) / 16;
-    if (sk > sk_max) sk = sk_max;
-    if (sk < 1) sk = 1;
-    const long long per_slab = (long long)M * N * 4;
-    if ((long long)sk * per_slab > ws_bytes) sk = (int)(ws_bytes / per_slab);
-    if (epilogue == EGOMI_EPI_SLABS) {
-        if (sk < 1) return EGOMI_E_UNSUPPORTED;                          // not even one slab fits the workspace
-    } else if (sk < 2) {
-        sk = 1;                                                          // no split: no workspace needed
-    }
-    if ((long long)p.tiles_n * sk * p.mch > 0x7FFFFFF8ll) return EGOMI_E_UNSUPPORTED;
-    p.splitk = sk;
-    return EGOMI_OK;
-}
-
-extern "C" int egomi_gemm_w8_slab_count(int M, int N, int K, int64_t workspace_bytes) {
-    W8Plan p;
-    return w8_plan(M, N, K, EGOMI_EPI_SLABS, workspace_bytes, p) == EGOMI_OK ? p.splitk : 0;
-}
+extern "C" int egomi_gemm_w8_slab_count(int M, int N, int K, int64_t workspace_bytes) { return wq_slab_count(M, N, K, workspace_bytes); }
 
 extern "C" int egomi_gemm_w8(const void* x, int64_t ldx, const uint8_t* codes, int64_t ldw, const float* scales, void* out, int64_t ldo,
                              const void* residual, int64_t ldr, int M, int N, int K, int epilogue, void* workspace, int64_t workspace_bytes,
                              egomi_stream_t stream) {
-    if (!x || !codes || !scales) return EGOMI_E_BADARG;
-    if (epilogue != EGOMI_EPI_NONE && epilogue != EGOMI_EPI_SLABS) return EGOMI_E_UNSUPPORTED;
-    if (epilogue == EGOMI_EPI_NONE && !out) return EGOMI_E_BADARG;
-    if (epilogue == EGOMI_EPI_SLABS && (!workspace || residual)) return EGOMI_E_BADARG;
-    if (M <= 0 || N <= 0 || K <= 0 || ldx < K || ldw < K || workspace_bytes < 0) return EGOMI_E_SHAPE;
-    if (epilogue == EGOMI_EPI_NONE && (ldo < N || (residual && ldr < N))) return EGOMI_E_SHAPE;
-    if (((uintptr_t)x & 15) || (ldx & 7) || ((uintptr_t)codes & 15) || (ldw & 15) || ((uintptr_t)workspace & 15)) return EGOMI_E_SHAPE;
-    W8Plan p;
-    if (const int rc = w8_plan(M, N, K, epilogue, workspace ? workspace_bytes : 0, p)) return rc;
-    W8Args g;
-    g.x = (const bf16_t*)x; g.w = codes; g.s = scales; g.out = (bf16_t*)out; g.res = (const bf16_t*)residual;
-    g.ws = (epilogue == EGOMI_EPI_SLABS || p.splitk > 1) ? (float*)workspace : nullptr;
-    g.ldx = ldx; g.ldw = ldw; g.ldo = ldo; g.ldr = ldr;
-    g.M = M; g.N = N; g.K = K;
-    g.splitk = p.splitk; g.mch = p.mch;
-    g.items = p.tiles_n * p.splitk * p.mch;
-    g.per_xcd = (g.items + 7) / 8;
-    hipStream_t st = (hipStream_t)stream;
-    if (p.mt == 1) EGOMI_LAUNCH(gemm_w8_kernel<1>, dim3(8 * g.per_xcd), dim3(256), 0, st, g);
-    else EGOMI_LAUNCH(gemm_w8_kernel<2>, dim3(8 * g.per_xcd), dim3(256), 0, st, g);
-    if (epilogue == EGOMI_EPI_NONE && p.splitk > 1) {
-        const long long total = (long long)M * (N / 4);
-        const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        EGOMI_LAUNCH(gemm_w8_reduce_kernel, dim3(grid), dim3(256), 0, st, g);
-    }
-    return egomi_launch_status();
+    return wq_gemm<W8Codec>(x, ldx, codes, ldw, scales, out, ldo, residual, ldr, M, N, K, epilogue, workspace, workspace_bytes, stream);
 }

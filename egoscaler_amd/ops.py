@@ -332,14 +332,30 @@ def quantize_rows_fp8(w):
     return codes, scales
 
 
-def _w8(x, codes, scales, out, residual, workspace, epilogue):
+def _wq_launch(sym, x, codes, scales, out, residual, workspace, epilogue):
+    """egomi_gemm_w8 / egomi_gemm_w4 (one argument list: csrc/wq_gemm.h) on operands the format's caller has checked."""
     M, K = x.shape
     N = codes.shape[0]
-    if x.dtype != torch.bfloat16 or codes.dtype != torch.uint8 or scales.dtype != torch.float32 or codes.shape[1] != K or scales.shape != (N,):
-        raise TypeError("mm_w8: x bf16 [M, K], codes uint8 [N, K], scales fp32 [N]")
-    call("egomi_gemm_w8", P(x), c_i64(_ld(x)), P(codes), c_i64(_ld(codes)), P(scales), P(out), c_i64(_ld(out) if out is not None else 0),
+    call(sym, P(x), c_i64(_ld(x)), P(codes), c_i64(_ld(codes)), P(scales), P(out), c_i64(_ld(out) if out is not None else 0),
          P(residual), c_i64(_ld(residual) if residual is not None else 0), c_i(M), c_i(N), c_i(K), c_i(epilogue), P(workspace),
          c_i64(workspace.numel() * workspace.element_size() if workspace is not None else 0), S())
+
+
+def _wq_slabs(launch, count_sym, x, codes, scales, workspace, count_only):
+    """The slab path of either format: the library's count for this shape and workspace, then (unless count_only) the launch."""
+    M, K = x.shape
+    N = codes.shape[0]
+    n = getattr(_lib.lib(), count_sym)(c_i(M), c_i(N), c_i(K), c_i64(workspace.numel() * workspace.element_size()))
+    if not count_only:
+        launch(x, codes, scales, None, None, workspace, 2)
+    return n
+
+
+def _w8(x, codes, scales, out, residual, workspace, epilogue):
+    K, N = x.shape[1], codes.shape[0]
+    if x.dtype != torch.bfloat16 or codes.dtype != torch.uint8 or scales.dtype != torch.float32 or codes.shape[1] != K or scales.shape != (N,):
+        raise TypeError("mm_w8: x bf16 [M, K], codes uint8 [N, K], scales fp32 [N]")
+    _wq_launch("egomi_gemm_w8", x, codes, scales, out, residual, workspace, epilogue)
 
 
 def mm_w8(x, codes, scales, out=None, residual=None, workspace=None):
@@ -354,13 +370,7 @@ def mm_w8(x, codes, scales, out=None, residual=None, workspace=None):
 def mm_w8_slabs(x, codes, scales, workspace, count_only=False):
     """x . (codes * scales[:, None])^T as UNSUMMED fp32 K-slice slabs [slices, M, N] at the start of `workspace` (egomi_gemm_w8,
     EGOMI_EPI_SLABS); returns the number of slices (count_only: without launching; 0 = the library cannot run this shape)."""
-    M, K = x.shape
-    N = codes.shape[0]
-    n = _lib.lib().egomi_gemm_w8_slab_count(c_i(M), c_i(N), c_i(K), c_i64(workspace.numel() * workspace.element_size()))
-    if count_only:
-        return n
-    _w8(x, codes, scales, None, None, workspace, 2)
-    return n
+    return _wq_slabs(_w8, "egomi_gemm_w8_slab_count", x, codes, scales, workspace, count_only)
 
 
 # ------------------------------------------------------------------------------------------ int4 weights (decode projections)
@@ -378,14 +388,11 @@ def quantize_rows_int4(w):
 
 
 def _w4(x, packed, scales, out, residual, workspace, epilogue):
-    M, K = x.shape
-    N = packed.shape[0]
+    K, N = x.shape[1], packed.shape[0]
     if x.dtype != torch.bfloat16 or packed.dtype != torch.uint8 or scales.dtype != torch.float32 or packed.shape[1] * 2 != K \
             or scales.shape != (-(-K // 128), N) or not scales.is_contiguous():
         raise TypeError("mm_w4: x bf16 [M, K], packed uint8 [N, K / 2], scales fp32 [ceil(K / 128), N] contiguous")
-    call("egomi_gemm_w4", P(x), c_i64(_ld(x)), P(packed), c_i64(_ld(packed)), P(scales), P(out), c_i64(_ld(out) if out is not None else 0),
-         P(residual), c_i64(_ld(residual) if residual is not None else 0), c_i(M), c_i(N), c_i(K), c_i(epilogue), P(workspace),
-         c_i64(workspace.numel() * workspace.element_size() if workspace is not None else 0), S())
+    _wq_launch("egomi_gemm_w4", x, packed, scales, out, residual, workspace, epilogue)
 
 
 def mm_w4(x, packed, scales, out=None, residual=None, workspace=None):
@@ -400,13 +407,7 @@ def mm_w4(x, packed, scales, out=None, residual=None, workspace=None):
 def mm_w4_slabs(x, packed, scales, workspace, count_only=False):
     """mm_w4's product as UNSUMMED fp32 K-slice slabs [slices, M, N] at the start of `workspace` (egomi_gemm_w4, EGOMI_EPI_SLABS);
     returns the number of slices (count_only: without launching; 0 = the library cannot run this shape)."""
-    M, K = x.shape
-    N = packed.shape[0]
-    n = _lib.lib().egomi_gemm_w4_slab_count(c_i(M), c_i(N), c_i(K), c_i64(workspace.numel() * workspace.element_size()))
-    if count_only:
-        return n
-    _w4(x, packed, scales, None, None, workspace, 2)
-    return n
+    return _wq_slabs(_w4, "egomi_gemm_w4_slab_count", x, packed, scales, workspace, count_only)
 
 
 # ------------------------------------------------------------------------------------------ rows
