@@ -15,8 +15,8 @@ import os
 import torch
 
 from . import lora, ops
-from ._lib import c_i, c_f, c_i64, call
-from .ops import P, S, dt
+from ._lib import call
+from .ops import S, dt
 
 
 @contextlib.contextmanager
@@ -40,24 +40,23 @@ def _capture(g):
 
 
 def kv_append(k, v, ld, kc, vc, B, Sq, H, hd, Smax, pos0):
-    call("egomi_kv_append", P(k), P(v), c_i64(ld), P(kc), P(vc), c_i(B), c_i(Sq), c_i(H), c_i(hd), c_i(Smax), c_i(pos0), c_i(dt(k.dtype)), S())
+    call("egomi_kv_append", k, v, ld, kc, vc, B, Sq, H, hd, Smax, pos0, dt(k.dtype), S())
 
 
 def attn_decode(q, ld_q, kc, vc, key_mask, out, B, H, hd, Smax, T_len, scale):
-    call("egomi_attn_decode", P(q), c_i64(ld_q), P(kc), P(vc), P(key_mask), c_i64(key_mask.stride(0) if key_mask is not None else 0),
-         P(out), c_i64(out.stride(0)), c_i(B), c_i(H), c_i(hd), c_i(Smax), c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+    call("egomi_attn_decode", q, ld_q, kc, vc, key_mask, key_mask.stride(0) if key_mask is not None else 0, out, out.stride(0), B, H, hd, Smax, T_len,
+         scale, dt(q.dtype), S())
 
 
 def kv_append_fp8(k, v, ld, kc, vc, ks, vs, B, Sq, H, hd, Smax, pos0):
     """kv_append into the fp8 cache: codes kc / vc uint8 [B, H, Smax, hd], scales ks / vs fp32 [B, H, Smax] (include/egomi.h egomi_kv_append_fp8)."""
-    call("egomi_kv_append_fp8", P(k), P(v), c_i64(ld), P(kc), P(vc), P(ks), P(vs), c_i(B), c_i(Sq), c_i(H), c_i(hd), c_i(Smax), c_i(pos0),
-         c_i(dt(k.dtype)), S())
+    call("egomi_kv_append_fp8", k, v, ld, kc, vc, ks, vs, B, Sq, H, hd, Smax, pos0, dt(k.dtype), S())
 
 
 def attn_decode_fp8(q, ld_q, kc, vc, ks, vs, key_mask, out, B, H, hd, Smax, T_len, scale):
     """attn_decode over the fp8 cache (include/egomi.h egomi_attn_decode_fp8)."""
-    call("egomi_attn_decode_fp8", P(q), c_i64(ld_q), P(kc), P(vc), P(ks), P(vs), P(key_mask), c_i64(key_mask.stride(0) if key_mask is not None else 0),
-         P(out), c_i64(out.stride(0)), c_i(B), c_i(H), c_i(hd), c_i(Smax), c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+    call("egomi_attn_decode_fp8", q, ld_q, kc, vc, ks, vs, key_mask, key_mask.stride(0) if key_mask is not None else 0, out, out.stride(0), B, H, hd,
+         Smax, T_len, scale, dt(q.dtype), S())
 
 
 def kv8_quantize(x):
@@ -121,25 +120,23 @@ def w4_dequantize(packed, scales, K):
 
 def argmax_rows(logits, ids, seq=None, pos=0):
     B, V = logits.shape
-    call("egomi_argmax_rows", P(logits), c_i64(logits.stride(0)), c_i(B), c_i(V), P(ids), P(seq), c_i64(seq.stride(0) if seq is not None else 0),
-         c_i(pos), c_i(dt(logits.dtype)), S())
+    call("egomi_argmax_rows", logits, logits.stride(0), B, V, ids, seq, seq.stride(0) if seq is not None else 0, pos, dt(logits.dtype), S())
 
 
 def sample_rows(logits, scores, seq, pos, rep_from, ids, done, repetition_penalty, temperature, top_k, top_p, do_sample, rng, draw, eos, pad):
     """One step's token choice for the whole batch (include/egomi.h egomi_sample_rows): processed scores (HF's `.scores`) + next token."""
     B, V = logits.shape
-    call("egomi_sample_rows", P(logits), c_i64(logits.stride(0)), c_i(B), c_i(V), P(scores), c_i64(scores.stride(0)), P(seq),
-         c_i64(seq.stride(0) if seq is not None else 0), c_i(pos), c_i(rep_from), P(ids), P(done), c_f(repetition_penalty), c_f(temperature),
-         c_i(int(top_k or 0)), c_f(top_p), c_i(int(bool(do_sample))), P(rng), c_i(draw), c_i64(-1 if eos is None else int(eos)),
-         c_i64(0 if pad is None else int(pad)), c_i(dt(logits.dtype)), S())
+    call("egomi_sample_rows", logits, logits.stride(0), B, V, scores, scores.stride(0), seq, seq.stride(0) if seq is not None else 0, pos, rep_from,
+         ids, done, repetition_penalty, temperature, int(top_k or 0), top_p, int(bool(do_sample)), rng, draw, -1 if eos is None else int(eos),
+         0 if pad is None else int(pad), dt(logits.dtype), S())
 
 
 def token_logprob(logits, tok, eos, live, tok_lp, col, sum_lp, n_tok):
     """The log-prob of this step's chosen token under the RAW logits, per row (include/egomi.h egomi_token_logprob): tok_lp[:, col], and the
     running sum_lp / n_tok; live (int32 [R] or None) stops a row's count after its eos."""
     R, V = logits.shape
-    call("egomi_token_logprob", P(logits), c_i64(logits.stride(0)), c_i(R), c_i(V), P(tok), c_i64(-1 if eos is None else int(eos)), P(live),
-         P(tok_lp), c_i64(tok_lp.stride(0)), c_i(col), P(sum_lp), P(n_tok), c_i(dt(logits.dtype)), S())
+    call("egomi_token_logprob", logits, logits.stride(0), R, V, tok, -1 if eos is None else int(eos), live, tok_lp, tok_lp.stride(0), col, sum_lp,
+         n_tok, dt(logits.dtype), S())
 
 
 def seq_rank(sum_lp, n_tok, B, K, length_penalty=1.0):
@@ -150,7 +147,7 @@ def seq_rank(sum_lp, n_tok, B, K, length_penalty=1.0):
         raise ValueError(f"sum_lp / n_tok must hold B * K = {B * K} rows")
     score = torch.empty(B, K, dtype=torch.float32, device=sum_lp.device)
     order = torch.empty(B, K, dtype=torch.int32, device=sum_lp.device)
-    call("egomi_seq_rank", P(sum_lp), P(n_tok), c_i(B), c_i(K), c_f(float(length_penalty)), P(score), P(order), S())
+    call("egomi_seq_rank", sum_lp, n_tok, B, K, float(length_penalty), score, order, S())
     return score, order
 
 
@@ -158,49 +155,44 @@ def beam_rows(logits, lg_div, R, nb, scores, seq, pos, repetition_penalty, tempe
               cand_key, cand_score, cand_tok, ctl):
     """One beam step's row pass (include/egomi.h egomi_beam_rows): processed log-probs (HF's `.scores`) + each row's K best candidates."""
     V = logits.shape[1]
-    call("egomi_beam_rows", P(logits), c_i64(logits.stride(0)), c_i(lg_div), c_i(R), c_i(V), c_i(nb), P(scores), c_i64(scores.stride(0)), P(seq),
-         c_i64(seq.stride(0) if seq is not None else 0), c_i(pos), c_f(repetition_penalty), c_f(temperature), c_i(int(top_k or 0)), c_f(top_p),
-         c_i(min_keep), c_i(int(bool(do_sample))), P(rng), c_i(draw), P(run_score), c_i(cand_key.shape[1]), P(cand_key), P(cand_score), P(cand_tok),
-         P(ctl), c_i(dt(logits.dtype)), S())
+    call("egomi_beam_rows", logits, logits.stride(0), lg_div, R, V, nb, scores, scores.stride(0), seq, seq.stride(0) if seq is not None else 0, pos,
+         repetition_penalty, temperature, int(top_k or 0), top_p, min_keep, int(bool(do_sample)), rng, draw, run_score, cand_key.shape[1], cand_key,
+         cand_score, cand_tok, ctl, dt(logits.dtype), S())
 
 
 def beam_update(B, nb, V, cand_key, cand_score, cand_tok, S0, cur_len, max_len, eos, length_penalty, early_stopping, seq, fin_seq, bidx, fin_bidx,
                 kv_row, run_score, fin_score, fin_flag, heur, tok, ctl):
     """One beam step's per-item update (include/egomi.h egomi_beam_update).  early_stopping: False / True / "never"."""
     es = 2 if early_stopping == "never" else int(bool(early_stopping))
-    call("egomi_beam_update", c_i(B), c_i(nb), c_i(cand_key.shape[1]), c_i(V), P(cand_key), P(cand_score), P(cand_tok), c_i(S0), c_i(cur_len),
-         c_i(max_len), c_i64(-1 if eos is None else int(eos)), c_f(length_penalty), c_i(es), P(seq), P(fin_seq), c_i64(seq.stride(0)), P(bidx),
-         P(fin_bidx), c_i64(bidx.stride(0)), P(kv_row), c_i64(kv_row.stride(0)), P(run_score), P(fin_score), P(fin_flag), P(heur), P(tok), P(ctl), S())
+    call("egomi_beam_update", B, nb, cand_key.shape[1], V, cand_key, cand_score, cand_tok, S0, cur_len, max_len, -1 if eos is None else int(eos),
+         length_penalty, es, seq, fin_seq, seq.stride(0), bidx, fin_bidx, bidx.stride(0), kv_row, kv_row.stride(0), run_score, fin_score, fin_flag,
+         heur, tok, ctl, S())
 
 
 def attn_decode_rows(q, ld_q, kc, vc, kv_row, n_phys, key_mask, out, B, nb, H, hd, Smax, T_len, scale):
     """attn_decode with key t of logical row r read from physical cache row kv_row[r, t] (include/egomi.h egomi_attn_decode_rows)."""
-    call("egomi_attn_decode_rows", P(q), c_i64(ld_q), P(kc), P(vc), P(kv_row), c_i64(kv_row.stride(0)), c_i(n_phys), P(key_mask),
-         c_i64(key_mask.stride(0) if key_mask is not None else 0), P(out), c_i64(out.stride(0)), c_i(B), c_i(nb), c_i(H), c_i(hd), c_i(Smax),
-         c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+    call("egomi_attn_decode_rows", q, ld_q, kc, vc, kv_row, kv_row.stride(0), n_phys, key_mask, key_mask.stride(0) if key_mask is not None else 0,
+         out, out.stride(0), B, nb, H, hd, Smax, T_len, scale, dt(q.dtype), S())
 
 
 def attn_decode_rows_fp8(q, ld_q, kc, vc, ks, vs, kv_row, n_phys, key_mask, out, B, nb, H, hd, Smax, T_len, scale):
     """attn_decode_rows over the fp8 cache (include/egomi.h egomi_attn_decode_rows_fp8)."""
-    call("egomi_attn_decode_rows_fp8", P(q), c_i64(ld_q), P(kc), P(vc), P(ks), P(vs), P(kv_row), c_i64(kv_row.stride(0)), c_i(n_phys), P(key_mask),
-         c_i64(key_mask.stride(0) if key_mask is not None else 0), P(out), c_i64(out.stride(0)), c_i(B), c_i(nb), c_i(H), c_i(hd), c_i(Smax),
-         c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+    call("egomi_attn_decode_rows_fp8", q, ld_q, kc, vc, ks, vs, kv_row, kv_row.stride(0), n_phys, key_mask,
+         key_mask.stride(0) if key_mask is not None else 0, out, out.stride(0), B, nb, H, hd, Smax, T_len, scale, dt(q.dtype), S())
 
 
 def attn_decode_shared(q, ld_q, kp, vp, key_mask, ks, vs, out, B, K, H, hd, Sp, S0, Tmax, T_len, scale):
     """Attention of the B * K logical rows r = b * K + j over clip b's prompt cache kp / vp [B, H, Sp, hd] (keys 0 .. S0-1, key_mask
     [B, >= S0]) and the row's own suffix cache ks / vs [B*K, H, Tmax, hd] (keys 0 .. T_len-1)  (include/egomi.h egomi_attn_decode_shared)."""
-    call("egomi_attn_decode_shared", P(q), c_i64(ld_q), P(kp), P(vp), P(key_mask), c_i64(key_mask.stride(0) if key_mask is not None else 0),
-         P(ks), P(vs), P(out), c_i64(out.stride(0)), c_i(B), c_i(K), c_i(H), c_i(hd), c_i(Sp), c_i(S0), c_i(Tmax), c_i(T_len), c_f(scale),
-         c_i(dt(q.dtype)), S())
+    call("egomi_attn_decode_shared", q, ld_q, kp, vp, key_mask, key_mask.stride(0) if key_mask is not None else 0, ks, vs, out, out.stride(0), B, K,
+         H, hd, Sp, S0, Tmax, T_len, scale, dt(q.dtype), S())
 
 
 def attn_decode_shared_rows(q, ld_q, kp, vp, key_mask, ks, vs, sfx_row, n_phys, out, B, K, H, hd, Sp, S0, Tmax, T_len, scale):
     """attn_decode_shared with suffix key t of logical row r read from physical suffix row sfx_row[r, t] of ks / vs [n_phys, H, Tmax, hd]
     (beam search on the split cache; entries outside [0, n_phys) are masked keys)  (include/egomi.h egomi_attn_decode_shared_rows)."""
-    call("egomi_attn_decode_shared_rows", P(q), c_i64(ld_q), P(kp), P(vp), P(key_mask), c_i64(key_mask.stride(0) if key_mask is not None else 0),
-         P(ks), P(vs), P(sfx_row), c_i64(sfx_row.stride(0) if sfx_row is not None else 0), c_i(n_phys), P(out), c_i64(out.stride(0)), c_i(B),
-         c_i(K), c_i(H), c_i(hd), c_i(Sp), c_i(S0), c_i(Tmax), c_i(T_len), c_f(scale), c_i(dt(q.dtype)), S())
+    call("egomi_attn_decode_shared_rows", q, ld_q, kp, vp, key_mask, key_mask.stride(0) if key_mask is not None else 0, ks, vs, sfx_row,
+         sfx_row.stride(0) if sfx_row is not None else 0, n_phys, out, out.stride(0), B, K, H, hd, Sp, S0, Tmax, T_len, scale, dt(q.dtype), S())
 
 
 class DenseCache:

@@ -6,10 +6,10 @@ import math
 
 import torch
 
-from . import _lib
-from ._lib import c_p, c_i, c_d, c_f, c_sz, c_i64, call
+from . import _abi, _lib
+from ._lib import c_p, c_i, c_d, c_f, c_sz, c_i64, call, query  # noqa: F401  (the c_* names: tests and tools build arguments with them)
 
-F32, BF16 = 0, 1
+F32, BF16 = _abi.EGOMI_F32, _abi.EGOMI_BF16
 
 
 def dt(t: torch.dtype) -> int:
@@ -49,15 +49,14 @@ def unproject_gather(rgb, depth, pp, fx, fy, d_thres=None, boxes=None, n_out=0):
     pts = torch.empty(B, cap, 3, dtype=torch.float64, device=dev)
     col = torch.empty(B, cap, 3, dtype=torch.float32, device=dev)
     cnt = torch.empty(B, dtype=torch.int32, device=dev)
-    ws_bytes = _lib.lib().egomi_unproject_workspace_bytes(B, T, H, W)
+    ws_bytes = query("egomi_unproject_workspace_bytes", B, T, H, W)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     bx, nb = None, 0
     if boxes is not None and len(boxes):
         bx = torch.tensor([[b["ymin"], b["ymax"], b["xmin"], b["xmax"]] for b in boxes], dtype=torch.int32, device=dev)
         nb = bx.shape[0]
-    call("egomi_unproject_gather", P(rgb), P(depth), P(bx), c_i(nb), c_i(B), c_i(T), c_i(H), c_i(W),
-         c_d(pp), c_d(fx), c_d(fy), c_f(float("nan") if d_thres is None else d_thres), c_i(n_out),
-         P(pts), P(col), P(cnt), P(ws), c_sz(ws_bytes), S())
+    call("egomi_unproject_gather", rgb, depth, bx, nb, B, T, H, W, pp, fx, fy, float("nan") if d_thres is None else d_thres, n_out, pts, col, cnt, ws,
+         ws_bytes, S())
     return pts, col, cnt
 
 
@@ -79,8 +78,8 @@ def depth_to_cloud(pred, rgb, final_width, final_height, focal_len_x=0, focal_le
             raise ValueError(f"depth_to_cloud: rgb must be [{B},{H},{W},3], got {tuple(rgb.shape)}")
         pts = torch.empty(B, H * W, 3, dtype=torch.float64, device=dev)
         col = torch.empty(B, H * W, 3, dtype=torch.float64, device=dev)
-    call("egomi_depth_to_cloud", P(pred), c_i(B), c_i(h0), c_i(w0), P(rgb) if want else None, c_i(H), c_i(W),
-         c_d(float(focal_len_x)), c_d(float(focal_len_y)), c_d(float(principal_point)), P(tab), P(z), P(pts), P(col), S())
+    call("egomi_depth_to_cloud", pred, B, h0, w0, rgb if want else None, H, W, float(focal_len_x), float(focal_len_y), float(principal_point), tab, z,
+         pts, col, S())
     if single:
         return z[0], (pts[0] if want else None), (col[0] if want else None)
     return z, pts, col
@@ -90,7 +89,7 @@ def pc_norm(points, colors):
     points, colors = _c(points, torch.float64), _c(colors, torch.float32)
     B, N, _ = points.shape
     out = torch.empty(B, N, 6, dtype=torch.float32, device=points.device)
-    call("egomi_pc_norm", P(points), P(colors), P(out), c_i(B), c_i(N), S())
+    call("egomi_pc_norm", points, colors, out, B, N, S())
     return out
 
 
@@ -107,7 +106,7 @@ def fps(pts, start, num_group):
         start = host.to(torch.int32).to(pts.device)
     idx = torch.empty(B, num_group, dtype=torch.int32, device=pts.device)
     cen = torch.empty(B, num_group, 3, dtype=torch.float32, device=pts.device)
-    call("egomi_fps", P(pts), c_i(B), c_i(N), c_i(C), P(start), c_i(num_group), P(idx), P(cen), S())
+    call("egomi_fps", pts, B, N, C, start, num_group, idx, cen, S())
     return idx, cen
 
 
@@ -117,22 +116,12 @@ def knn_group(pts, center, k, out_dtype=torch.float32):
     G = center.shape[1]
     idx = torch.empty(B, G, k, dtype=torch.int32, device=pts.device)
     nb = torch.empty(B, G, k, C, dtype=out_dtype, device=pts.device)
-    call("egomi_knn_group", P(pts), P(center), c_i(B), c_i(N), c_i(C), c_i(G), c_i(k), P(idx), P(nb), c_i(dt(out_dtype)), S())
+    call("egomi_knn_group", pts, center, B, N, C, G, k, idx, nb, dt(out_dtype), S())
     return idx, nb
 
 
 # ------------------------------------------------------------------------------------------ GEMM
-class GemmDesc(ctypes.Structure):
-    _fields_ = [("A", c_p), ("B", c_p), ("C", c_p), ("bias", c_p), ("residual", c_p),
-                ("M", c_i), ("N", c_i), ("K", c_i),
-                ("lda", c_i64), ("ldb", c_i64), ("ldc", c_i64), ("ldr", c_i64),
-                ("a_layout", c_i), ("b_layout", c_i), ("ab_dtype", c_i), ("c_dtype", c_i),
-                ("batch", c_i), ("batch_inner", c_i),
-                ("sA0", c_i64), ("sA1", c_i64), ("sB0", c_i64), ("sB1", c_i64), ("sC0", c_i64), ("sC1", c_i64),
-                ("alpha", c_f), ("accumulate", c_i), ("act", c_i), ("force_generic", c_i),
-                ("workspace", c_p), ("workspace_bytes", c_i64), ("split_k", c_i), ("ws_tickets_zeroed", c_i),
-                ("epilogue", c_i), ("C2", c_p), ("ldc2", c_i64)]
-
+GemmDesc = _abi.STRUCTS["egomi_gemm_desc"]               # generated from the header's typedef, field for field
 
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -151,7 +140,6 @@ class GemmProfiler:
         the slab-combine pass of K-sliced tail rows; for other kernels both are the call."""
         torch.cuda.synchronize()
         n, flops, ms, call_ms = 0, 0.0, 0.0, 0.0
-        L = _lib.lib()
         for e0, e1, f, k0, k1 in self.recs:
             n += 1
             flops += f
@@ -159,18 +147,17 @@ class GemmProfiler:
             call_ms += c
             if k0 is not None:
                 t = ctypes.c_float()
-                ms += t.value if L.egomi_event_elapsed_ms(k0, k1, ctypes.byref(t)) == 0 else c     # never recorded (opt-in persistent form): the call
+                ms += t.value if query("egomi_event_elapsed_ms", k0, k1, ctypes.byref(t)) == 0 else c     # never recorded (opt-in persistent form): the call
             else:
                 ms += c
         return {"launches": n, "flops": flops, "ms": ms, "call_ms": call_ms}
 
     def __del__(self):
         try:
-            L = _lib.lib()
             for _, _, _, k0, k1 in self.recs:
                 if k0 is not None:
-                    L.egomi_event_destroy(k0)
-                    L.egomi_event_destroy(k1)
+                    query("egomi_event_destroy", k0)
+                    query("egomi_event_destroy", k1)
         except Exception:
             pass
 
@@ -213,11 +200,11 @@ def gemm_raw(A, B, C, M, N, K, lda, ldb, ldc, a_layout=0, b_layout=0, bias=None,
     d.sA0, d.sA1, d.sB0, d.sB1, d.sC0, d.sC1 = strides
     d.alpha, d.accumulate, d.act, d.force_generic = alpha, int(accumulate), act, int(force_generic)
     if swiglu_out is not None:                            # EGOMI_EPI_SWIGLU: C = interleaved-32 gate|up, swiglu_out [M, N/2] = silu(gate)*up
-        d.epilogue, d.C2, d.ldc2 = 1, swiglu_out.data_ptr(), _ld(swiglu_out)
+        d.epilogue, d.C2, d.ldc2 = _abi.EGOMI_EPI_SWIGLU, swiglu_out.data_ptr(), _ld(swiglu_out)
     if swiglu_bwd_gu is not None:                         # EGOMI_EPI_SWIGLU_BWD: the product is d(act); C = d(gate|up) [M, 2N], C2 = gate|up [M, 2N] (interleaved-32)
         if swiglu_out is not None or swiglu_bwd_gu.dtype != C.dtype:
             raise TypeError("gemm: swiglu_bwd_gu excludes swiglu_out and must have the output dtype")
-        d.epilogue, d.C2, d.ldc2 = 3, swiglu_bwd_gu.data_ptr(), _ld(swiglu_bwd_gu)
+        d.epilogue, d.C2, d.ldc2 = _abi.EGOMI_EPI_SWIGLU_BWD, swiglu_bwd_gu.data_ptr(), _ld(swiglu_bwd_gu)
     if workspace is None and M >= 1024 and batch <= 1:
         workspace = _tail_workspace(A.device)            # ticket words + fp32 slabs for the shared tiles of the 256x256 kernel
         if persistent is False:                          # A/B runs, tests: the non-persistent kernel + combine launch; its slabs must
@@ -230,8 +217,8 @@ def gemm_raw(A, B, C, M, N, K, lda, ldb, ldc, a_layout=0, b_layout=0, bias=None,
         if not t.is_cuda:
             raise _lib.EgomiError("gemm needs device tensors")
     if slabs or count_only:                               # EGOMI_EPI_SLABS: K-slice slabs stay unsummed in `workspace`; -> their number
-        d.epilogue = 2
-        n = _lib.lib().egomi_gemm_slab_count(ctypes.byref(d))
+        d.epilogue = _abi.EGOMI_EPI_SLABS
+        n = query("egomi_gemm_slab_count", ctypes.byref(d))
         if count_only:
             return n
         if n < 2:
@@ -244,24 +231,23 @@ def gemm_raw(A, B, C, M, N, K, lda, ldb, ldc, a_layout=0, b_layout=0, bias=None,
         # EGOMI_EPI_SLABS on a large product: the K-sliced tail rows stay as fp32 slabs for the caller's next kernel (ops.rmsnorm /
         # ops.rmsnorm_bwd with tail=...); nothing changes when the library's plan has no such rows for this shape
         row0, slices = c_i(0), c_i(0)
-        if _lib.lib().egomi_gemm_tail_plan(ctypes.byref(d), ctypes.byref(row0), ctypes.byref(slices)) == 0 and slices.value >= 2:
-            d.epilogue = 2
-            if _lib.lib().egomi_gemm_kernel_id(ctypes.byref(d)) == 2:    # the launch must take the kernel the plan was made for
+        if query("egomi_gemm_tail_plan", ctypes.byref(d), ctypes.byref(row0), ctypes.byref(slices)) == 0 and slices.value >= 2:
+            d.epilogue = _abi.EGOMI_EPI_SLABS
+            if query("egomi_gemm_kernel_id", ctypes.byref(d)) == 2:    # the launch must take the kernel the plan was made for
                 tail = (row0.value, slices.value, d.workspace + (4096 if d.ws_tickets_zeroed else 0))
             else:
-                d.epilogue = 0
+                d.epilogue = _abi.EGOMI_EPI_NONE
     prof = PROFILER
     flops = 2.0 * M * N * K * max(1, batch)
-    kid = _lib.lib().egomi_gemm_kernel_id(ctypes.byref(d)) if (prof is not None and prof.enabled and flops >= prof.min_flops) else None
+    kid = query("egomi_gemm_kernel_id", ctypes.byref(d)) if (prof is not None and prof.enabled and flops >= prof.min_flops) else None
     if kid is not None and (prof.kernel_ids is None or kid in prof.kernel_ids):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         k0 = k1 = None
         if kid == 2:                                        # the 256x256 kernel: the library brackets the kernel itself
-            L = _lib.lib()
             k0, k1 = c_p(), c_p()
-            _lib.check(L.egomi_event_create(ctypes.byref(k0)), "egomi_event_create")
-            _lib.check(L.egomi_event_create(ctypes.byref(k1)), "egomi_event_create")
-            _lib.check(L.egomi_gemm_time_next(k0, k1), "egomi_gemm_time_next")
+            call("egomi_event_create", ctypes.byref(k0))
+            call("egomi_event_create", ctypes.byref(k1))
+            call("egomi_gemm_time_next", k0, k1)
         e0.record()
         call("egomi_gemm", ctypes.byref(d), S())
         e1.record()
@@ -303,20 +289,18 @@ def mm_slabs(a, b, out_like, workspace, count_only=False):
 def slabs_rmsnorm(workspace, slices, residual, w, eps, x_out, h_out):
     """x_out = round(sum of the slabs + residual), h_out = rmsnorm(x_out) * w  (egomi_slabs_rmsnorm)."""
     rows, cols = x_out.shape
-    call("egomi_slabs_rmsnorm", P(workspace), c_i(slices), c_i(rows), c_i(cols), P(residual), c_i64(_ld(residual) if residual is not None else 0), P(w),
-         c_f(eps), P(x_out), c_i64(_ld(x_out)), P(h_out), c_i64(_ld(h_out)), c_i(dt(x_out.dtype)), S())
+    call("egomi_slabs_rmsnorm", workspace, slices, rows, cols, residual, _ld(residual) if residual is not None else 0, w, eps, x_out, _ld(x_out),
+         h_out, _ld(h_out), dt(x_out.dtype), S())
 
 
 def qkv_finish(workspace, slices, qkv, cos, sin, pos, kc, vc, B, H, hd, Smax):
     """q|k|v = round(sum of the slabs); RoPE(pos) on q and k; q -> qkv, k / v -> the caches at `pos`  (egomi_qkv_finish)."""
-    call("egomi_qkv_finish", P(workspace), c_i(slices), P(qkv), c_i64(_ld(qkv)), P(cos), P(sin), c_i(pos), P(kc), P(vc), c_i(B), c_i(H), c_i(hd),
-         c_i(Smax), c_i(dt(qkv.dtype)), S())
+    call("egomi_qkv_finish", workspace, slices, qkv, _ld(qkv), cos, sin, pos, kc, vc, B, H, hd, Smax, dt(qkv.dtype), S())
 
 
 def qkv_finish_fp8(workspace, slices, qkv, cos, sin, pos, kc, vc, ks, vs, B, H, hd, Smax):
     """qkv_finish with k / v quantised into the fp8 cache at `pos`: codes kc / vc uint8, scales ks / vs fp32  (egomi_qkv_finish_fp8)."""
-    call("egomi_qkv_finish_fp8", P(workspace), c_i(slices), P(qkv), c_i64(_ld(qkv)), P(cos), P(sin), c_i(pos), P(kc), P(vc), P(ks), P(vs), c_i(B),
-         c_i(H), c_i(hd), c_i(Smax), c_i(dt(qkv.dtype)), S())
+    call("egomi_qkv_finish_fp8", workspace, slices, qkv, _ld(qkv), cos, sin, pos, kc, vc, ks, vs, B, H, hd, Smax, dt(qkv.dtype), S())
 
 
 # ------------------------------------------------------------------------------------------ fp8 weights (decode projections)
@@ -328,7 +312,7 @@ def quantize_rows_fp8(w):
     N, K = w.shape
     codes = torch.empty(N, K, dtype=torch.uint8, device=w.device)
     scales = torch.empty(N, dtype=torch.float32, device=w.device)
-    call("egomi_quantize_rows_fp8", P(w), c_i64(_ld(w)), c_i(N), c_i(K), P(codes), c_i64(K), P(scales), S())
+    call("egomi_quantize_rows_fp8", w, _ld(w), N, K, codes, K, scales, S())
     return codes, scales
 
 
@@ -336,18 +320,17 @@ def _wq_launch(sym, x, codes, scales, out, residual, workspace, epilogue):
     """egomi_gemm_w8 / egomi_gemm_w4 (one argument list: csrc/wq_gemm.h) on operands the format's caller has checked."""
     M, K = x.shape
     N = codes.shape[0]
-    call(sym, P(x), c_i64(_ld(x)), P(codes), c_i64(_ld(codes)), P(scales), P(out), c_i64(_ld(out) if out is not None else 0),
-         P(residual), c_i64(_ld(residual) if residual is not None else 0), c_i(M), c_i(N), c_i(K), c_i(epilogue), P(workspace),
-         c_i64(workspace.numel() * workspace.element_size() if workspace is not None else 0), S())
+    call(sym, x, _ld(x), codes, _ld(codes), scales, out, _ld(out) if out is not None else 0, residual, _ld(residual) if residual is not None else 0,
+         M, N, K, epilogue, workspace, workspace.numel() * workspace.element_size() if workspace is not None else 0, S())
 
 
 def _wq_slabs(launch, count_sym, x, codes, scales, workspace, count_only):
     """The slab path of either format: the library's count for this shape and workspace, then (unless count_only) the launch."""
     M, K = x.shape
     N = codes.shape[0]
-    n = getattr(_lib.lib(), count_sym)(c_i(M), c_i(N), c_i(K), c_i64(workspace.numel() * workspace.element_size()))
+    n = query(count_sym, M, N, K, workspace.numel() * workspace.element_size())
     if not count_only:
-        launch(x, codes, scales, None, None, workspace, 2)
+        launch(x, codes, scales, None, None, workspace, _abi.EGOMI_EPI_SLABS)
     return n
 
 
@@ -363,7 +346,7 @@ def mm_w8(x, codes, scales, out=None, residual=None, workspace=None):
     (egomi_gemm_w8, EGOMI_EPI_NONE; `workspace` lets the library split K)."""
     if out is None:
         out = torch.empty(x.shape[0], codes.shape[0], dtype=torch.bfloat16, device=x.device)
-    _w8(x, codes, scales, out, residual, workspace, 0)
+    _w8(x, codes, scales, out, residual, workspace, _abi.EGOMI_EPI_NONE)
     return out
 
 
@@ -383,7 +366,7 @@ def quantize_rows_int4(w):
     N, K = w.shape
     packed = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
     scales = torch.empty(-(-K // 128), N, dtype=torch.float32, device=w.device)
-    call("egomi_quantize_rows_int4", P(w), c_i64(_ld(w)), c_i(N), c_i(K), P(packed), c_i64(K // 2), P(scales), S())
+    call("egomi_quantize_rows_int4", w, _ld(w), N, K, packed, K // 2, scales, S())
     return packed, scales
 
 
@@ -400,7 +383,7 @@ def mm_w4(x, packed, scales, out=None, residual=None, workspace=None):
     (egomi_gemm_w4, EGOMI_EPI_NONE; `workspace` lets the library split K)."""
     if out is None:
         out = torch.empty(x.shape[0], packed.shape[0], dtype=torch.bfloat16, device=x.device)
-    _w4(x, packed, scales, out, residual, workspace, 0)
+    _w4(x, packed, scales, out, residual, workspace, _abi.EGOMI_EPI_NONE)
     return out
 
 
@@ -414,7 +397,7 @@ def mm_w4_slabs(x, packed, scales, workspace, count_only=False):
 def layernorm(x, w, b, eps=1e-5, add=None, sum_out=None, out=None):
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]
     out = torch.empty_like(x) if out is None else out
-    call("egomi_layernorm_fwd", P(x), P(add), P(w), P(b), P(sum_out), P(out), c_i(rows), c_i(cols), c_f(eps), c_i(dt(x.dtype)), S())
+    call("egomi_layernorm_fwd", x, add, w, b, sum_out, out, rows, cols, eps, dt(x.dtype), S())
     return out
 
 
@@ -424,10 +407,10 @@ def rmsnorm(x, w, eps, rstd=None, out=None, tail=None, tail_residual=None):
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]
     out = torch.empty_like(x) if out is None else out
     if tail is not None:
-        call("egomi_rmsnorm_fwd_tail", P(x), P(w), P(out), P(rstd), c_i(rows), c_i(cols), c_f(eps), c_i(tail[0]), c_p(tail[2]), c_i(tail[1]),
-             P(tail_residual), c_i64(_ld(tail_residual) if tail_residual is not None else 0), c_i(dt(x.dtype)), S())
+        call("egomi_rmsnorm_fwd_tail", x, w, out, rstd, rows, cols, eps, tail[0], c_p(tail[2]), tail[1], tail_residual,
+             _ld(tail_residual) if tail_residual is not None else 0, dt(x.dtype), S())
         return out
-    call("egomi_rmsnorm_fwd", P(x), P(w), P(out), P(rstd), c_i(rows), c_i(cols), c_f(eps), c_i(dt(x.dtype)), S())
+    call("egomi_rmsnorm_fwd", x, w, out, rstd, rows, cols, eps, dt(x.dtype), S())
     return out
 
 
@@ -438,14 +421,12 @@ def rmsnorm_bwd(dy, x, w, rstd, dx_add=None, dw=None, out=None, tail=None, windo
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]
     out = torch.empty_like(x) if out is None else out
     if window is not None:
-        call("egomi_rmsnorm_bwd_rows", P(dy), P(x), P(w), P(rstd), P(out), P(dx_add), P(dw), c_i(rows), c_i(cols), c_i(window[0]), c_i(window[1]),
-             c_i(dt(x.dtype)), S())
+        call("egomi_rmsnorm_bwd_rows", dy, x, w, rstd, out, dx_add, dw, rows, cols, window[0], window[1], dt(x.dtype), S())
         return out
     if tail is not None:
-        call("egomi_rmsnorm_bwd_tail", P(dy), P(x), P(w), P(rstd), P(out), P(dx_add), P(dw), c_i(rows), c_i(cols), c_i(tail[0]), c_p(tail[2]), c_i(tail[1]),
-             c_i(dt(x.dtype)), S())
+        call("egomi_rmsnorm_bwd_tail", dy, x, w, rstd, out, dx_add, dw, rows, cols, tail[0], c_p(tail[2]), tail[1], dt(x.dtype), S())
         return out
-    call("egomi_rmsnorm_bwd", P(dy), P(x), P(w), P(rstd), P(out), P(dx_add), P(dw), c_i(rows), c_i(cols), c_i(dt(x.dtype)), S())
+    call("egomi_rmsnorm_bwd", dy, x, w, rstd, out, dx_add, dw, rows, cols, dt(x.dtype), S())
     return out
 
 
@@ -457,34 +438,33 @@ def rope_tables(seq, head_dim, theta):
 
 
 def rope_(x, cos, sin, rows, seq, pos_offset, H, hd, ld, inverse=False):
-    call("egomi_rope", P(x), P(cos), P(sin), c_i64(rows), c_i(seq), c_i(pos_offset), c_i(H), c_i(hd), c_i64(ld), c_i(int(inverse)), c_i(dt(x.dtype)), S())
+    call("egomi_rope", x, cos, sin, rows, seq, pos_offset, H, hd, ld, int(inverse), dt(x.dtype), S())
     return x
 
 
 def rope_qkv_tail_(qkv, cos, sin, rows, seq, pos_offset, H, hd, ld, tail):
     """rope_ on the q and k heads of a stacked q|k|v array (H = heads of ONE of them) whose rows >= tail[0] are still the K-slice
     slabs of the product (mm(..., defer_tail=True)): summed, rounded, rotated / materialised in this pass (egomi_rope_qkv_tail)."""
-    call("egomi_rope_qkv_tail", P(qkv), P(cos), P(sin), c_i64(rows), c_i(seq), c_i(pos_offset), c_i(H), c_i(hd), c_i64(ld), c_i(tail[0]), c_p(tail[2]),
-         c_i(tail[1]), c_i(dt(qkv.dtype)), S())
+    call("egomi_rope_qkv_tail", qkv, cos, sin, rows, seq, pos_offset, H, hd, ld, tail[0], c_p(tail[2]), tail[1], dt(qkv.dtype), S())
     return qkv
 
 
 def swiglu(gate, up, out):
     rows, cols = gate.shape
-    call("egomi_swiglu_fwd", P(gate), P(up), P(out), c_i64(rows), c_i(cols), c_i64(_ld(gate)), c_i64(_ld(out)), c_i(dt(gate.dtype)), S())
+    call("egomi_swiglu_fwd", gate, up, out, rows, cols, _ld(gate), _ld(out), dt(gate.dtype), S())
     return out
 
 
 def swiglu_il(gu, out):
     """Interleaved-32 gate|up array gu [rows, 2*cols] -> out [rows, cols] = silu(gate)*up."""
     rows, cols = out.shape
-    call("egomi_swiglu_il_fwd", P(gu), P(out), c_i64(rows), c_i(cols), c_i64(_ld(gu)), c_i64(_ld(out)), c_i(dt(gu.dtype)), S())
+    call("egomi_swiglu_il_fwd", gu, out, rows, cols, _ld(gu), _ld(out), dt(gu.dtype), S())
     return out
 
 
 def swiglu_il_bwd(dact, gu, dgu):
     rows, cols = dact.shape
-    call("egomi_swiglu_il_bwd", P(dact), P(gu), P(dgu), c_i64(rows), c_i(cols), c_i64(_ld(gu)), c_i64(_ld(dact)), c_i64(_ld(dgu)), c_i(dt(gu.dtype)), S())
+    call("egomi_swiglu_il_bwd", dact, gu, dgu, rows, cols, _ld(gu), _ld(dact), _ld(dgu), dt(gu.dtype), S())
     return dgu
 
 
@@ -494,7 +474,7 @@ def gemm_kernel_id(M, N, K, dtype=torch.bfloat16, out_dtype=torch.bfloat16):
     d.A = d.B = d.C = 256                                 # aligned placeholders: the selection looks at shapes and alignment only
     d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, N, K, K, K, N
     d.ab_dtype, d.c_dtype, d.batch = dt(dtype), dt(out_dtype), 1
-    return _lib.lib().egomi_gemm_kernel_id(ctypes.byref(d))
+    return query("egomi_gemm_kernel_id", ctypes.byref(d))
 
 
 def mm_kernel_id(a, b, out, a_layout=0, b_layout=0, accumulate=False):
@@ -507,7 +487,7 @@ def mm_kernel_id(a, b, out, a_layout=0, b_layout=0, accumulate=False):
     d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, N, K, _ld(a), _ld(b), _ld(out)
     d.a_layout, d.b_layout, d.ab_dtype, d.c_dtype, d.batch = a_layout, b_layout, dt(a.dtype), dt(out.dtype), 1
     d.alpha, d.accumulate = 1.0, int(accumulate)
-    return _lib.lib().egomi_gemm_kernel_id(ctypes.byref(d))
+    return query("egomi_gemm_kernel_id", ctypes.byref(d))
 
 
 GEMM_FORMS = {0: "none", 1: "generic", 2: "128x128", 3: "256x128", 4: "gemv_m16", 5: "m256", 6: "8phase", 7: "persistent", 8: "tall",
@@ -518,7 +498,7 @@ def gemm_last_route():
     """The route of this thread's most recent egomi_gemm (include/egomi.h egomi_gemm_last_route), as recorded by the launch that ran:
     (form name, split-K slices, first K-sliced tail row, tail slices, column split Na)."""
     out = (c_i * 4)()
-    form = _lib.lib().egomi_gemm_last_route(out)
+    form = query("egomi_gemm_last_route", out)
     if form < 0:
         _lib.check(form, "egomi_gemm_last_route")
     return (GEMM_FORMS[form],) + tuple(out)
@@ -526,30 +506,28 @@ def gemm_last_route():
 
 def swiglu_bwd(dact, gate, up, dgate, dup):
     rows, cols = gate.shape
-    call("egomi_swiglu_bwd", P(dact), P(gate), P(up), P(dgate), P(dup), c_i64(rows), c_i(cols), c_i64(_ld(gate)), c_i64(_ld(dact)),
-         c_i64(_ld(dgate)), c_i(dt(gate.dtype)), S())
+    call("egomi_swiglu_bwd", dact, gate, up, dgate, dup, rows, cols, _ld(gate), _ld(dact), _ld(dgate), dt(gate.dtype), S())
 
 
 def gelu(x, out=None):
     out = torch.empty_like(x) if out is None else out
-    call("egomi_gelu_fwd", P(x), P(out), c_i64(x.numel()), c_i(dt(x.dtype)), S())
+    call("egomi_gelu_fwd", x, out, x.numel(), dt(x.dtype), S())
     return out
 
 
 def gelu_bwd(dy, x, out=None):
     out = torch.empty_like(x) if out is None else out
-    call("egomi_gelu_bwd", P(dy), P(x), P(out), c_i64(x.numel()), c_i(dt(x.dtype)), S())
+    call("egomi_gelu_bwd", dy, x, out, x.numel(), dt(x.dtype), S())
     return out
 
 
 def softmax(scores, Z, heads, Sq, Sk, out, causal=False, q_offset=0, key_mask=None):
-    call("egomi_softmax_fwd", P(scores), c_i64(Sk), P(key_mask), c_i(Z), c_i(heads), c_i(Sq), c_i(Sk), c_i(int(causal)), c_i(q_offset),
-         P(out), c_i64(Sk), c_i(dt(out.dtype)), S())
+    call("egomi_softmax_fwd", scores, Sk, key_mask, Z, heads, Sq, Sk, int(causal), q_offset, out, Sk, dt(out.dtype), S())
     return out
 
 
 def softmax_bwd(Pm, dP, dS, rows, Sk):
-    call("egomi_softmax_bwd", P(Pm), c_i64(Sk), P(dP), c_i64(Sk), P(dS), c_i64(Sk), c_i64(rows), c_i(Sk), c_i(dt(Pm.dtype)), S())
+    call("egomi_softmax_bwd", Pm, Sk, dP, Sk, dS, Sk, rows, Sk, dt(Pm.dtype), S())
     return dS
 
 
@@ -557,8 +535,8 @@ def splice_scan(ids, tok, Pn, n_clouds=None):
     """-> (start_pos, err, cloud_idx), int32 [B] each (include/egomi.h: the reference's position checks and its running cloud index)."""
     B, Sl = ids.shape
     sp, err, cloud, scratch = (torch.empty(B, dtype=torch.int32, device=ids.device) for _ in range(4))
-    call("egomi_splice_scan", P(ids), c_i(B), c_i(Sl), c_i64(tok.point_patch), c_i64(tok.point_start), c_i64(tok.point_end), c_i(Pn),
-         c_i(B if n_clouds is None else n_clouds), P(sp), P(err), P(cloud), P(scratch), S())
+    call("egomi_splice_scan", ids, B, Sl, tok.point_patch, tok.point_start, tok.point_end, Pn, B if n_clouds is None else n_clouds, sp, err, cloud,
+         scratch, S())
     return sp, err, cloud
 
 
@@ -566,14 +544,13 @@ def embed_splice(ids, W, feats, start_pos, Pn, out=None, cloud_idx=None):
     B, Sl = ids.shape
     V, d = W.shape
     out = torch.empty(B, Sl, d, dtype=W.dtype, device=W.device) if out is None else out
-    call("egomi_embed_splice_fwd", P(ids), P(W), P(feats), P(start_pos), P(cloud_idx), c_i(B), c_i(Sl), c_i(d), c_i(Pn), c_i(V), P(out), c_i(dt(W.dtype)), S())
+    call("egomi_embed_splice_fwd", ids, W, feats, start_pos, cloud_idx, B, Sl, d, Pn, V, out, dt(W.dtype), S())
     return out
 
 
 def embed_splice_bwd(dout, ids, start_pos, Pn, V, dW=None, dfeats=None, cloud_idx=None):
     B, Sl, d = dout.shape
-    call("egomi_embed_splice_bwd", P(dout), P(ids), P(start_pos), P(cloud_idx), c_i(B), c_i(Sl), c_i(d), c_i(Pn), c_i(V), P(dW), P(dfeats),
-         c_i(dt(dout.dtype)), S())
+    call("egomi_embed_splice_bwd", dout, ids, start_pos, cloud_idx, B, Sl, d, Pn, V, dW, dfeats, dt(dout.dtype), S())
 
 
 def cross_entropy(logits, targets, ignore_index, dlogits=None, grad_scale=1.0):
@@ -582,57 +559,57 @@ def cross_entropy(logits, targets, ignore_index, dlogits=None, grad_scale=1.0):
     cnt = torch.zeros(1, dtype=torch.int32, device=logits.device)
     ls = torch.zeros(1, dtype=torch.float32, device=logits.device)
     rows = torch.empty(R, dtype=torch.float32, device=logits.device)
-    call("egomi_ce_count", P(targets), c_i64(R), c_i64(ignore_index), P(cnt), S())
-    call("egomi_ce_fwd_bwd", P(logits), c_i64(_ld(logits)), P(targets), c_i(R), c_i(V), c_i64(ignore_index), P(cnt), P(ls), P(rows),
-         P(dlogits), c_i64(_ld(dlogits) if dlogits is not None else 0), c_f(grad_scale), c_i(dt(logits.dtype)), S())
+    call("egomi_ce_count", targets, R, ignore_index, cnt, S())
+    call("egomi_ce_fwd_bwd", logits, _ld(logits), targets, R, V, ignore_index, cnt, ls, rows, dlogits, _ld(dlogits) if dlogits is not None else 0,
+         grad_scale, dt(logits.dtype), S())
     return ls, cnt
 
 
 def adamw(master, model_copy, grad, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
     if grad.dtype not in (torch.float32, torch.bfloat16) or not grad.is_contiguous() or grad.numel() != master.numel():
         raise _lib.EgomiError("adamw: the gradient must be a contiguous fp32 or bf16 tensor of the parameter's size")
-    call("egomi_adamw" if grad.dtype == torch.float32 else "egomi_adamw_g16", P(master), P(model_copy), P(grad), P(m), P(v), c_i64(master.numel()), c_f(lr), c_f(beta1), c_f(beta2), c_f(eps),
-         c_f(wd), c_i(step), c_f(grad_scale), c_i(dt(model_copy.dtype) if model_copy is not None else F32), S())
+    call("egomi_adamw" if grad.dtype == torch.float32 else "egomi_adamw_g16", master, model_copy, grad, m, v, master.numel(), lr, beta1, beta2, eps,
+         wd, step, grad_scale, dt(model_copy.dtype) if model_copy is not None else F32, S())
 
 
 def transpose(x, ldo=None, out=None):
     R, C = x.shape
     ldo = R if ldo is None else ldo
     out = torch.empty(C, ldo, dtype=x.dtype, device=x.device) if out is None else out
-    call("egomi_transpose", P(x), c_i(R), c_i(C), c_i64(_ld(x)), P(out), c_i64(ldo), c_i(dt(x.dtype)), S())
+    call("egomi_transpose", x, R, C, _ld(x), out, ldo, dt(x.dtype), S())
     return out
 
 
 def cast(x, dtype, out=None):
     out = torch.empty(x.shape, dtype=dtype, device=x.device) if out is None else out
-    call("egomi_cast", P(x), c_i(dt(x.dtype)), P(out), c_i(dt(dtype)), c_i64(x.numel()), S())
+    call("egomi_cast", x, dt(x.dtype), out, dt(dtype), x.numel(), S())
     return out
 
 
 def rank_sum(chunks, out):
     """chunks [W, c] (bf16 / fp32, contiguous) -> out [c] (bf16 / fp32): fp32-accumulated sum over the leading (rank) axis."""
     W, c = chunks.shape
-    call("egomi_rank_sum", P(chunks), c_i(dt(chunks.dtype)), c_i(W), c_i64(c), P(out), c_i(dt(out.dtype)), S())
+    call("egomi_rank_sum", chunks, dt(chunks.dtype), W, c, out, dt(out.dtype), S())
     return out
 
 
 def add(a, b, out=None):
     out = torch.empty_like(a) if out is None else out
-    call("egomi_add", P(a), P(b), P(out), c_i64(a.numel()), c_i(dt(a.dtype)), S())
+    call("egomi_add", a, b, out, a.numel(), dt(a.dtype), S())
     return out
 
 
 def colsum_(x, out):
     """out (fp32 [C]) += column sums of x [R,C]."""
     R, C = x.shape
-    call("egomi_colsum", P(x), c_i64(R), c_i(C), c_i64(_ld(x)), P(out), c_i(dt(x.dtype)), S())
+    call("egomi_colsum", x, R, C, _ld(x), out, dt(x.dtype), S())
     return out
 
 
 def group_max(x, BG, M, C, concat=False, out=None):
     if out is None:
         out = torch.empty((BG * M, 2 * C) if concat else (BG, C), dtype=x.dtype, device=x.device)
-    call("egomi_group_max", P(x), c_i(BG), c_i(M), c_i(C), P(out), c_i(int(concat)), c_i(dt(x.dtype)), S())
+    call("egomi_group_max", x, BG, M, C, out, int(concat), dt(x.dtype), S())
     return out
 
 
@@ -640,18 +617,12 @@ def linear_smallk(x, w, b, act=0, out=None):
     R, K = x.numel() // x.shape[-1], x.shape[-1]
     N = w.shape[0]
     out = torch.empty(R, N, dtype=w.dtype, device=w.device) if out is None else out
-    call("egomi_linear_smallk", P(x), c_i(dt(x.dtype)), P(w), P(b), P(out), c_i64(R), c_i(N), c_i(K), c_i(act), c_i(dt(w.dtype)), S())
+    call("egomi_linear_smallk", x, dt(x.dtype), w, b, out, R, N, K, act, dt(w.dtype), S())
     return out
 
 
 # ------------------------------------------------------------------------------------------ fused attention
-class AttnDesc(ctypes.Structure):
-    _fields_ = [("q", c_p), ("k", c_p), ("v", c_p), ("o", c_p), ("lse", c_p),
-                ("dout", c_p), ("delta", c_p), ("dq", c_p), ("dk", c_p), ("dv", c_p), ("key_mask", c_p),
-                ("B", c_i), ("H", c_i), ("S", c_i), ("head_dim", c_i),
-                ("ld_qkv", c_i64), ("ld_o", c_i64), ("ld_dqkv", c_i64),
-                ("scale", c_f), ("causal", c_i), ("dtype", c_i), ("rope_cos", c_p), ("rope_sin", c_p),
-                ("q_rows", c_i)]
+AttnDesc = _abi.STRUCTS["egomi_attn_desc"]
 
 
 def _attn_desc(qkv, B, Sq, H, hd, scale, causal, key_mask):
@@ -702,9 +673,7 @@ def attn_bwd(qkv, out, lse, dout, dqkv, delta, B, Sq, H, hd, scale, causal=True,
 # PEFT's lora.Linear.forward: y = x W^T + s (x A^T) B^T, s = lora_alpha / r (no dropout, no bias).  `il`: the wide activation operand is
 # read / written in the interleaved-32 gate|up layout (include/egomi.h).
 def lora_down_workspace_bytes(M, K, R):
-    fn = _lib.lib().egomi_lora_down_workspace_bytes
-    fn.restype = c_i64
-    return int(fn(c_i(M), c_i(K), c_i(R)))
+    return query("egomi_lora_down_workspace_bytes", M, K, R)
 
 
 def lora_down(x, q, out, q_trans=False, il=False, alpha=1.0, workspace=None):
@@ -721,8 +690,8 @@ def lora_down(x, q, out, q_trans=False, il=False, alpha=1.0, workspace=None):
     if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
         workspace = torch.empty(need, dtype=torch.uint8, device=out.device)
     wb = workspace.numel() * workspace.element_size() if workspace is not None else 0
-    call("egomi_lora_down", P(x), c_i64(x.stride(0)), P(q), c_i64(q.stride(0)), c_i(int(q_trans)), P(out), c_i64(out.stride(0)), c_i(M),
-         c_i(K), c_i(R), c_f(alpha), c_i(int(il)), P(workspace), c_i64(wb), c_i(dt(x.dtype)), S())
+    call("egomi_lora_down", x, x.stride(0), q, q.stride(0), int(q_trans), out, out.stride(0), M, K, R, alpha, int(il), workspace, wb, dt(x.dtype),
+         S())
     return out
 
 
@@ -736,15 +705,12 @@ def lora_up(p, q, out, alpha, q_trans=False, il=False):
         raise ValueError("lora_up: p [M, R], Q [N, R] (or Q^T), out [M, >= N] of one dtype, rows contiguous")
     if out.shape[1] < (2 * N - 32 if il else N):
         raise ValueError(f"lora_up: out {tuple(out.shape)} is narrower than {2 * N - 32 if il else N} columns")
-    call("egomi_lora_up", P(p), c_i64(p.stride(0)), P(q), c_i64(q.stride(0)), c_i(int(q_trans)), P(out), c_i64(out.stride(0)), c_i(M),
-         c_i(N), c_i(R), c_f(alpha), c_i(int(il)), c_i(dt(p.dtype)), S())
+    call("egomi_lora_up", p, p.stride(0), q, q.stride(0), int(q_trans), out, out.stride(0), M, N, R, alpha, int(il), dt(p.dtype), S())
     return out
 
 
 def lora_wgrad_workspace_bytes(M, Pd, Qd):
-    fn = _lib.lib().egomi_lora_wgrad_workspace_bytes
-    fn.restype = c_i64
-    return int(fn(c_i(M), c_i(Pd), c_i(Qd)))
+    return query("egomi_lora_wgrad_workspace_bytes", M, Pd, Qd)
 
 
 def lora_wgrad(l, r, g, alpha, accumulate=False, il=False, Pd=None, workspace=None):
@@ -761,6 +727,6 @@ def lora_wgrad(l, r, g, alpha, accumulate=False, il=False, Pd=None, workspace=No
     if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
         workspace = torch.empty(need, dtype=torch.uint8, device=g.device)
     wb = workspace.numel() * workspace.element_size() if workspace is not None else 0
-    call("egomi_lora_wgrad", P(l), c_i64(l.stride(0)), P(r), c_i64(r.stride(0)), P(g), c_i64(g.stride(0)), c_i(M), c_i(Pd), c_i(Qd),
-         c_f(alpha), c_i(int(accumulate)), c_i(int(il)), P(workspace), c_i64(wb), c_i(dt(r.dtype)), S())
+    call("egomi_lora_wgrad", l, l.stride(0), r, r.stride(0), g, g.stride(0), M, Pd, Qd, alpha, int(accumulate), int(il), workspace, wb, dt(r.dtype),
+         S())
     return g

@@ -10,8 +10,8 @@ Gradients go to the engine's fp32 main_grad buffers.  No gradient flows to the i
 import torch
 
 from . import ops
-from ._lib import c_i, c_f, c_i64, call
-from .ops import P, S, dt
+from ._lib import call
+from .ops import S, dt
 
 PRE = "model.point_backbone."
 
@@ -33,8 +33,7 @@ def layernorm_bwd(dy, x, w, eps, dx_add=None, dw=None, db=None, out=None):
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]
     out = torch.empty_like(x) if out is None else out
     pt = _partials(min((rows + 3) // 4, 512) * 2 * cols, x.device)
-    call("egomi_layernorm_bwd", P(dy), P(x), P(w), P(out), P(dx_add), P(dw), P(db), c_i(rows), c_i(cols), c_f(eps), P(pt), c_i64(pt.numel()),
-         c_i(dt(x.dtype)), S())
+    call("egomi_layernorm_bwd", dy, x, w, out, dx_add, dw, db, rows, cols, eps, pt, pt.numel(), dt(x.dtype), S())
     return out
 
 
@@ -42,8 +41,7 @@ def bn_train_fwd(x, gamma, beta, eps, relu, stats, rmean, rvar, momentum=0.1, ou
     R, C = x.shape
     out = torch.empty_like(x) if out is None else out
     pt = _partials((R + 255) // 256 * 2 * C, x.device)
-    call("egomi_bn_train_fwd", P(x), c_i64(R), c_i(C), P(gamma), P(beta), c_f(eps), c_i(int(relu)), P(out), P(stats), P(rmean), P(rvar),
-         c_f(momentum), P(pt), c_i64(pt.numel()), c_i(dt(x.dtype)), S())
+    call("egomi_bn_train_fwd", x, R, C, gamma, beta, eps, int(relu), out, stats, rmean, rvar, momentum, pt, pt.numel(), dt(x.dtype), S())
     return out
 
 
@@ -51,20 +49,19 @@ def bn_train_bwd(dy, x, y, stats, gamma, relu, dgamma, dbeta, out=None):
     R, C = x.shape
     out = torch.empty_like(x) if out is None else out
     pt = _partials((R + 255) // 256 * 2 * C, x.device)
-    call("egomi_bn_train_bwd", P(dy), P(x), P(y), c_i64(R), c_i(C), P(stats), P(gamma), c_i(int(relu)), P(dgamma), P(dbeta), P(out),
-         P(pt), c_i64(pt.numel()), c_i(dt(x.dtype)), S())
+    call("egomi_bn_train_bwd", dy, x, y, R, C, stats, gamma, int(relu), dgamma, dbeta, out, pt, pt.numel(), dt(x.dtype), S())
     return out
 
 
 def group_argmax(x, BG, M, C):
     out = torch.empty(BG, C, dtype=x.dtype, device=x.device)
     idx = torch.empty(BG, C, dtype=torch.int32, device=x.device)
-    call("egomi_group_argmax", P(x), c_i(BG), c_i(M), c_i(C), P(out), P(idx), c_i(dt(x.dtype)), S())
+    call("egomi_group_argmax", x, BG, M, C, out, idx, dt(x.dtype), S())
     return out, idx
 
 
 def group_max_bwd(dout, idx, BG, M, C, dx, accumulate):
-    call("egomi_group_max_bwd", P(dout), P(idx), c_i(BG), c_i(M), c_i(C), P(dx), c_i64(dx.stride(0)), c_i(int(accumulate)), c_i(dt(dout.dtype)), S())
+    call("egomi_group_max_bwd", dout, idx, BG, M, C, dx, dx.stride(0), int(accumulate), dt(dout.dtype), S())
     return dx
 
 
@@ -72,13 +69,13 @@ def smallk_wgrad(dy, x, dW):
     R, N = dy.shape
     K = x.shape[-1]
     pt = _partials((R + 511) // 512 * N * K, dy.device)
-    call("egomi_smallk_wgrad", P(dy), P(x), c_i(dt(x.dtype)), c_i64(R), c_i(N), c_i(K), P(dW), P(pt), c_i64(pt.numel()), c_i(dt(dy.dtype)), S())
+    call("egomi_smallk_wgrad", dy, x, dt(x.dtype), R, N, K, dW, pt, pt.numel(), dt(dy.dtype), S())
 
 
 def rowscale_add(resid, branch, scale, rows_per_sample, out=None):
     rows, cols = branch.shape
     out = torch.empty_like(branch) if out is None else out
-    call("egomi_rowscale_add", P(resid), P(branch), P(scale), c_i64(rows), c_i(cols), c_i(rows_per_sample), P(out), c_i(dt(branch.dtype)), S())
+    call("egomi_rowscale_add", resid, branch, scale, rows, cols, rows_per_sample, out, dt(branch.dtype), S())
     return out
 
 
@@ -300,7 +297,7 @@ class PointBackboneTrainer:
         d_cat = self._dgrad(d_h3p, W3)                                      # [R, 512] = [global | local]
         d_h2 = d_cat[:, pb.pn_c2:].contiguous()
         gsum = torch.empty(BG, pb.pn_c2, dtype=T, device=dev)              # expanded global feature: sum over the group's M rows
-        call("egomi_group_sum", P(d_cat), c_i(BG), c_i(K), c_i(pb.pn_c2), c_i64(2 * pb.pn_c2), P(gsum), c_i(dt(T)), S())
+        call("egomi_group_sum", d_cat, BG, K, pb.pn_c2, 2 * pb.pn_c2, gsum, dt(T), S())
         group_max_bwd(gsum, c["am2"], BG, K, pb.pn_c2, d_h2, True)
         self._wg(e + "first_conv.3.weight", d_h2, c["y1"])
         self._bg(e + "first_conv.3.bias", d_h2)

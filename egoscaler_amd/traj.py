@@ -14,8 +14,8 @@ import re
 import numpy as np
 import torch
 
-from ._lib import c_i, c_i64, call
-from .ops import P, S
+from ._lib import call
+from .ops import S
 
 # Aria pin-hole camera and workspace constants (egoscaler/configs/camera.py:7-9, configs/dataset.py:1-7)
 PINHOLE_IMAGE_SIZE = 1408
@@ -39,8 +39,8 @@ def tokenize_batch(traj: torch.Tensor, tok, seq_len: int, steps=None):
     mask = torch.empty(B, seq_len, dtype=torch.uint8, device=dev)
     err = torch.empty(B, dtype=torch.int32, device=dev)
     st = None if steps is None else torch.as_tensor(steps, dtype=torch.int32, device=dev).contiguous()
-    call("egomi_traj_tokenize", P(traj), P(st), c_i(B), c_i(T), P(bin_edges(tok.num_bins, dev)), c_i(tok.num_bins), c_i64(tok.p0),
-         c_i64(tok.ts), c_i64(tok.tsep), c_i64(tok.te), c_i64(tok.eos), c_i64(tok.pad), c_i(seq_len), P(ids), P(mask), P(err), S())
+    call("egomi_traj_tokenize", traj, st, B, T, bin_edges(tok.num_bins, dev), tok.num_bins, tok.p0, tok.ts, tok.tsep, tok.te, tok.eos, tok.pad,
+         seq_len, ids, mask, err, S())
     if int(err.max()) != 0:
         raise ValueError("trajectory tokens exceed max_traj_token")
     return ids, mask.bool()
@@ -53,8 +53,7 @@ def detokenize_batch(ids: torch.Tensor, tok, max_steps: int):
     dev = ids.device
     out = torch.zeros(B, max_steps, 6, dtype=torch.float32, device=dev)
     n = torch.empty(B, dtype=torch.int32, device=dev)
-    call("egomi_traj_detokenize", P(ids), c_i(B), c_i(L), P(bin_edges(tok.num_bins, dev)), c_i(tok.num_bins), c_i64(tok.p0), c_i64(tok.tsep),
-         c_i64(tok.eos), c_i(max_steps), P(out), P(n), S())
+    call("egomi_traj_detokenize", ids, B, L, bin_edges(tok.num_bins, dev), tok.num_bins, tok.p0, tok.tsep, tok.eos, max_steps, out, n, S())
     return out, n
 
 
@@ -70,7 +69,7 @@ def metrics_batch(gen, n_gen, gt, n_gt=None):
     fde = torch.empty(B, dtype=torch.float64, device=dev)
     ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
     nt = None if n_gt is None else n_gt.to(torch.int32).contiguous()
-    call("egomi_traj_metrics", P(gen), P(ng), P(gt), P(nt), c_i(B), c_i(T), c_i(D), P(ade), P(fde), S())
+    call("egomi_traj_metrics", gen, ng, gt, nt, B, T, D, ade, fde, S())
     return ade, fde
 
 
@@ -94,7 +93,7 @@ def metrics_best_of(gen, n_gen, gt, n_gt=None):
     best = torch.empty(B, dtype=torch.int32, device=dev)
     ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
     nt = None if n_gt is None else n_gt.to(torch.int32).contiguous()
-    call("egomi_traj_metrics_min", P(gen), P(ng), P(gt), P(nt), c_i(B), c_i(K), c_i(T), c_i(D), P(min_ade), P(min_fde), P(best), S())
+    call("egomi_traj_metrics_min", gen, ng, gt, nt, B, K, T, D, min_ade, min_fde, best, S())
     return min_ade, min_fde, best
 
 
@@ -114,7 +113,7 @@ def select_medoid(gen, n_gen=None):
     cost = torch.empty(B, K, dtype=torch.float64, device=dev)
     pick = torch.empty(B, dtype=torch.int32, device=dev)
     ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
-    call("egomi_traj_medoid", P(gen), P(ng), c_i(B), c_i(K), c_i(Tn), c_i(D), P(cost), P(pick), S())
+    call("egomi_traj_medoid", gen, ng, B, K, Tn, D, cost, pick, S())
     return pick, cost
 
 

@@ -15,6 +15,18 @@
  *     any launch, so a bad call never reaches the GPU
  *   - dtype arguments: EGOMI_F32 / EGOMI_BF16 (raw uint16 storage)
  *   - thread-safe for distinct streams
+ *
+ * This header is the single statement of the ABI: egoscaler_amd/_abi.py reads it when the library is loaded and
+ * binds every prototype, both descriptor structures and the integer EGOMI_* constants from it.  Its reader is a
+ * few regular expressions, not a C parser, so declarations here keep to these rules (a line it cannot read makes
+ * the load fail, naming it):
+ *   - prototypes: `<return type> egomi_name(<type> <name>, ...);` with one parameter per declarator, every
+ *     parameter named, no function pointers, no arrays, no macros
+ *   - types: int, int64_t, size_t, float, double, egomi_stream_t; (const) pointers to void, float, double, int,
+ *     int32_t, int64_t, uint8_t, uint64_t and to the two descriptors; void**; const char* as a return type only
+ *   - descriptor fields: `<type> name[, name...];` of the same types; the `*` belongs to the type
+ *   - constants: `#define EGOMI_NAME <integer>`, negative values in parentheses
+ *   - debug-only symbols (egomi_*_stamp_*) are not declared here and are not bound
  */
 #ifndef EGOMI_H
 #define EGOMI_H

@@ -118,7 +118,8 @@ class Recorder:
 
     def __call__(self, name, *args):
         if self.only is None or name.startswith(self.only):
-            self.raw.append([name] + [_raw(a) for a in args])
+            from egoscaler_amd import _lib
+            self.raw.append([name] + [_raw(a) for a in _lib.marshal(name, args)])        # the ctypes values the library receives
         return self.inner(name, *args)
 
     def resolved(self, dec):
