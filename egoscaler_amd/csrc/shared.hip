@@ -32,12 +32,46 @@
 //   Order of the sums of a row: prompt (as above), slice 0 in key order on top of it, slices 1.. each in key order from empty, merge in
 //       slice order: a function of (K, S0, T_len), never of the slot j.  No atomics; a replay is bit-equal; permuting the beams of a clip
 //       (queries and table rows together) permutes the output rows bit for bit.
+//
+// Suffix pass (egomi_attn_suffix_shared; teacher-forced scoring of given candidates): every candidate row r = b*K + j brings T queries,
+// suffix positions t = 0 .. T-1, logical query row (b*K + j)*T + t, and query (j, t) is the decode query of row b*K + j at T_len = t + 1:
+// the prompt of clip b, then the row's own suffix keys 0 .. t.  The kernels are templated on SFX: a workgroup per (clip, head, tile of 32
+// consecutive of the clip's K*T queries) runs the prompt phase above on its 32 queries (one pass of the prompt K/V through LDS per
+// workgroup), then each query's 8 lanes walk its own causal cut of the suffix with the same consume_keys rounds.  Every query slot maps
+// to (query row, suffix row, T_len) through QuerySlots; with SFX = false that map is the decode one and the code is what it was.  The
+// bits of query (b, j, t) are those egomi_attn_decode_shared gives it at T_len = t + 1: a function of its own data and (S0, t, hd, dtype),
+// never of K, T, j, b or its neighbours in the tile.  Keys > t of the suffix row and keys >= S0 of the prompt row are never read.
 #include "common.h"
 #include <math.h>
 
 namespace {
 
 template <int DPT> struct RowState { float m, l, acc[DPT]; };
+
+// The 32 query slots of a workgroup.  Decode (SFX = false): slot s < K is logical row b*K + s, every row at suffix length T.  Suffix
+// pass (SFX = true): slot s is query q0 + s of the clip's K*T queries (j, t) = ((q0 + s) / T, (q0 + s) % T), q0 = 32 * tile; it
+// reads suffix row b*K + j up to key t.  The tiles of one (clip, head) are consecutive workgroups (see block_of), so the
+// workgroups in flight at any time share few prompts.  Slots >= nq are dead and clamped to the last live one (their loads stay in bounds).
+template <bool SFX> struct QuerySlots {
+    int nq, q0, T;
+    long long qbase, sbase;
+    __device__ __forceinline__ QuerySlots(int b, int K, int T_, int tile) : T(T_) {
+        q0 = SFX ? 32 * tile : 0;
+        nq = SFX ? (K * T - q0 < 32 ? K * T - q0 : 32) : K;
+        sbase = (long long)b * K;
+        qbase = SFX ? sbase * T + q0 : sbase;
+    }
+    __device__ __forceinline__ int clamp(int s) const { return s < nq ? s : nq - 1; }
+    __device__ __forceinline__ long long qrow(int s) const { return qbase + clamp(s); }                                  // of q and out
+    __device__ __forceinline__ long long srow(int s) const { return SFX ? sbase + (q0 + clamp(s)) / T : qrow(s); }       // of ks / vs
+    __device__ __forceinline__ int tlen(int s) const { return SFX ? (q0 + clamp(s)) % T + 1 : T; }                       // suffix keys it sees
+};
+// blockIdx.x -> (clip * H + head, query tile): decode has one workgroup per (clip, head); the suffix pass numbers them tile-fastest
+template <bool SFX> __device__ __forceinline__ void block_of(int K, int T, int& bh, int& tile) {
+    const int ntile = SFX ? (K * T + 31) / 32 : 1;
+    bh = SFX ? (int)blockIdx.x / ntile : (int)blockIdx.x;
+    tile = SFX ? (int)blockIdx.x % ntile : 0;
+}
 
 // DPT (4, 8 or 16) consecutive elements -> float; p aligned to the chunk
 template <typename T, int DPT> __device__ __forceinline__ void load_chunk(const T* p, float (&v)[DPT]) {
@@ -97,14 +131,14 @@ __device__ __forceinline__ void consume_keys(RowState<DPT>& st, const float (&qd
     }
 }
 
-// suffix keys of logical row `row` (from global memory), then O = acc / l
+// suffix keys 0 .. Tlen-1 of suffix row `srow` (from global memory), then O = acc / l -> out row `orow`
 template <typename T, int HD>
 __device__ __forceinline__ void suffix_and_store(RowState<HD / 8>& st, const float (&qd)[HD / 8], const T* ks, const T* vs, T* out, long long ld_o,
-                                                 long long row, int h, int H, int Tmax, int Tlen, int sub, bool live) {
+                                                 long long srow, long long orow, int h, int H, int Tmax, int Tlen, int sub, bool live) {
     constexpr int DPT = HD / 8;
     if (Tlen > 0) {
-        const T* Ks = ks + ((row * H + h) * (long long)Tmax) * HD + sub * DPT;
-        const T* Vs = vs + ((row * H + h) * (long long)Tmax) * HD + sub * DPT;
+        const T* Ks = ks + ((srow * H + h) * (long long)Tmax) * HD + sub * DPT;
+        const T* Vs = vs + ((srow * H + h) * (long long)Tmax) * HD + sub * DPT;
         consume_keys<DPT>(st, qd, Tlen,
                           [&](int key, float (&v)[DPT]) { load_chunk<T, DPT>(Ks + (long long)key * HD, v); },
                           [&](int key, float (&v)[DPT]) { load_chunk<T, DPT>(Vs + (long long)key * HD, v); },
@@ -112,7 +146,7 @@ __device__ __forceinline__ void suffix_and_store(RowState<HD / 8>& st, const flo
     }
     if (live) {
         const float inv = st.l > 0.f ? 1.0f / st.l : 0.f;
-        T* o = out + row * ld_o + (long long)h * HD + sub * DPT;
+        T* o = out + orow * ld_o + (long long)h * HD + sub * DPT;
 #pragma unroll
         for (int j = 0; j < DPT; ++j) Cvt<T>::st(o + j, st.l > 0.f ? st.acc[j] * inv : 0.f);
     }
@@ -194,7 +228,7 @@ __device__ __forceinline__ void suffix_rows_and_store(float* sAcc, int pitch, fl
 // ------------------------------------------------------------------------------------------------
 // VALU form: any dtype, hd 32 / 64 / 128.  Thread t: query t >> 3, dims (t & 7) * hd/8 ...
 // ------------------------------------------------------------------------------------------------
-template <typename T, int HD, bool ROWS>
+template <typename T, int HD, bool ROWS, bool SFX>
 __global__ __launch_bounds__(256) void attn_decode_shared_valu_kernel(const T* q, long long ld_q, const T* kp, const T* vp, const uint8_t* key_mask,
                                                                       long long ld_mask, const T* ks, const T* vs, const int* sfx_row,
                                                                       long long ld_row, int n_phys, T* out, long long ld_o, int K, int H, int Sp,
@@ -203,10 +237,13 @@ __global__ __launch_bounds__(256) void attn_decode_shared_valu_kernel(const T* q
     __shared__ __attribute__((aligned(16))) float sK[32 * HD];
     __shared__ __attribute__((aligned(16))) float sV[32 * HD];
     __shared__ int sOk[32];
-    const int bh = blockIdx.x, b = bh / H, h = bh % H;
+    int bh, tile;
+    block_of<SFX>(K, Tlen, bh, tile);
+    const int b = bh / H, h = bh % H;
     const int qq = threadIdx.x >> 3, sub = threadIdx.x & 7;
-    const bool live = qq < K;
-    const long long row = (long long)b * K + (live ? qq : K - 1);
+    const QuerySlots<SFX> slots(b, K, Tlen, tile);
+    const bool live = qq < slots.nq;
+    const long long row = slots.qrow(qq);
     float qd[DPT];
     load_chunk<T, DPT>(q + row * ld_q + (long long)h * HD + sub * DPT, qd);
 #pragma unroll
@@ -247,7 +284,7 @@ __global__ __launch_bounds__(256) void attn_decode_shared_valu_kernel(const T* q
         __syncthreads();
         suffix_rows_and_store<T, HD>(sK, HD, sV, sV + 32, q, ld_q, scale, ks, vs, sfx_row, ld_row, n_phys, out, ld_o, b, K, h, H, Tmax, Tlen);
     } else {
-        suffix_and_store<T, HD>(st, qd, ks, vs, out, ld_o, row, h, H, Tmax, Tlen, sub, live);
+        suffix_and_store<T, HD>(st, qd, ks, vs, out, ld_o, slots.srow(qq), row, h, H, Tmax, slots.tlen(qq), sub, live);
     }
 }
 
@@ -280,7 +317,7 @@ template <int HD> __device__ __forceinline__ bf16x8 lds_tr8(const char* tile, in
     return r;
 }
 
-template <int HD, bool ROWS>
+template <int HD, bool ROWS, bool SFX>
 __global__ __launch_bounds__(256) void attn_decode_shared_mfma_kernel(const bf16_t* q, long long ld_q, const bf16_t* kp, const bf16_t* vp,
                                                                       const uint8_t* key_mask, long long ld_mask, const bf16_t* ks,
                                                                       const bf16_t* vs, const int* sfx_row, long long ld_row, int n_phys,
@@ -290,18 +327,21 @@ __global__ __launch_bounds__(256) void attn_decode_shared_mfma_kernel(const bf16
     __shared__ __attribute__((aligned(16))) char sV[4][32 * HD * 2];
     __shared__ float sAcc[32 * PITCH];
     __shared__ float sM[32], sL[32];
-    const int bh = blockIdx.x, b = bh / H, h = bh % H;
+    int bh, tile;
+    block_of<SFX>(K, Tlen, bh, tile);
+    const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, half = lane >> 5;
 
-    // Q^T as the B operand: lane (r, half) holds Q[query r][16c + 8 half + 0..7]; queries >= K are zero columns
+    // Q^T as the B operand: lane (r, half) holds Q[query slot r][16c + 8 half + 0..7]; dead slots are zero columns
+    const QuerySlots<SFX> slots(b, K, Tlen, tile);
     bf16x8 qf[NK];
     {
-        const bf16_t* qrow = q + ((long long)b * K + (r < K ? r : K - 1)) * ld_q + (long long)h * HD + 8 * half;
+        const bf16_t* qrow = q + slots.qrow(r) * ld_q + (long long)h * HD + 8 * half;
 #pragma unroll
         for (int c = 0; c < NK; ++c) {
             u32x4 d = *reinterpret_cast<const u32x4*>(qrow + 16 * c);
-            if (r >= K) d = u32x4{0u, 0u, 0u, 0u};
+            if (r >= slots.nq) d = u32x4{0u, 0u, 0u, 0u};
             qf[c] = __builtin_bit_cast(bf16x8, d);
         }
     }
@@ -414,8 +454,8 @@ __global__ __launch_bounds__(256) void attn_decode_shared_mfma_kernel(const bf16
     }
     // 8 lanes per query: the prompt state, then the row's own suffix
     const int qq = threadIdx.x >> 3, sub = threadIdx.x & 7;
-    const bool live = qq < K;
-    const long long row = (long long)b * K + (live ? qq : K - 1);
+    const bool live = qq < slots.nq;
+    const long long row = slots.qrow(qq);
     RowState<DPT> st;
     st.m = sM[qq]; st.l = sL[qq];
 #pragma unroll
@@ -424,42 +464,48 @@ __global__ __launch_bounds__(256) void attn_decode_shared_mfma_kernel(const bf16
     load_chunk<bf16_t, DPT>(q + row * ld_q + (long long)h * HD + sub * DPT, qd);
 #pragma unroll
     for (int j = 0; j < DPT; ++j) qd[j] *= scale;
-    suffix_and_store<bf16_t, HD>(st, qd, ks, vs, out, ld_o, row, h, H, Tmax, Tlen, sub, live);
+    suffix_and_store<bf16_t, HD>(st, qd, ks, vs, out, ld_o, slots.srow(qq), row, h, H, Tmax, slots.tlen(qq), sub, live);
 }
 
 }  // namespace
 
-// both entry points: sfx_row == nullptr is the own-row suffix of egomi_attn_decode_shared
-static int launch_shared(bool rows, const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
+enum { FORM_OWN = 0, FORM_ROWS = 1, FORM_SUFFIX = 2 };               // egomi_attn_decode_shared, ..._rows, egomi_attn_suffix_shared
+
+// the three entry points.  FORM_SUFFIX: T_len is T, the queries per candidate row, and the grid gains the clip's ceil(K * T / 32) tiles
+static int launch_shared(int form, const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
                          int64_t ld_mask, const void* ksuffix, const void* vsuffix, const int32_t* sfx_row, int64_t ld_row, int n_phys, void* out,
                          int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0, int Tmax, int T_len, float scale, int dtype,
                          egomi_stream_t stream) {
+    const bool rows = form == FORM_ROWS, sfx = form == FORM_SUFFIX;
     if (!q || !kprompt || !vprompt || !out) return EGOMI_E_BADARG;
     if (T_len > 0 && (!ksuffix || !vsuffix)) return EGOMI_E_BADARG;
     if (rows && T_len > 0 && !sfx_row) return EGOMI_E_BADARG;
     if (B <= 0 || H <= 0 || K < 1 || K > 32 || S0 <= 0 || S0 > Sp || T_len < 0 || T_len > Tmax || ld_q % 8 || ld_q < (int64_t)H * hd ||
         ld_o < (int64_t)H * hd)
         return EGOMI_E_SHAPE;
+    const int64_t ntile = sfx ? ((int64_t)K * T_len + 31) / 32 : 1;
+    if (sfx && (T_len < 1 || (int64_t)B * H * ntile > 0x7fffffff)) return EGOMI_E_SHAPE;     // (one workgroup per (clip, head, tile))
     if (rows && T_len > 0 && (ld_row < T_len || n_phys < 1)) return EGOMI_E_SHAPE;
     if (key_mask && ld_mask < S0) return EGOMI_E_SHAPE;
     if (dtype != EGOMI_BF16 && dtype != EGOMI_F32) return EGOMI_E_BADARG;
     if (hd != 32 && hd != 64 && hd != 128) return EGOMI_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-#define SHK(KERNEL, TT)                                                                                                                 \
-    EGOMI_LAUNCH((KERNEL), dim3(B * H), dim3(256), 0, s, (const TT*)q, (long long)ld_q, (const TT*)kprompt, (const TT*)vprompt, key_mask, \
-                 (long long)ld_mask, (const TT*)ksuffix, (const TT*)vsuffix, (const int*)sfx_row, (long long)ld_row, n_phys, (TT*)out,     \
+    const dim3 grid((unsigned)(B * H * ntile));
+#define SHK(KERNEL, TT)                                                                                                            \
+    EGOMI_LAUNCH((KERNEL), grid, dim3(256), 0, s, (const TT*)q, (long long)ld_q, (const TT*)kprompt, (const TT*)vprompt, key_mask,  \
+                 (long long)ld_mask, (const TT*)ksuffix, (const TT*)vsuffix, (const int*)sfx_row, (long long)ld_row, n_phys, (TT*)out, \
                  (long long)ld_o, K, H, Sp, S0, Tmax, T_len, scale)
-#define SHF(ROWS)                                                                         \
-    if (dtype == EGOMI_BF16) {                                                            \
-        if (hd == 128) SHK((attn_decode_shared_mfma_kernel<128, ROWS>), bf16_t);          \
-        else if (hd == 64) SHK((attn_decode_shared_mfma_kernel<64, ROWS>), bf16_t);       \
-        else SHK((attn_decode_shared_valu_kernel<bf16_t, 32, ROWS>), bf16_t);             \
-    } else {                                                                              \
-        if (hd == 128) SHK((attn_decode_shared_valu_kernel<float, 128, ROWS>), float);    \
-        else if (hd == 64) SHK((attn_decode_shared_valu_kernel<float, 64, ROWS>), float); \
-        else SHK((attn_decode_shared_valu_kernel<float, 32, ROWS>), float);               \
+#define SHF(ROWS, SFX)                                                                         \
+    if (dtype == EGOMI_BF16) {                                                                 \
+        if (hd == 128) SHK((attn_decode_shared_mfma_kernel<128, ROWS, SFX>), bf16_t);          \
+        else if (hd == 64) SHK((attn_decode_shared_mfma_kernel<64, ROWS, SFX>), bf16_t);       \
+        else SHK((attn_decode_shared_valu_kernel<bf16_t, 32, ROWS, SFX>), bf16_t);             \
+    } else {                                                                                   \
+        if (hd == 128) SHK((attn_decode_shared_valu_kernel<float, 128, ROWS, SFX>), float);    \
+        else if (hd == 64) SHK((attn_decode_shared_valu_kernel<float, 64, ROWS, SFX>), float); \
+        else SHK((attn_decode_shared_valu_kernel<float, 32, ROWS, SFX>), float);               \
     }
-    if (rows) { SHF(true) } else { SHF(false) }
+    if (rows) { SHF(true, false) } else if (sfx) { SHF(false, true) } else { SHF(false, false) }
 #undef SHF
 #undef SHK
     return egomi_launch_status();
@@ -468,7 +514,7 @@ static int launch_shared(bool rows, const void* q, int64_t ld_q, const void* kpr
 extern "C" int egomi_attn_decode_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
                                         int64_t ld_mask, const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H,
                                         int hd, int Sp, int S0, int Tmax, int T_len, float scale, int dtype, egomi_stream_t stream) {
-    return launch_shared(false, q, ld_q, kprompt, vprompt, key_mask, ld_mask, ksuffix, vsuffix, nullptr, 0, 0, out, ld_o, B, K, H, hd, Sp, S0,
+    return launch_shared(FORM_OWN, q, ld_q, kprompt, vprompt, key_mask, ld_mask, ksuffix, vsuffix, nullptr, 0, 0, out, ld_o, B, K, H, hd, Sp, S0,
                          Tmax, T_len, scale, dtype, stream);
 }
 
@@ -476,6 +522,13 @@ extern "C" int egomi_attn_decode_shared_rows(const void* q, int64_t ld_q, const 
                                              int64_t ld_mask, const void* ksuffix, const void* vsuffix, const int32_t* sfx_row, int64_t ld_row,
                                              int n_phys, void* out, int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0, int Tmax,
                                              int T_len, float scale, int dtype, egomi_stream_t stream) {
-    return launch_shared(true, q, ld_q, kprompt, vprompt, key_mask, ld_mask, ksuffix, vsuffix, sfx_row, ld_row, n_phys, out, ld_o, B, K, H, hd,
-                         Sp, S0, Tmax, T_len, scale, dtype, stream);
+    return launch_shared(FORM_ROWS, q, ld_q, kprompt, vprompt, key_mask, ld_mask, ksuffix, vsuffix, sfx_row, ld_row, n_phys, out, ld_o, B, K, H,
+                         hd, Sp, S0, Tmax, T_len, scale, dtype, stream);
+}
+
+extern "C" int egomi_attn_suffix_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask,
+                                        int64_t ld_mask, const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H,
+                                        int hd, int Sp, int S0, int Tmax, int T, float scale, int dtype, egomi_stream_t stream) {
+    return launch_shared(FORM_SUFFIX, q, ld_q, kprompt, vprompt, key_mask, ld_mask, ksuffix, vsuffix, nullptr, 0, 0, out, ld_o, B, K, H, hd, Sp,
+                         S0, Tmax, T, scale, dtype, stream);
 }

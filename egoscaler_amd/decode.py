@@ -195,6 +195,24 @@ def attn_decode_shared_rows(q, ld_q, kp, vp, key_mask, ks, vs, sfx_row, n_phys, 
          sfx_row.stride(0) if sfx_row is not None else 0, n_phys, out, out.stride(0), B, K, H, hd, Sp, S0, Tmax, T_len, scale, dt(q.dtype), S())
 
 
+def attn_suffix_shared(q, ld_q, kp, vp, key_mask, ks, vs, out, B, K, H, hd, Sp, S0, Tmax, T, scale):
+    """The suffix pass of attn_decode_shared: the B * K * T queries (b * K + j) * T + t over clip b's prompt cache, then keys 0 .. t of
+    suffix row b * K + j (causal)  (include/egomi.h egomi_attn_suffix_shared)."""
+    call("egomi_attn_suffix_shared", q, ld_q, kp, vp, key_mask, key_mask.stride(0) if key_mask is not None else 0, ks, vs, out, out.stride(0), B, K,
+         H, hd, Sp, S0, Tmax, T, scale, dt(q.dtype), S())
+
+
+def candidate_lengths(cand, eos):
+    """The tokens of every candidate that score() counts: cand [..., T] token ids (any device) -> int32 [...]: through the first `eos`
+    inclusive, T where there is none, and T everywhere with eos=None (egomi_token_logprob's `live` rule, restated on whole rows)."""
+    T = cand.shape[-1]
+    if eos is None:
+        return torch.full(cand.shape[:-1], T, dtype=torch.int32, device=cand.device)
+    hit = cand == int(eos)
+    first = hit.int().argmax(-1) + 1                        # (argmax: the first of equal maxima)
+    return torch.where(hit.any(-1), first, torch.full_like(first, T)).to(torch.int32)
+
+
 class DenseCache:
     """The KV cache of B decoder rows in the model's dtype: kc / vc [L, B, H, Smax, hd], one row of Smax keys per decoder row.
 
@@ -308,7 +326,7 @@ def _group_spec(flag, rows, G, B, kv_dtype, max_new_tokens, max_len):
 
 class Decoder:
     def __init__(self, engine, B, max_len, num_beams=1, kv_dtype=None, weight_dtype=None, samples_per_prompt=1, max_new_tokens=None,
-                 split_cache=False):
+                 split_cache=False, score_cache=False):
         """B = rows of every decode step; num_beams > 1: B = items * num_beams logical beams (beam() after prefill(nb=...)).
         self.cache is the KV cache, one object per layout (DenseCache, Fp8Cache, SplitCache above); its tensors also read as self.kc / vc /
         ks / vs / kp / vp / ksfx / vsfx, None where the layout has none.
@@ -325,7 +343,10 @@ class Decoder:
         greedy() are unchanged: same rows, same seed, same draws as the expanded decoder.
         split_cache=True with num_beams = nb > 1 (needs max_new_tokens = Tmax): beam search on a SplitCache with G = nb.  A beam's suffix is
         the path through its ancestors' rows, so step() appends into the row's own suffix row and attends with
-        egomi_attn_decode_shared_rows through kv_row[:, S0:] (egomi_beam_update keeps that table as in the dense layout).  beam() is unchanged."""
+        egomi_attn_decode_shared_rows through kv_row[:, S0:] (egomi_beam_update keeps that table as in the dense layout).  beam() is unchanged.
+        score_cache=True (needs max_new_tokens = Tmax; num_beams == 1, model-dtype cache and weights): the decoder of score(), on the
+        SplitCache with G = samples_per_prompt also when that is 1 (one given candidate per prompt: the ground truth).  Without the
+        flag samples_per_prompt = 1 is the dense decoder, as ever."""
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', not {kv_dtype!r}")
         if weight_dtype not in (None, "fp8", "int4"):
@@ -347,11 +368,16 @@ class Decoder:
             if nb > 32:
                 raise ValueError(f"split_cache supports at most 32 beams, not {num_beams}")
             G = _group_spec("split_cache", "num_beams", nb, B, kv_dtype, max_new_tokens, max_len)
+        if score_cache:
+            if nb != 1 or weight_dtype is not None:
+                raise ValueError("score_cache is for num_beams == 1 on the model's own weights")
+            G = _group_spec("score_cache", "samples_per_prompt", K, B, kv_dtype, max_new_tokens, max_len)
+        split = G > 1 or bool(score_cache)
         self.eng, self.B, self.Smax, self.nb, self.K, self.kv_dtype = engine, B, max_len, nb, K, kv_dtype
         lm = engine.dims.lm
         L, d, Fd, V = lm.num_hidden_layers, lm.hidden_size, lm.intermediate_size, lm.vocab_size
         T, dev = engine.dtype, engine.device
-        self.cache = SplitCache(lm, B, G, max_len, int(max_new_tokens), T, dev) if G > 1 else \
+        self.cache = SplitCache(lm, B, G, max_len, int(max_new_tokens), T, dev) if split else \
             (Fp8Cache if kv_dtype == "fp8" else DenseCache)(lm, B, max_len, T, dev)
         z = lambda *s, dtype=T: torch.zeros(*s, dtype=dtype, device=dev)
         self.x, self.h, self.qkv, self.ao, self.x_mid, self.h2 = z(B, d), z(B, d), z(B, 3 * d), z(B, d), z(B, d), z(B, d)
@@ -366,6 +392,7 @@ class Decoder:
         self.done_buf = z(B, dtype=torch.int32)
         self._graphs, self._scores = {}, {}
         self.lp_tok = self.lp_sum = self.lp_n = self.lp_live = None      # sample() / greedy() with logprobs=True: made on first use (_lp_buffers)
+        self._score_act = None                              # score(): the activations of a suffix pass, made on first use (_score_buffers)
         self.kv_row = None                                  # beam mode: [B, Smax] int32, physical cache row of every key of every logical row
         if self.nb > 1:
             self._beam_buffers()
@@ -665,6 +692,92 @@ class Decoder:
         self.pos = S0 + T_new
         return self.seq, scores
 
+    # -- teacher-forced scoring of given candidates ------------------------------------------------------
+    def _score_buffers(self, rows):
+        """The activations of one suffix pass of `rows` token rows, made on first use and kept while they are large enough."""
+        held = self._score_act
+        if held is None or held["x"].shape[0] < rows:
+            lm, T, dev = self.eng.dims.lm, self.eng.dtype, self.eng.device
+            d, Fd, V = lm.hidden_size, lm.intermediate_size, lm.vocab_size
+            self._score_act = held = None                   # the smaller set goes before the larger one comes
+            z = lambda *s: torch.zeros(*s, dtype=T, device=dev)
+            held = self._score_act = {"x": z(rows, d), "h": z(rows, d), "qkv": z(rows, 3 * d), "ao": z(rows, d), "x_mid": z(rows, d),
+                                      "gu": z(rows, 2 * Fd), "act": z(rows, Fd), "lg": z(rows, V)}
+        return {n: t[:rows] for n, t in held.items()}
+
+    def _suffix_pass(self, tokens, b0, b1):
+        """step() widened to Tq tokens per row: tokens int64 [(b1 - b0) * K, Tq] are suffix tokens 0 .. Tq-1 of the candidates of clips
+        b0 .. b1-1; their k | v go to suffix slots 0 .. Tq-1 and row (r, t) attends over its clip's prompt and its own keys 0 .. t
+        (egomi_attn_suffix_shared).  The unfused products on the weights step() reads (never the quantized ones).
+        -> logits [(b1 - b0) * K * Tq, V], row (r, t) = the distribution of suffix token t + 1."""
+        eng, c = self.eng, self.cache
+        w, lm = eng.w, eng.dims.lm
+        d, Fd, H, hd, L = lm.hidden_size, lm.intermediate_size, lm.num_attention_heads, lm.head_dim, lm.num_hidden_layers
+        K, S0 = c.G, c.S0
+        Rg, Tq = tokens.shape
+        M, r0, r1 = Rg * Tq, b0 * K, b1 * K
+        a = self._score_buffers(M)
+        x, h, qkv, ao, x_mid, gu, act, lg = (a[n] for n in ("x", "h", "qkv", "ao", "x_mid", "gu", "act", "lg"))
+        ops.embed_splice(tokens, w["model.embed_tokens.weight"], None, None, eng.dims.pb.point_token_len, out=x.view(Rg, Tq, d))
+        mask = self.mask[::K][b0:b1]
+        for l in range(L):
+            p = f"model.layers.{l}."
+            ops.rmsnorm(x, w[p + "input_layernorm.weight"], lm.rms_norm_eps, out=h)
+            ops.mm(h, self.wqkv[l], out=qkv, workspace=self.gws)
+            ops.rope_(qkv, eng.cos, eng.sin, M, Tq, S0, 2 * H, hd, 3 * d)
+            ks, vs = c.ksfx[l][r0:r1], c.vsfx[l][r0:r1]
+            kv_append(qkv[:, d:2 * d], qkv[:, 2 * d:], qkv.stride(0), ks, vs, Rg, Tq, H, hd, c.Tmax, 0)
+            attn_suffix_shared(qkv, qkv.stride(0), c.kp[l][b0:b1], c.vp[l][b0:b1], mask, ks, vs, ao, b1 - b0, K, H, hd, c.Sp, S0, c.Tmax, Tq,
+                               hd ** -0.5)
+            ops.mm(ao, self._w(l, "o"), out=x_mid, residual=x, workspace=self.gws)
+            ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, out=h)
+            ops.mm(h, self.wgu[l], out=gu, workspace=self.gws)
+            if eng.gu_il:
+                ops.swiglu_il(gu, act)
+            else:
+                ops.swiglu(gu[:, :Fd], gu[:, Fd:], act)
+            ops.mm(act, self._w(l, "down"), out=x, residual=x_mid, workspace=self.gws)
+        ops.rmsnorm(x, w["model.norm.weight"], lm.rms_norm_eps, out=h)
+        ops.mm(h, w["lm_head.weight"], out=lg)
+        return lg
+
+    def score(self, cand, eos, keep_logits=False, row_budget=16384):
+        """After prefill() on a score_cache decoder: the log-probs of GIVEN suffix tokens cand int64 [B, T] (row r = b * K + j, candidate j
+        of clip b) under teacher forcing, on the model's own weights.  Column 0 is read from the prefill logits; columns 1 .. T-1 come
+        from ONE suffix pass over tokens 0 .. T-2 of every row (_suffix_pass), clips in groups of at most `row_budget` token rows (at
+        least one clip), then one egomi_token_logprob launch per column on that pass's logits (row stride Tq * V) with the buffers, the
+        eos rule and the column order of sample(logprobs=True): self.lp_tok[:, :T] (0 after a row's eos), self.lp_sum, self.lp_n.
+        Columns past the longest candidate (candidate_lengths) are zero for every row: the pass and the launches stop there.
+        keep_logits: -> the pass's logits [B, Tq, V] (Tq = longest candidate - 1; row (r, t) scores token t + 1), else None."""
+        if not self.split or self.nb != 1:
+            raise ValueError("score() needs a Decoder(score_cache=True)")
+        K, S0, dev = self.cache.G, self.pos, self.eng.device
+        R, T = cand.shape
+        if R != self.B or T < 1 or T > self.cache.Tmax:
+            raise ValueError(f"score(): candidates [{R}, {T}] do not fit the decoder's {self.B} rows / {self.cache.Tmax} suffix tokens")
+        cand = cand.to(dev, torch.int64)
+        Tn = int(candidate_lengths(cand, eos).max())        # columns >= Tn count for no row
+        toks = cand.t().contiguous()                        # [T, R]: a column's tokens are contiguous
+        self._lp_buffers()
+        self.lp_tok[:, :T].zero_()
+        live = self.lp_live if eos is not None else None
+        token_logprob(self.lg, toks[0], eos, live, self.lp_tok, 0, self.lp_sum, self.lp_n)
+        Tq, V, kept = Tn - 1, self.lg.shape[1], None
+        if Tq > 0:
+            per = max(1, int(row_budget) // (K * Tq))       # clips per pass
+            if keep_logits:
+                kept = torch.empty(R, Tq, V, dtype=self.lg.dtype, device=dev)
+            for b0 in range(0, R // K, per):
+                b1 = min(R // K, b0 + per)
+                r0, r1 = b0 * K, b1 * K
+                lg = self._suffix_pass(cand[r0:r1, :Tq].contiguous(), b0, b1).view(r1 - r0, Tq, V)
+                for t in range(1, Tn):
+                    token_logprob(lg[:, t - 1], toks[t, r0:r1], eos, None if live is None else live[r0:r1], self.lp_tok[r0:r1], t,
+                                  self.lp_sum[r0:r1], self.lp_n[r0:r1])
+                if keep_logits:
+                    kept[r0:r1] = lg
+        return kept
+
     # -- beam search / beam sampling ---------------------------------------------------------------
     def _beam_buffers(self):
         R, Smax, dev = self.B, self.Smax, self.eng.device
@@ -735,6 +848,6 @@ class Decoder:
         return (self.fin_seq[rows, :S0 + lgen].clone(), self.fin_score[rows].clone(), sc_buf[:n_iter].clone(), bidx[:, :lgen].long())
 
 
-Decoder.split = property(lambda self: self.cache.G > 1, doc="prompt cache + suffix cache instead of the dense one")
+Decoder.split = property(lambda self: isinstance(self.cache, SplitCache), doc="prompt cache + suffix cache instead of the dense one")
 for _n in ("kc", "vc", "ks", "vs", "kp", "vp", "ksfx", "vsfx"):           # the cache's tensors under their names; None where the layout has none
     setattr(Decoder, _n, property(lambda self, _n=_n: getattr(self.cache, _n, None)))

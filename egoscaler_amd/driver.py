@@ -163,7 +163,9 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     "logprob" = the sample the model finds most probable (generate(output_logprobs=True).rank[:, 0]: highest mean token log-prob under the
     raw logits); "medoid" = the most central sample (T.select_medoid: smallest mean ADE to the other parsed samples).  The record gains
     'ADE_sel' / 'FDE_sel' (T.metrics_selected; means over the 'n_sel' clips whose pick parsed) and 'select'; the dump gains one key,
-    "selected": {image id: picked sample index}.  "none" leaves the record and the dump as they are."""
+    "selected": {image id: picked sample index}.  "none" leaves the record and the dump as they are.
+    args.rescore with select "logprob": the rank comes from model.score() on the generated samples (the exact model's teacher-forced
+    log-probs; one more pass over the K suffixes of every clip) instead of the sampling run's own log-probs."""
     dims = model.dims
     K = int(num_samples if num_samples is not None else (getattr(args, "num_samples", 1) or 1))
     if K < 1:
@@ -175,6 +177,9 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
         raise ValueError(f"select must be none, logprob or medoid, not {select!r}")
     if select != "none" and K < 2:
         raise ValueError("--select chooses among samples: it needs --num_samples K > 1")
+    rescore = bool(getattr(args, "rescore", False))
+    if rescore and select != "logprob":
+        raise ValueError("--rescore re-ranks by log-prob: it needs --select logprob")
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
     sample = bool(getattr(args, "val_sample", True))
@@ -245,7 +250,12 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
                 dump[int(ids_h[j])] = [gen[j * K + i].tolist() if n_h[j * K + i] > 0 else None for i in range(K)]
             if select != "none":
                 gen_k, n_k = gen_d.view(len(idx), K, Tn, -1), (n > 0).to(torch.int32).view(len(idx), K) * Tn
-                pick = out.rank[:, 0].contiguous() if select == "logprob" else T.select_medoid(gen_k, n_k)[0]
+                if select == "logprob" and rescore:                          # the same samples, ranked on the model's own weights
+                    rank_k = model.score(prompts, batch["prompt_masks"], batch["pcrgbs"], all_ids.reshape(len(idx), K, -1),
+                                         fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device)).rank
+                else:
+                    rank_k = out.rank if select == "logprob" else None
+                pick = rank_k[:, 0].contiguous() if select == "logprob" else T.select_medoid(gen_k, n_k)[0]
                 sade, sfde = T.metrics_selected(gen_k, n_k, gt, None, pick)
                 sade, sfde, pick = sade.cpu().numpy(), sfde.cpu().numpy(), pick.cpu().numpy()
                 for j in range(len(idx)):
@@ -469,7 +479,14 @@ def parse_args(argv=None):
     ap.add_argument("--data_dir", default=None, help="directory of the split files {train,val,test}.json (dataset.py:37)")
     ap.add_argument("--smooth_traj", action="store_true", help="smoothing_traj on the resampled tracks (dataset.py:39 reads this attribute)")
     ap.add_argument("--split", default="test", help="eval mode: the split to generate for (evaluate.py:89-100 uses 'test')")
-    return ap.parse_args(argv)
+    ap.add_argument("--rescore", action="store_true",
+                    help="validation / eval with --num_samples K > 1 --select logprob: rank the K samples by model.score() (teacher-forced "
+                         "log-probs on the model's own weights, one suffix pass on the shared prompt) instead of the sampling run's own "
+                         "log-probs, which are those of the quantized decoder under --decode_weight_dtype fp8 / int4")
+    a = ap.parse_args(argv)
+    if a.rescore and not (a.num_samples > 1 and a.select == "logprob"):
+        ap.error("--rescore re-ranks sampled trajectories by log-prob: it needs --num_samples K > 1 and --select logprob")
+    return a
 
 
 DESC2TRAJ = {"desc": "Action description: {desc}"}                      # dataset.py:16-19

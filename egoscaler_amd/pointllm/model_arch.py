@@ -330,6 +330,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         dev = self.model.embed_tokens.weight.device
         old = self.engine
         self.__dict__.pop("_decoders", None)                # decoders hold stacked copies of the old engine's weights
+        self.__dict__.pop("_scorers", None)
         self.engine = Engine(self.dims, {k: v.data for k, v in tensors.items()}, dev, dtype)
         self.engine.param_ref = dict(self.named_parameters())
         self.engine.lora = self.lora_cfg
@@ -721,6 +722,67 @@ class TrajPointLLMForCausalLM(nn.Module):
             if n_ret > 1:
                 from ..decode import seq_rank
                 out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B // n_ret, n_ret, float(rank_length_penalty))
+        return out
+
+    @torch.no_grad()
+    def score(self, input_ids, attention_mask, point_clouds, candidates, fps_start=None, eos_token_id="config", rank_length_penalty=1.0,
+              row_budget=16384):
+        """Teacher-forced log-probs of GIVEN trajectories on a shared prompt: candidates int64 [B, K, T] are K token suffixes per prompt
+        (1 <= K <= 32; sampled by another call, another seed or a quantized decoder, proposed by a planner, or the ground truth at K = 1).
+        Every prompt is prefilled once; ONE further pass over tokens 0 .. T-2 of all B * K candidates gives the logits of tokens 1 .. T-1
+        (decode.Decoder.score, egomi_attn_suffix_shared in csrc/shared.hip: each suffix query attends over its clip's prompt cache and
+        its own causal suffix), always on the model's own weights (with merged LoRA adapters), never on quantized ones.  `row_budget`
+        bounds the token rows of one pass: larger batches run clip group by clip group.
+
+        eos_token_id: generate()'s rule ("config", an int or None).  A candidate counts through its first eos; whatever follows it is
+        ignored and scores 0.  None counts all T tokens.  Returns a GenerateOutput with the fields, dtypes and row order (b * K + j) of
+        generate(output_logprobs=True): token_logprobs fp32 [B*K, T], sequences_logprobs fp32 [B*K], sequences_lengths int32 [B*K],
+        sample_scores fp32 [B, K] = sum / length ** rank_length_penalty, rank int32 [B, K]; sequences = the candidates [B*K, T], scores = ().
+        ValueError: K > 32, T < 1, candidates of another rank / dtype / batch, S0 + T beyond max_position_embeddings.
+        NotImplementedError: a list of ragged clouds."""
+        from ..decode import Decoder, seq_rank
+        if isinstance(point_clouds, (list, tuple)):
+            raise NotImplementedError("score() with a list of ragged clouds is not built")
+        ids = input_ids.to(self.engine.device)
+        if not torch.is_tensor(candidates) or candidates.dim() != 3 or candidates.dtype != torch.int64:
+            raise ValueError("score(): `candidates` must be an int64 tensor [B, K, T]")
+        B, S0 = ids.shape
+        Bc, K, T = candidates.shape
+        if Bc != B:
+            raise ValueError(f"score(): {Bc} candidate sets for {B} prompts")
+        if not 1 <= K <= 32:
+            raise ValueError(f"score() supports 1 to 32 candidates per prompt, not {K}")
+        if T < 1:
+            raise ValueError("score() needs candidates of at least one token")
+        if S0 + T > self.dims.lm.max_position_embeddings:
+            raise ValueError(f"score(): prompt ({S0}) + candidate ({T}) tokens exceed max_position_embeddings "
+                             f"({self.dims.lm.max_position_embeddings})")
+        if isinstance(eos_token_id, str):
+            eos_token_id = self.dims.tok.eos
+        eng = self.engine
+        eng.wait_param_updates()
+        if fps_start is None and point_clouds is not None:
+            fps_start = torch.randint(0, point_clouds.shape[1], (B,), dtype=torch.long)
+        if not eng.prepared:
+            eng.prepare()
+        # scorer decoders have a cache of their own (same key rule as _decoder's): generate()'s two cached decoders stay what they were
+        key = (id(eng), eng.prepare_epoch, B, K, S0, T, eng.lora_key())
+        cache = self.__dict__.setdefault("_scorers", {})
+        reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
+        dec = cache.get(key) if reuse else None
+        if dec is None:
+            dec = Decoder(eng, B * K, S0 + T, samples_per_prompt=K, max_new_tokens=T, score_cache=True)
+            if reuse:
+                while len(cache) >= 2:
+                    cache.pop(next(iter(cache)))
+                cache[key] = dec
+        self._prefill_prompts(dec, ids, attention_mask, point_clouds, fps_start, T)
+        cand = candidates.to(eng.device).reshape(B * K, T)
+        dec.score(cand, eos_token_id, row_budget=row_budget)
+        out = GenerateOutput(sequences=cand.clone(), scores=())
+        out.token_logprobs = dec.lp_tok[:, :T].clone()
+        out.sequences_logprobs, out.sequences_lengths = dec.lp_sum.clone(), dec.lp_n.clone()
+        out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B, K, float(rank_length_penalty))
         return out
 
     def _sampling_args(self, eos_token_id, pad_token_id, temperature, repetition_penalty, top_p):

@@ -369,6 +369,22 @@ int egomi_attn_decode_rows(const void* q, int64_t ld_q, const void* kcache, cons
 int egomi_attn_decode_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask, int64_t ld_mask,
                              const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0,
                              int Tmax, int T_len, float scale, int dtype, egomi_stream_t stream);
+/* The suffix pass of egomi_attn_decode_shared: teacher-forced scoring of K given candidates per clip, T suffix tokens each, in ONE launch.
+ * Logical query row (b * K + j) * T + t (clip b, candidate j, suffix position t); 1 <= K <= 32, 1 <= T <= Tmax, 1 <= S0 <= Sp.
+ *   q [B*K*T, ld_q] (16-B aligned rows), out [B*K*T, ld_o]
+ *   kprompt, vprompt [B, H, Sp, hd], key_mask [B, >= S0] u8 or NULL: as above
+ *   ksuffix, vsuffix [B*K, H, Tmax, hd]: keys 0 .. T-1 of every candidate row, already appended
+ *   out[(b*K + j)*T + t] = attention of that query over the visible prompt keys of clip b, then suffix keys 0 .. t of row b*K + j (causal):
+ *            what egomi_attn_decode_shared gives that query at T_len = t + 1, bit for bit.  (A query always sees its own key; a fully
+ *            masked prompt is legal.)
+ * One workgroup per (clip, head, tile of 32 consecutive of the clip's K*T queries): the prompt K/V pass through LDS once per workgroup and
+ * serve the whole tile (bf16 at hd 64 / 128: MFMA; otherwise VALU), then every query walks its own causal cut of its candidate's suffix.
+ * Fixed summation order, no atomics: replays are bit-equal, and the bits of (b, j, t) depend on its own data and (S0, t, hd, dtype) only,
+ * not on K, T, j, b or the queries that share its tile.  Never read: suffix keys > t or >= T, prompt keys >= S0.  Dtypes, head dims and
+ * error codes are those of egomi_attn_decode_shared (T = 0, T > Tmax, more than 2^31 - 1 workgroups: EGOMI_E_SHAPE). */
+int egomi_attn_suffix_shared(const void* q, int64_t ld_q, const void* kprompt, const void* vprompt, const uint8_t* key_mask, int64_t ld_mask,
+                             const void* ksuffix, const void* vsuffix, void* out, int64_t ld_o, int B, int K, int H, int hd, int Sp, int S0,
+                             int Tmax, int T, float scale, int dtype, egomi_stream_t stream);
 /* egomi_attn_decode_shared with the suffix read through a row table: beam search on the prompt / suffix cache layout.  K = beams per clip,
  * logical row r = b * K + j; suffix key t of row r lives in physical suffix row sfx_row[r * ld_row + t] of ksuffix, vsuffix
  * [n_phys, H, Tmax, hd] (a beam's suffix is the path through its ancestors' rows; egomi_beam_update keeps the table).  An entry outside
