@@ -11,6 +11,7 @@ Reference call stack this replaces:
   pointllm/model/pointllm.py:227-228  lm_head ;  train.py:174-184  loss, backward
 """
 import os
+import types
 from typing import Dict
 
 import torch
@@ -30,11 +31,8 @@ class Workspace:
         t = self.bufs.get(name)
         shape = tuple(int(s) for s in shape)
         if t is None or t.shape != shape or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=self.device)
-            self.bufs[name] = t
-            if zero:
-                t.zero_()
-        elif zero:
+            t = self.bufs[name] = torch.empty(shape, dtype=dtype, device=self.device)
+        if zero:
             t.zero_()
         return t
 
@@ -81,6 +79,7 @@ class Engine:
         self.pb_trainer = None
         self.defer_splice_check = False     # hipGraph capture of a whole step: the marker verdict is copied to pinned memory by the graph and
         self.pending_splice = None          # looked at by the caller after the replay (check_pending_splice) instead of inside the forward pass
+        self._splice_host = {}              # elements -> pinned host copy of the splice scan's verdict (_stash_splice_err)
         self.pb_train_mode = False          # set by TrajPointLLMForCausalLM.train(): point backbone in train() mode
         self.prepared_bn_stale = False
         self.fold_stale = False
@@ -412,7 +411,7 @@ class Engine:
             p = f"{pre}blocks.blocks.{i}."
             ops.layernorm(xf, w[p + "norm1.weight"], w[p + "norm1.bias"], pb.ln_eps, add=pos.view(M, D), sum_out=xs, out=h)
             ops.mm(h, w[p + "attn.qkv.weight"], out=qkv)
-            if self.use_fused_attention and T == torch.bfloat16 and hd == 64:
+            if self._fused_attn(hd, 64):
                 ops.attn_fwd(qkv, B, Pn, H, hd, hd ** -0.5, ao, None, causal=False)       # scores never reach HBM
             else:
                 self._attention(qkv, B, Pn, H, hd, ao, False, None, hd ** -0.5, False)
@@ -425,6 +424,37 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------------------------ forward
+    def _fused_attn(self, hd, at):
+        """The flash-style kernels (csrc/attention.hip) run bf16 at the head size they were built for: 128 in the decoder, 64 in PointBERT."""
+        return self.use_fused_attention and self.dtype == torch.bfloat16 and hd == at
+
+    def _buf(self, keep, name, shape, dtype=None):
+        """A buffer that backward will read (keep) is a fresh allocation owned by the saved context; anything else is the named workspace buffer."""
+        dtype = dtype or self.dtype
+        return torch.empty(shape, dtype=dtype, device=self.device) if keep else self.ws.get(name, shape, dtype)
+
+    def _plan(self, B, S, save, loss_from):
+        """Everything a step DECIDES before it computes: made by forward_hidden, read back by backward_hidden from ctx["plan"].
+        defer / defer_b: the K-sliced tail rows of o_proj / down_proj (backward: of the q|k|v / gate|up dgrads) are summed by the RMSNorm that
+        reads them instead of by a combine pass (EGOMI_EPI_SLABS, include/egomi.h); in backward with frozen layers only: the wgrad products
+        between a dgrad and its norm would reuse the slab area.  layers[l]: the rows the layer runs on past its attention and whether SwiGLU and
+        its backward run in the GEMM epilogue at that height; for the windowed top layer the suffix of its own buffers (the lower layers' keep
+        their shape from step to step) and mm = split_k 1: whole 256x256 tiles, in which every element accumulates its K-tiles in the order of
+        the forms the M = B*S products take, so the step keeps the bits of the full path."""
+        lm, bf16 = self.dims.lm, self.dtype == torch.bfloat16
+        d, Fd = lm.hidden_size, lm.intermediate_size
+        fused = self._fused_attn(lm.head_dim, 128)
+        R = self._top_rows(save, loss_from, fused, S)
+        tail, epi, keep_in = self.use_tail_fuse and bf16, self.use_fused_swiglu and bf16 and self.gu_il, self.any_layer_trainable
+
+        def at(rows, top):
+            return types.SimpleNamespace(rows=rows, top=top, sfx="_top" if top else "", mm={"split_k": 1} if top else {},
+                                         swiglu=epi and (2 * Fd) % 256 == 0 and ops.gemm_kernel_id(rows, 2 * Fd, d) == 2,
+                                         swiglu_bwd=epi and Fd % 64 == 0 and ops.gemm_kernel_id(rows, Fd, d) == 2)
+        layers = [at(B * S, False)] * (lm.num_hidden_layers - bool(R)) + [at(B * R, True)] * bool(R)
+        return types.SimpleNamespace(B=B, S=S, M=B * S, R=R, save=save, fused=fused, defer=tail, defer_b=tail and not keep_in, keep_in=keep_in,
+                                     la=self.lora_groups, layers=layers)
+
     def _top_rows(self, save, loss_from, fused, S):
         """The query window R of the top decoder layer (0 = every row): the loss reads the final hidden state at rows >= loss_from of every
         sample only, so below that row the top layer is needed as keys and values alone.  Holds for the TOP layer of a training step whose
@@ -455,6 +485,142 @@ class Engine:
             self._top_key = key
         return ao, lse, d_ao, d_mid
 
+    def _top_window(self, pl, full, compact, scatter=False):
+        """The windowed top layer: the window rows (the last R of every sample) of full-layout arrays [B*S, d] copied into compact ones
+        [B*R, d] (forward: its attention output and its input), or back (scatter; backward: d_ao and d_mid, zero below the window)."""
+        for f, c in zip(full, compact):
+            fw, cw = f.view(pl.B, pl.S, -1)[:, pl.S - pl.R:], c.view(pl.B, pl.R, -1)
+            (fw if scatter else cw).copy_(cw if scatter else fw)
+        return full if scatter else compact
+
+    def _points_fwd(self, input_ids, point_clouds, fps_start, ctx):
+        """Point branch, projector and splice positions (pointllm.py:112-156) -> (projected features [Bc*Pn, d], start_pos, cloud_idx, the
+        pending marker verdict); fills ctx (save) with what _points_bwd needs."""
+        w, pb, T, ws, save = self.w, self.dims.pb, self.dtype, self.ws, ctx is not None
+        Pn = pb.point_token_len
+        if isinstance(point_clouds, (list, tuple)):                          # pointllm.py:117-122
+            fl = [self.point_backbone(pc[None].to(self.device, torch.float32), [int(fps_start[i])]) for i, pc in enumerate(point_clouds)]
+            feats = torch.cat(fl, 0)
+        elif save and self.pb_train_mode and self.pb_trainable:
+            # --unfreeze_pc_encoder in train(): batch-statistics BatchNorm, DropPath, activations kept for backward
+            from .pointbert_train import PointBackboneTrainer
+            if self.pb_trainer is None:
+                self.pb_trainer = PointBackboneTrainer(self)
+            drop = self.pb_drop_override if self.pb_drop_override is not None else self.pb_trainer.drop_scales(point_clouds.shape[0])
+            self.pb_drop_override = None                # one forward pass only (tests hand in recorded DropPath draws: [depth, 2, B] scales)
+            feats, ctx["pb_ctx"] = self.pb_trainer.forward(point_clouds.to(self.device, torch.float32), fps_start, drop)
+            self.prepared_bn_stale = True
+        else:
+            feats = self.point_backbone(point_clouds.to(self.device, torch.float32), fps_start)
+        Bc = feats.shape[0]                      # clouds given: one per sample in EgoScaler's data; the splice follows the reference's running
+        cur = feats.reshape(Bc * Pn, pb.trans_dim)   # cloud index, so a batch whose samples hold several segments may bring more (pointllm.py:135-156)
+        acts = [cur]
+        nh = len(pb.projection_hidden_dim)
+        for j in range(nh):                                                    # pointllm.py:67-81
+            Wj, bj = w[f"model.point_proj.{2 * j}.weight"], w[f"model.point_proj.{2 * j}.bias"]
+            pre_act = ops.mm(cur, Wj, bias=bj, out=ws.get(f"pp_pre{j}", (Bc * Pn, Wj.shape[0]), T))
+            cur = ops.gelu(pre_act, out=ws.get(f"pp_act{j}", (Bc * Pn, Wj.shape[0]), T))
+            acts += [pre_act, cur]
+        Wl, bl = w[f"model.point_proj.{2 * nh}.weight"], w[f"model.point_proj.{2 * nh}.bias"]
+        feats_proj = ops.mm(cur, Wl, bias=bl, out=ws.get("pp_out", (Bc * Pn, Wl.shape[0]), T))
+        start_pos, err, cloud_idx = ops.splice_scan(input_ids, self.dims.tok, Pn, Bc)
+        # the reference checks the markers on the host right here (pointllm.py:137-151) and stalls the stream for it.  The scan kernel already
+        # answers an inconsistent sample with start_pos = -1 (= text only: nothing downstream reads out of range), so the verdict is copied to pinned
+        # memory now and looked at when the rest of the forward pass has been queued: the same exceptions from the same call, without 0.6 ms of idle GPU
+        pending_err = self._stash_splice_err(err)
+        if save:
+            ctx["pp_acts"] = acts
+        return feats_proj, start_pos, cloud_idx, pending_err, Bc
+
+    def _qkv_fwd(self, l, h, qkv, defer):
+        """q|k|v = h [Wq;Wk;Wv]^T: one product over the stack (a view of the parameters or a concatenation: prepare()), else one per
+        weight.  -> the product's deferred tail (defer) or None."""
+        if l in self.wqkv:
+            r = ops.mm(h, self.wqkv[l], out=qkv, defer_tail=defer)
+            return r[1] if defer else None
+        d = h.shape[1]
+        for i, n in enumerate("qkv"):
+            ops.mm(h, self.w[f"model.layers.{l}.self_attn.{n}_proj.weight"], out=qkv[:, i * d:(i + 1) * d])
+        return None
+
+    def _gate_up_fwd(self, l, h2, gu, act, lw, lT):
+        """gate|up = h2 [Wgate;Wup]^T, act = silu(gate) * up, by the form prepare() left the weights in: the interleaved-32 stack (act leaves the GEMM
+        epilogue where the plan allows; gu is kept for backward), the plain stack, or one product each.  -> whether gu is interleaved."""
+        Fd, il, adapted = act.shape[1], l in self.wgu and self.gu_il, lT is not None and "gu" in lT
+        if il and lw.swiglu and not adapted:
+            ops.mm(h2, self.wgu[l], out=gu, swiglu_out=act, **lw.mm)
+            return il
+        if il:
+            ops.mm(h2, self.wgu[l], out=gu, **lw.mm)
+        elif l in self.wgu or l in self.wgu_cat:
+            ops.mm(h2, self.wgu[l] if l in self.wgu else self.wgu_cat[l], out=gu)
+        else:
+            ops.mm(h2, self.w[f"model.layers.{l}.mlp.gate_proj.weight"], out=gu[:, :Fd])
+            ops.mm(h2, self.w[f"model.layers.{l}.mlp.up_proj.weight"], out=gu[:, Fd:])
+        if adapted:
+            self._lora_fwd(l, "gu", h2, gu, lT["gu"], il=il)
+        if il:
+            ops.swiglu_il(gu, act)
+        else:
+            ops.swiglu(gu[:, :Fd], gu[:, Fd:], act)
+        return il
+
+    def _res_proj_fwd(self, l, pl, grp, name, a, res, out, lT):
+        """out = a W^T + res for o_proj / down_proj (+ its adapter) -> the deferred tail (the norm that reads `out` sums it, with `res`) or None."""
+        W, mm = self.w[f"model.layers.{l}.{name}.weight"], pl.layers[l].mm
+        if pl.defer and grp not in pl.la:
+            return ops.mm(a, W, out=out, residual=res, defer_tail=True, **mm)[1]
+        ops.mm(a, W, out=out, residual=res, **mm)
+        if grp in pl.la:
+            self._lora_fwd(l, grp, a, out, lT[grp])
+        return None
+
+    def _layer_fwd(self, l, x, pl, key_mask, kv_sink, pend):
+        """Decoder layer l on x [M, d] -> (its output [rows, d], pend, what backward needs of it (save) or None).  pend = (tail, residual): the
+        K-sliced tail rows of the down_proj that made x (and the result) are still slabs, summed by the next norm that reads them."""
+        w, lm, T, lw, la, save = self.w, self.dims.lm, self.dtype, pl.layers[l], pl.la, pl.save
+        d, Fd, H, hd = lm.hidden_size, lm.intermediate_size, lm.num_attention_heads, lm.head_dim
+        B, S, M, Ml, top = pl.B, pl.S, pl.M, lw.rows, lw.top
+        p, scale, keep = f"model.layers.{l}.", hd ** -0.5, save and not top and pl.keep_in
+        lT = {g: self._buf(save, f"lora_T_{g}", (M, len(ts) * self.lora.r)) for g, ts in la.items()}    # T = x A^T of every adapted input: kept for backward
+        rstd1, rstd2 = (torch.empty(n, dtype=torch.float32, device=self.device) if save else None for n in (M, Ml))
+        qkv, gu = self._buf(save, "qkv", (M, 3 * d)), self._buf(save, "gu", (Ml, 2 * Fd))
+        h = self._buf(save and (pl.keep_in or "qkv" in la), "h", (M, d))
+        if top:                                            # frozen, no adapters: nothing past the attention is kept for a weight gradient
+            ao, lse = self._top_buffers(B, S, pl.R)[:2]
+        else:                                              # the fused kernel's output and LSE are kept for backward
+            ao = self._buf(keep or (save and (pl.fused or "o" in la)), "ao", (M, d))
+            lse = self._buf(save, "att_lse", (B, H, S), torch.float32) if pl.fused else None
+        h2 = self._buf(keep or (save and not top and "gu" in la), "h2" + lw.sfx, (Ml, d))
+        act = self._buf(keep or (save and not top and "down" in la), "act" + lw.sfx, (Ml, Fd))
+        x_mid, x_out = self._buf(save, "x_mid", (Ml, d)), self._buf(save, f"x_out{l & 1}", (Ml, d))
+        lc = {"x_in": x, "rstd1": rstd1, "rstd2": rstd2, "qkv": qkv, "gu": gu} if save else None
+        # ---- attention
+        ops.rmsnorm(x, w[p + "input_layernorm.weight"], lm.rms_norm_eps, rstd=rstd1, out=h, tail=pend[0], tail_residual=pend[1])
+        t_qkv = self._qkv_fwd(l, h, qkv, pl.defer and "qkv" not in la)
+        if "qkv" in la:                                    # adapters: before RoPE, as PEFT wraps q_proj / k_proj / v_proj
+            self._lora_fwd(l, "qkv", h, qkv, lT["qkv"])
+        if t_qkv is not None:
+            ops.rope_qkv_tail_(qkv, self.cos, self.sin, M, S, 0, H, hd, 3 * d, t_qkv)
+        else:
+            ops.rope_(qkv, self.cos, self.sin, M, S, 0, 2 * H, hd, 3 * d)      # q and k heads are adjacent columns
+        if kv_sink is not None:
+            kv_sink(l, qkv, B, S)
+        Pm = None
+        if pl.fused:                                       # fused flash-style kernel: scores never reach HBM
+            ops.attn_fwd(qkv, B, S, H, hd, scale, ao, lse, causal=True, key_mask=key_mask, q_rows=pl.R if top else 0)
+        else:
+            Pm = self._attention(qkv, B, S, H, hd, ao, True, key_mask, scale, save)
+        ao_w, x = self._top_window(pl, (ao, x), [self.ws.get(n, (Ml, d), T) for n in ("ao_rows_top", "x_rows_top")]) if top else (ao, x)
+        t_o = self._res_proj_fwd(l, pl, "o", "self_attn.o_proj", ao_w, x, x_mid, lT)
+        # ---- MLP
+        ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, rstd=rstd2, out=h2, tail=t_o, tail_residual=x)
+        gu_il = self._gate_up_fwd(l, h2, gu, act, lw, lT)
+        t_down = self._res_proj_fwd(l, pl, "down", "mlp.down_proj", act, x_mid, x_out, lT)     # ... deferred to the NEXT layer's input norm (or the final norm)
+        if save:
+            lc.update(P=Pm, lse=lse, x_mid=x_mid, h=h, ao=ao, h2=h2, act=act, lora_T=lT, gu_il=gu_il)
+        return x_out, (t_down, x_mid), lc
+
     def forward_hidden(self, input_ids, attention_mask, point_clouds, fps_start, save=True, kv_sink=None, loss_from=None):
         """-> final-normed hidden [B*S, d]; fills self.ctx for backward when save=True.
         kv_sink(layer, qkv, B, S): optional prefill hook that receives the post-RoPE q|k|v buffer of every
@@ -465,195 +631,37 @@ class Engine:
         backward_hidden takes the gradient in the same layout.  self.top_rows_taken reports R (0: every row ran, full layout)."""
         if not self.prepared:
             self.prepare()
-        w, dims, T, ws = self.w, self.dims, self.dtype, self.ws
-        lm, pb, tok = dims.lm, dims.pb, dims.tok
+        w, lm, T, d = self.w, self.dims.lm, self.dtype, self.dims.lm.hidden_size
         if input_ids.dtype != torch.int64 or not input_ids.is_contiguous():
             input_ids = input_ids.to(torch.int64).contiguous()      # kernels index ids as a dense [B,S] int64 array
         B, S = input_ids.shape
-        d, Fd, H, hd, L = lm.hidden_size, lm.intermediate_size, lm.num_attention_heads, lm.head_dim, lm.num_hidden_layers
-        M = B * S
-        Pn = pb.point_token_len
         ctx = {"B": B, "S": S, "ids": input_ids, "layers": []} if save else None
-        past = 0
         self.wait_params("pre")
-        # ---- point branch (pointllm.py:112-129): only when S != 1 (prefill / training)
-        feats_proj, start_pos, pending_err, cloud_idx, Bc = None, None, None, None, 0
-        if point_clouds is not None and S != 1:
-            if isinstance(point_clouds, (list, tuple)):                          # pointllm.py:117-122
-                fl = [self.point_backbone(pc[None].to(self.device, torch.float32), [int(fps_start[i])]) for i, pc in enumerate(point_clouds)]
-                feats = torch.cat(fl, 0)
-            elif save and self.pb_train_mode and self.pb_trainable:
-                # --unfreeze_pc_encoder in train(): batch-statistics BatchNorm, DropPath, activations kept for backward
-                from .pointbert_train import PointBackboneTrainer
-                if self.pb_trainer is None:
-                    self.pb_trainer = PointBackboneTrainer(self)
-                drop = self.pb_drop_override if self.pb_drop_override is not None else self.pb_trainer.drop_scales(point_clouds.shape[0])
-                self.pb_drop_override = None                # one forward pass only (tests hand in recorded DropPath draws: [depth, 2, B] scales)
-                feats, pb_ctx = self.pb_trainer.forward(point_clouds.to(self.device, torch.float32), fps_start, drop)
-                ctx["pb_ctx"] = pb_ctx
-                self.prepared_bn_stale = True
-            else:
-                feats = self.point_backbone(point_clouds.to(self.device, torch.float32), fps_start)
-            Bc = feats.shape[0]                      # clouds given: one per sample in EgoScaler's data; the splice follows the reference's running
-            fm = feats.reshape(Bc * Pn, pb.trans_dim)   # cloud index, so a batch whose samples hold several segments may bring more (pointllm.py:135-156)
-            acts = [fm]
-            nh = len(pb.projection_hidden_dim)
-            cur = fm
-            for j in range(nh):                                                    # pointllm.py:67-81
-                Wj, bj = w[f"model.point_proj.{2 * j}.weight"], w[f"model.point_proj.{2 * j}.bias"]
-                pre_act = ops.mm(cur, Wj, bias=bj, out=ws.get(f"pp_pre{j}", (Bc * Pn, Wj.shape[0]), T))
-                cur = ops.gelu(pre_act, out=ws.get(f"pp_act{j}", (Bc * Pn, Wj.shape[0]), T))
-                acts += [pre_act, cur]
-            Wl, bl = w[f"model.point_proj.{2 * nh}.weight"], w[f"model.point_proj.{2 * nh}.bias"]
-            feats_proj = ops.mm(cur, Wl, bias=bl, out=ws.get("pp_out", (Bc * Pn, d), T))
-            sp, err, cloud_idx = ops.splice_scan(input_ids, tok, Pn, Bc)
-            # the reference checks the markers on the host right here (pointllm.py:137-151) and stalls the stream for it.  The
-            # scan kernel already answers an inconsistent sample with start_pos = -1 (= text only: nothing downstream reads out
-            # of range), so the verdict is copied to pinned memory now and looked at when the rest of the forward pass has been
-            # queued — the same exceptions, raised by the same call, without 0.6 ms of idle GPU per step
-            pending_err = self._stash_splice_err(err)
-            start_pos = sp
-            if save:
-                ctx["pp_acts"] = acts
+        feats_proj, start_pos, cloud_idx, pending_err, Bc = None, None, None, None, 0
+        if point_clouds is not None and S != 1:                     # the point branch runs in prefill / training only (pointllm.py:112-129)
+            feats_proj, start_pos, cloud_idx, pending_err, Bc = self._points_fwd(input_ids, point_clouds, fps_start, ctx)
         if save:
-            ctx["start_pos"], ctx["cloud_idx"], ctx["n_clouds"] = start_pos, cloud_idx, Bc
-            ctx["has_points"] = feats_proj is not None
-        x = ws.get("x_emb", (B, S, d), T) if not save else torch.empty(B, S, d, dtype=T, device=self.device)
+            ctx.update(start_pos=start_pos, cloud_idx=cloud_idx, n_clouds=Bc, has_points=feats_proj is not None)
+        x = self._buf(save, "x_emb", (B, S, d))
         self.wait_params("embed")
-        ops.embed_splice(input_ids, w["model.embed_tokens.weight"], feats_proj, start_pos, Pn, out=x, cloud_idx=cloud_idx)
-        x = x.view(M, d)
-        key_mask = None
-        if attention_mask is not None:
-            key_mask = attention_mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        scale = hd ** -0.5
-        fused = self.use_fused_attention and T == torch.bfloat16 and hd == 128
-        # the K-sliced tail rows of o_proj / down_proj (and, in backward, of the qkv / gate|up dgrads) are summed by the RMSNorm
-        # kernel that reads them instead of by a combine pass (EGOMI_EPI_SLABS, include/egomi.h).  EGOMI_NO_TAIL_FUSE=1: A/B switch
-        defer = self.use_tail_fuse and T == torch.bfloat16
-        pend = pend_res = None
-        fuse_swiglu_all = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and (2 * Fd) % 256 == 0
-        fuse_swiglu = fuse_swiglu_all and ops.gemm_kernel_id(M, 2 * Fd, d) == 2
-        la = self.lora_groups
-        R = self._top_rows(save, loss_from, fused, S)
+        ops.embed_splice(input_ids, w["model.embed_tokens.weight"], feats_proj, start_pos, self.dims.pb.point_token_len, out=x, cloud_idx=cloud_idx)
+        x = x.view(B * S, d)
+        key_mask = None if attention_mask is None else attention_mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        pl = self._plan(B, S, save, loss_from)
         if save:
-            self.top_rows_taken = R
-        for l in range(L):
-            p = f"model.layers.{l}."
+            self.top_rows_taken = pl.R
+        pend = (None, None)
+        for l in range(lm.num_hidden_layers):
             self.wait_params(l)
-            top = R > 0 and l == L - 1                         # the windowed top layer: Ml = B*R compact rows past the attention
-            Ml = B * R if top else M
-            lT = {}                                            # T = x A^T of every adapted input: kept for backward
-            for g, ts in la.items():
-                shp = (M, len(ts) * self.lora.r)
-                lT[g] = torch.empty(shp, dtype=T, device=self.device) if save else ws.get(f"lora_T_{g}", shp, T)
+            x, pend, lc = self._layer_fwd(l, x, pl, key_mask, kv_sink, pend)
             if save:
-                lc = {"x_in": x, "rstd1": torch.empty(M, dtype=torch.float32, device=self.device),
-                      "rstd2": torch.empty(Ml, dtype=torch.float32, device=self.device),
-                      "qkv": torch.empty(M, 3 * d, dtype=T, device=self.device),
-                      "gu": torch.empty(Ml, 2 * Fd, dtype=T, device=self.device)}
-                keep_in = self.any_layer_trainable
-                h = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or "qkv" in la) else ws.get("h", (M, d), T)
-                if top:                                        # frozen, no adapters: nothing past the attention is kept for a weight gradient
-                    ao, lse_top = self._top_buffers(B, S, R)[:2]
-                    h2, act = ws.get("h2_top", (Ml, d), T), ws.get("act_top", (Ml, Fd), T)
-                else:
-                    ao = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or fused or "o" in la) else ws.get("ao", (M, d), T)
-                    h2 = torch.empty(M, d, dtype=T, device=self.device) if (keep_in or "gu" in la) else ws.get("h2", (M, d), T)
-                    act = torch.empty(M, Fd, dtype=T, device=self.device) if (keep_in or "down" in la) else ws.get("act", (M, Fd), T)
-                x_mid = torch.empty(Ml, d, dtype=T, device=self.device)
-                x_out = torch.empty(Ml, d, dtype=T, device=self.device)
-                qkv, gu, rstd1, rstd2 = lc["qkv"], lc["gu"], lc["rstd1"], lc["rstd2"]
-            else:
-                h, ao, h2, act = ws.get("h", (M, d), T), ws.get("ao", (M, d), T), ws.get("h2", (M, d), T), ws.get("act", (M, Fd), T)
-                x_mid, x_out = ws.get("x_mid", (M, d), T), ws.get(f"x_out{l & 1}", (M, d), T)
-                qkv, gu, rstd1, rstd2 = ws.get("qkv", (M, 3 * d), T), ws.get("gu", (M, 2 * Fd), T), None, None
-            ops.rmsnorm(x, w[p + "input_layernorm.weight"], lm.rms_norm_eps, rstd=rstd1, out=h, tail=pend, tail_residual=pend_res)
-            pend = pend_res = None
-            t_qkv = None
-            if l in self.wqkv:
-                if defer and "qkv" not in la:
-                    _, t_qkv = ops.mm(h, self.wqkv[l], out=qkv, defer_tail=True)
-                else:
-                    ops.mm(h, self.wqkv[l], out=qkv)
-            else:
-                ops.mm(h, w[p + "self_attn.q_proj.weight"], out=qkv[:, :d])
-                ops.mm(h, w[p + "self_attn.k_proj.weight"], out=qkv[:, d:2 * d])
-                ops.mm(h, w[p + "self_attn.v_proj.weight"], out=qkv[:, 2 * d:])
-            if "qkv" in la:                                    # adapters: before RoPE, as PEFT wraps q_proj / k_proj / v_proj
-                self._lora_fwd(l, "qkv", h, qkv, lT["qkv"])
-            if t_qkv is not None:
-                ops.rope_qkv_tail_(qkv, self.cos, self.sin, M, S, past, H, hd, 3 * d, t_qkv)
-            else:
-                ops.rope_(qkv, self.cos, self.sin, M, S, past, 2 * H, hd, 3 * d)      # q and k heads are adjacent columns
-            if kv_sink is not None:
-                kv_sink(l, qkv, B, S)
-            lse = None
-            if fused:
-                # fused flash-style kernel: scores never reach HBM; LSE (and the output) are kept for backward
-                Pm = None
-                if top:
-                    lse = lse_top
-                else:
-                    lse = torch.empty(B, H, S, dtype=torch.float32, device=self.device) if save else ws.get("att_lse", (B, H, S), torch.float32)
-                ops.attn_fwd(qkv, B, S, H, hd, scale, ao, lse, causal=True, key_mask=key_mask, q_rows=R if top else 0)
-            else:
-                Pm = self._attention(qkv, B, S, H, hd, ao, True, key_mask, scale, save)
-            ao_full = ao
-            # the windowed top layer's products run whole 256x256 tiles (split_k = 1: no K-sliced rows, no deferred tail), in which every
-            # element accumulates its K-tiles in the order of the forms the M = B*S products take: the step keeps the bits of the full path
-            wt = {"split_k": 1} if top else {}
-            if top:                                            # the window rows of the attention output and of the layer input, compact
-                ao = ws.get("ao_rows_top", (Ml, d), T)
-                ao.view(B, R, d).copy_(ao_full.view(B, S, d)[:, S - R:])
-                xw = ws.get("x_rows_top", (Ml, d), T)
-                xw.view(B, R, d).copy_(x.view(B, S, d)[:, S - R:])
-                x = xw
-            if defer and "o" not in la:                        # the K-sliced tail rows of the product are summed by the norm that reads them
-                _, t_o = ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x, defer_tail=True, **wt)
-                ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, rstd=rstd2, out=h2, tail=t_o, tail_residual=x)
-            else:
-                ops.mm(ao, w[p + "self_attn.o_proj.weight"], out=x_mid, residual=x, **wt)
-                if "o" in la:
-                    self._lora_fwd(l, "o", ao, x_mid, lT["o"])
-                ops.rmsnorm(x_mid, w[p + "post_attention_layernorm.weight"], lm.rms_norm_eps, rstd=rstd2, out=h2)
-            gu_il = l in self.wgu and self.gu_il
-            if top:
-                fuse_swiglu = fuse_swiglu_all and ops.gemm_kernel_id(Ml, 2 * Fd, d) == 2
-            if gu_il:
-                if fuse_swiglu and "gu" not in la:
-                    ops.mm(h2, self.wgu[l], out=gu, swiglu_out=act, **wt)    # act leaves the GEMM epilogue; gu (interleaved-32) is kept for backward
-                else:
-                    ops.mm(h2, self.wgu[l], out=gu, **wt)
-                    if "gu" in la:
-                        self._lora_fwd(l, "gu", h2, gu, lT["gu"], il=True)
-                    ops.swiglu_il(gu, act)
-            else:
-                if l in self.wgu or l in self.wgu_cat:
-                    ops.mm(h2, self.wgu[l] if l in self.wgu else self.wgu_cat[l], out=gu)
-                else:
-                    ops.mm(h2, w[p + "mlp.gate_proj.weight"], out=gu[:, :Fd])
-                    ops.mm(h2, w[p + "mlp.up_proj.weight"], out=gu[:, Fd:])
-                if "gu" in la:
-                    self._lora_fwd(l, "gu", h2, gu, lT["gu"])
-                ops.swiglu(gu[:, :Fd], gu[:, Fd:], act)
-            if defer and "down" not in la:                     # ... here by the NEXT layer's input norm (or the final norm)
-                _, pend = ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid, defer_tail=True, **wt)
-                pend_res = x_mid
-            else:
-                ops.mm(act, w[p + "mlp.down_proj.weight"], out=x_out, residual=x_mid, **wt)
-                if "down" in la:
-                    self._lora_fwd(l, "down", act, x_out, lT["down"])
-            if save:
-                lc.update(P=Pm, lse=lse, x_mid=x_mid, h=h, ao=ao_full, h2=h2, act=act, lora_T=lT, gu_il=gu_il)
                 ctx["layers"].append(lc)
-            x = x_out
         self.wait_params("post")
-        Mf = x.shape[0]                                        # B*R after a windowed top layer
-        rstd_f = torch.empty(Mf, dtype=torch.float32, device=self.device) if save else None
-        hn = torch.empty(Mf, d, dtype=T, device=self.device)
-        ops.rmsnorm(x, w["model.norm.weight"], lm.rms_norm_eps, rstd=rstd_f, out=hn, tail=pend, tail_residual=pend_res)
+        rstd_f = torch.empty(x.shape[0], dtype=torch.float32, device=self.device) if save else None
+        hn = torch.empty(x.shape, dtype=T, device=self.device)          # [B*R, d] after a windowed top layer
+        ops.rmsnorm(x, w["model.norm.weight"], lm.rms_norm_eps, rstd=rstd_f, out=hn, tail=pend[0], tail_residual=pend[1])
         if save:
-            ctx.update(x_last=x, rstd_f=rstd_f, hn=hn, key_mask=key_mask, top_rows=R)
+            ctx.update(x_last=x, rstd_f=rstd_f, hn=hn, key_mask=key_mask, top_rows=pl.R, plan=pl)
             self.ctx = ctx
         if self.defer_splice_check:
             self.pending_splice = pending_err
@@ -662,10 +670,8 @@ class Engine:
         return hn
 
     def _stash_splice_err(self, err):
-        host = self._splice_host.get(err.numel()) if hasattr(self, "_splice_host") else None
+        host = self._splice_host.get(err.numel())
         if host is None:
-            if not hasattr(self, "_splice_host"):
-                self._splice_host = {}
             host = self._splice_host[err.numel()] = torch.empty(err.numel(), dtype=torch.int32).pin_memory() if err.is_cuda else torch.empty(err.numel(), dtype=torch.int32)
         host.copy_(err, non_blocking=True)
         ev = None
@@ -891,143 +897,137 @@ class Engine:
         g[:, :R - 1] = d_hs.view(B, R - 1, d)
         return g.view(B * R, d)
 
+    def _stacked_dgrad(self, dY, wT, stack, names, out, defer, **mm):
+        """out = dY [W_1; ...; W_n] for projections that share their input (q|k|v, gate|up), by the form prepare() left the weights in: their K-concatenated
+        transposes (frozen: one long-K product, its tail deferred where asked), the stack in place on the k-major kernel, or one product each.  -> (out, tail)"""
+        if wT is not None:
+            r = ops.mm(dY, wT, out=out, defer_tail=defer, **mm)
+            return r if defer else (r, None)
+        if stack is not None:
+            return self._dgrad_w(dY, stack, out), None
+        c = 0
+        for n in names:
+            N = self.w[n].shape[0]
+            self._dgrad(dY[:, c:c + N], n, out, residual=out if c else None)
+            c += N
+        return out, None
+
+    def _mlp_bwd(self, l, dx, lc, pl):
+        """MLP half of decoder layer l: dx [rows, d] at the layer's output -> the gradient at x_mid."""
+        w, lm, T, ws, lw, la = self.w, self.dims.lm, self.dtype, self.ws, pl.layers[l], pl.la
+        d, Fd, Ml, sfx, mm = lm.hidden_size, lm.intermediate_size, lw.rows, lw.sfx, lw.mm
+        p, gu, lT = f"model.layers.{l}.mlp.", lc["gu"], lc["lora_T"]
+        wguT = self.wguT.get(l) if self.prepared else None
+        wt_down = self.wT.get(p + "down_proj.weight") if self.prepared else None
+        dgu = ws.get("dgu" + sfx, (Ml, 2 * Fd), T)
+        if lw.swiglu_bwd and wt_down is not None and wguT is not None and "down" not in la:
+            # d(act) = dx . W_down never reaches memory: the GEMM epilogue reads gate|up and writes d(gate|up) (EGOMI_EPI_SWIGLU_BWD)
+            ops.mm(dx, wt_down, out=dgu, swiglu_bwd_gu=gu, **mm)
+        else:
+            d_act = self._dgrad(dx, p + "down_proj.weight", ws.get("d_act" + sfx, (Ml, Fd), T), **mm)
+            if "down" in la:
+                self._lora_bwd(l, "down", dx, lc["act"], d_act, lT["down"])
+            if wguT is not None and self.gu_il:
+                ops.swiglu_il_bwd(d_act, gu, dgu)                           # gu / dgu in the interleaved-32 layout of the stacked weight
+            else:
+                ops.swiglu_bwd(d_act, gu[:, :Fd], gu[:, Fd:], dgu[:, :Fd], dgu[:, Fd:])
+        self._wgrad(p + "down_proj.weight", dx, lc["act"])
+        names = [p + "gate_proj.weight", p + "up_proj.weight"]
+        d_h2, t_h2 = self._stacked_dgrad(dgu, wguT, self.wgu_cat.get(l) if self.prepared else None, names, ws.get("d_h" + sfx, (Ml, d), T),
+                                         pl.defer_b and "gu" not in la, **mm)
+        if "gu" in la:
+            self._lora_bwd(l, "gu", dgu, lc["h2"], d_h2, lT["gu"], il=lc["gu_il"])
+        self._wgrad_stacked(names, dgu, lc["h2"])
+        n2 = f"model.layers.{l}.post_attention_layernorm.weight"
+        return ops.rmsnorm_bwd(d_h2, lc["x_mid"], w[n2], lc["rstd2"], dx_add=dx, dw=self.grad_buffer(n2) if n2 in self.trainable else None,
+                               out=ws.get("dx_b" + sfx, (Ml, d), T), tail=t_h2)
+
+    def _attn_half_bwd(self, l, d_mid, lc, pl, key_mask):
+        """Attention half of decoder layer l: d_mid [rows, d] at x_mid -> the gradient at the layer's input [M, d]."""
+        w, lm, T, ws, lw, la = self.w, self.dims.lm, self.dtype, self.ws, pl.layers[l], pl.la
+        d, H, hd, B, S, M = lm.hidden_size, lm.num_attention_heads, lm.head_dim, pl.B, pl.S, pl.M
+        p, qkv, lT = f"model.layers.{l}.self_attn.", lc["qkv"], lc["lora_T"]
+        d_ao = self._dgrad(d_mid, p + "o_proj.weight", ws.get("d_ao" + ("_rows_top" if lw.top else ""), (lw.rows, d), T), **lw.mm)
+        if "o" in la:
+            self._lora_bwd(l, "o", d_mid, lc["ao"], d_ao, lT["o"])
+        self._wgrad(p + "o_proj.weight", d_mid, lc["ao"])
+        if lw.top:
+            d_ao, d_mid = self._top_window(pl, self._top_buffers(B, S, pl.R)[2:], (d_ao, d_mid), scatter=True)
+        dqkv = ws.get("dqkv", (M, 3 * d), T)
+        if lc["lse"] is not None:
+            # dq, dk leave the kernels already rotated back (the inverse RoPE pass is fused into their epilogues)
+            ops.attn_bwd(qkv, lc["ao"], lc["lse"], d_ao, dqkv, ws.get("att_delta", (B, H, S), torch.float32), B, S, H, hd, hd ** -0.5,
+                         causal=True, key_mask=key_mask, rope=(self.cos, self.sin), q_rows=pl.R if lw.top else 0)
+        else:
+            self._attention_bwd(qkv, lc["P"], d_ao, dqkv, B, S, H, hd, hd ** -0.5)
+            ops.rope_(dqkv, self.cos, self.sin, M, S, 0, 2 * H, hd, 3 * d, inverse=True)
+        names = [p + f"{nm}_proj.weight" for nm in "qkv"]
+        stack = self.wqkv.get(l) if self.prepared and self.use_tn and T == torch.bfloat16 else None
+        d_h, t_h = self._stacked_dgrad(dqkv, self.wqkvT.get(l) if self.prepared else None, stack, names, ws.get("d_h", (M, d), T),
+                                       pl.defer_b and "qkv" not in la)
+        if "qkv" in la:
+            self._lora_bwd(l, "qkv", dqkv, lc["h"], d_h, lT["qkv"])
+        self._wgrad_stacked(names, dqkv, lc["h"])
+        n1 = f"model.layers.{l}.input_layernorm.weight"
+        return ops.rmsnorm_bwd(d_h, lc["x_in"], w[n1], lc["rstd1"], dx_add=d_mid, dw=self.grad_buffer(n1) if n1 in self.trainable else None,
+                               out=ws.get("dx_a", (M, d), T), tail=t_h)
+
+    def _layer_bwd(self, l, dx, pl, ctx):
+        """Decoder layer l: dx [rows, d] at its output -> the gradient at its input [M, d]; the layer's weight gradients are final afterwards."""
+        lc = ctx["layers"][l]
+        self._begin_direct(l)
+        dx = self._attn_half_bwd(l, self._mlp_bwd(l, dx, lc, pl), lc, pl, ctx["key_mask"])
+        self._notify_layer(l)
+        return dx
+
+    def _points_bwd(self, dx, ctx):
+        """Embedding, splice and projector (pointllm.py:107,126-129,155), then the trainable point backbone: dx [M, d] at the decoder's input."""
+        w, pb, T, ws, tr = self.w, self.dims.pb, self.dtype, self.ws, self.trainable
+        B, S, Bc, Pn, d = ctx["B"], ctx["S"], ctx["n_clouds"], pb.point_token_len, dx.shape[1]
+        emb_name = "model.embed_tokens.weight"
+        # zeroed: a cloud no sample received (text-only sample, skipped index) has a zero gradient
+        d_feats = ws.get("d_pp_out", (Bc * Pn, d), T, zero=True) if ctx["has_points"] else None
+        ops.embed_splice_bwd(dx.view(B, S, d), ctx["ids"], ctx["start_pos"], Pn, self.dims.lm.vocab_size,
+                             self.grad_buffer(emb_name) if emb_name in tr else None, d_feats, cloud_idx=ctx["cloud_idx"])
+        if d_feats is None:
+            return
+        acts, g = ctx["pp_acts"], d_feats
+        for j in range(len(pb.projection_hidden_dim), -1, -1):
+            Wn, bn = f"model.point_proj.{2 * j}.weight", f"model.point_proj.{2 * j}.bias"
+            self._wgrad(Wn, g, acts[2 * j])                    # acts[2j]: the input of linear j: feats (j = 0) or a gelu output
+            self._bgrad(bn, g)
+            if j > 0:
+                if T == torch.bfloat16:
+                    # dX = dY . W on the tuned K-contiguous kernel: the (trainable, hence changing) projector weight is
+                    # transposed on the fly (a 16-MB pass) instead of running the transposing generic kernel (0.34 ms each)
+                    wt = ops.transpose(w[Wn], out=ws.get(f"pp_wT{j}", (w[Wn].shape[1], w[Wn].shape[0]), T))
+                    g_in = ops.mm(g, wt, out=ws.get(f"d_pp_act{j}", (Bc * Pn, w[Wn].shape[1]), T))
+                else:
+                    g_in = ops.mm(g, w[Wn], out=ws.get(f"d_pp_act{j}", (Bc * Pn, w[Wn].shape[1]), T), b_layout=1)
+                g = ops.gelu_bwd(g_in, acts[2 * j - 1], out=ws.get(f"d_pp_pre{j}", g_in.shape, T))
+            elif ctx.get("pb_ctx") is not None:
+                d_backbone = ops.mm(g, w[Wn], b_layout=1)                  # gradient w.r.t. the PointBERT output
+                self.pb_trainer.backward(d_backbone.view(Bc, Pn, pb.trans_dim), ctx["pb_ctx"])
+                if self.grad_sync is not None:
+                    for nm in tr:
+                        if nm.startswith("model.point_backbone."):
+                            self._notify(nm)
+
     def backward_hidden(self, d_hn):
         """d_hn: gradient w.r.t. the final-normed hidden [M,d] ([B*R,d] compact after a windowed forward: forward_hidden).  Accumulates
         fp32 main_grad of the trainable tensors (model_arch.py:33-51 decides which)."""
-        ctx, w, dims, T, ws = self.ctx, self.w, self.dims, self.dtype, self.ws
-        lm, pb = dims.lm, dims.pb
-        B, S = ctx["B"], ctx["S"]
-        d, Fd, H, hd, L = lm.hidden_size, lm.intermediate_size, lm.num_attention_heads, lm.head_dim, lm.num_hidden_layers
-        M = B * S
-        scale = hd ** -0.5
-        tr = self.trainable
-        dw = self.grad_buffer("model.norm.weight") if "model.norm.weight" in tr else None
-        R = ctx.get("top_rows", 0)                             # > 0: the top layer ran on B*R compact rows past its attention (forward_hidden)
-        sfx = "_top" if R else ""                              # ... in buffers of their own: the lower layers' keep their shape from step to step
-        dx = ops.rmsnorm_bwd(d_hn, ctx["x_last"], w["model.norm.weight"], ctx["rstd_f"], dw=dw, out=ws.get("dx_a" + sfx, ctx["x_last"].shape, T),
-                             window=(S, R) if R else None)        # (compact rows: dw still summed in the full layout's order)
-        # frozen layers only: with trainable layers the wgrad products between a dgrad and its norm would reuse the slab area
-        defer_b = self.use_tail_fuse and T == torch.bfloat16 and not self.any_layer_trainable
-        fuse_swiglu_bwd_all = self.use_fused_swiglu and T == torch.bfloat16 and self.gu_il and Fd % 64 == 0
-        la = self.lora_groups
-        for l in reversed(range(L)):
-            p = f"model.layers.{l}."
-            lc = ctx["layers"][l]
-            lT = lc.get("lora_T")
-            gu, qkv = lc["gu"], lc["qkv"]
-            top = R > 0 and l == L - 1
-            Ml, sfx = (B * R, "_top") if top else (M, "")
-            fuse_swiglu_bwd = fuse_swiglu_bwd_all and ops.gemm_kernel_id(Ml, Fd, d) == 2
-            wt = {"split_k": 1} if top else {}                  # whole tiles, as in forward_hidden
-            self._begin_direct(l)
-            # ---- MLP
-            dgu = ws.get("dgu" + sfx, (Ml, 2 * Fd), T)
-            wt_down = self.wT.get(p + "mlp.down_proj.weight") if self.prepared else None
-            if fuse_swiglu_bwd and wt_down is not None and l in self.wguT and "down" not in la:
-                # d(act) = dx . W_down never reaches memory: the GEMM epilogue reads gate|up and writes d(gate|up) (EGOMI_EPI_SWIGLU_BWD)
-                ops.mm(dx, wt_down, out=dgu, swiglu_bwd_gu=gu, **wt)
-            else:
-                d_act = self._dgrad(dx, p + "mlp.down_proj.weight", ws.get("d_act" + sfx, (Ml, Fd), T), **wt)
-                if "down" in la:
-                    self._lora_bwd(l, "down", dx, lc["act"], d_act, lT["down"])
-                if self.prepared and l in self.wguT and self.gu_il:
-                    ops.swiglu_il_bwd(d_act, gu, dgu)                           # gu / dgu in the interleaved-32 layout of the stacked weight
-                else:
-                    ops.swiglu_bwd(d_act, gu[:, :Fd], gu[:, Fd:], dgu[:, :Fd], dgu[:, Fd:])
-            self._wgrad(p + "mlp.down_proj.weight", dx, lc["act"])
-            t_h2 = None
-            if self.prepared and l in self.wguT:
-                if defer_b and "gu" not in la:
-                    d_h2, t_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h" + sfx, (Ml, d), T), defer_tail=True, **wt)
-                else:
-                    d_h2 = ops.mm(dgu, self.wguT[l], out=ws.get("d_h" + sfx, (Ml, d), T), **wt)
-            elif self.prepared and l in self.wgu_cat:
-                d_h2 = self._dgrad_w(dgu, self.wgu_cat[l], ws.get("d_h" + sfx, (Ml, d), T))          # one K = 2*ffn product over [Wgate;Wup] in place
-            else:
-                d_h2 = self._dgrad(dgu[:, :Fd], p + "mlp.gate_proj.weight", ws.get("d_h" + sfx, (Ml, d), T))
-                self._dgrad(dgu[:, Fd:], p + "mlp.up_proj.weight", d_h2, residual=d_h2)
-            if "gu" in la:
-                self._lora_bwd(l, "gu", dgu, lc["h2"], d_h2, lT["gu"], il=lc["gu_il"])
-            self._wgrad_stacked([p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], dgu, lc["h2"])
-            n2 = p + "post_attention_layernorm.weight"
-            d_mid = ops.rmsnorm_bwd(d_h2, lc["x_mid"], w[n2], lc["rstd2"], dx_add=dx,
-                                    dw=self.grad_buffer(n2) if n2 in tr else None, out=ws.get("dx_b" + sfx, (Ml, d), T), tail=t_h2)
-            # ---- attention
-            d_ao = self._dgrad(d_mid, p + "self_attn.o_proj.weight", ws.get("d_ao" + ("_rows_top" if top else ""), (Ml, d), T), **wt)
-            if "o" in la:
-                self._lora_bwd(l, "o", d_mid, lc["ao"], d_ao, lT["o"])
-            self._wgrad(p + "self_attn.o_proj.weight", d_mid, lc["ao"])
-            if top:                                            # back to all rows: d_ao and d_mid are zero below the window (_top_buffers)
-                d_ao_f, d_mid_f = self._top_buffers(B, S, R)[2:]
-                d_ao_f.view(B, S, d)[:, S - R:].copy_(d_ao.view(B, R, d))
-                d_mid_f.view(B, S, d)[:, S - R:].copy_(d_mid.view(B, R, d))
-                d_ao, d_mid = d_ao_f, d_mid_f
-            dqkv = ws.get("dqkv", (M, 3 * d), T)
-            if lc["lse"] is not None:
-                # dq, dk leave the kernels already rotated back (the inverse RoPE pass is fused into their epilogues)
-                ops.attn_bwd(qkv, lc["ao"], lc["lse"], d_ao, dqkv, ws.get("att_delta", (B, H, S), torch.float32), B, S, H, hd, scale,
-                             causal=True, key_mask=ctx["key_mask"], rope=(self.cos, self.sin), q_rows=R if top else 0)
-            else:
-                self._attention_bwd(qkv, lc["P"], d_ao, dqkv, B, S, H, hd, scale)
-                ops.rope_(dqkv, self.cos, self.sin, M, S, 0, 2 * H, hd, 3 * d, inverse=True)
-            t_h = None
-            if self.prepared and l in self.wqkvT:
-                if defer_b and "qkv" not in la:
-                    d_h, t_h = ops.mm(dqkv, self.wqkvT[l], out=ws.get("d_h", (M, d), T), defer_tail=True)
-                else:
-                    d_h = ops.mm(dqkv, self.wqkvT[l], out=ws.get("d_h", (M, d), T))
-            elif self.prepared and l in self.wqkv and self.use_tn and T == torch.bfloat16:
-                d_h = self._dgrad_w(dqkv, self.wqkv[l], ws.get("d_h", (M, d), T))             # one K = 3d product over [Wq;Wk;Wv] in place
-            else:
-                d_h = self._dgrad(dqkv[:, :d], p + "self_attn.q_proj.weight", ws.get("d_h", (M, d), T))
-                self._dgrad(dqkv[:, d:2 * d], p + "self_attn.k_proj.weight", d_h, residual=d_h)
-                self._dgrad(dqkv[:, 2 * d:], p + "self_attn.v_proj.weight", d_h, residual=d_h)
-            if "qkv" in la:
-                self._lora_bwd(l, "qkv", dqkv, lc["h"], d_h, lT["qkv"])
-            self._wgrad_stacked([p + f"self_attn.{nm}_proj.weight" for nm in "qkv"], dqkv, lc["h"])
-            n1 = p + "input_layernorm.weight"
-            dx = ops.rmsnorm_bwd(d_h, lc["x_in"], w[n1], lc["rstd1"], dx_add=d_mid,
-                                 dw=self.grad_buffer(n1) if n1 in tr else None, out=ws.get("dx_a", (M, d), T), tail=t_h)
-            self._notify_layer(l)
-        # ---- embedding + splice + projector (pointllm.py:107,126-129,155)
-        Pn = pb.point_token_len
-        V = lm.vocab_size
-        emb_name = "model.embed_tokens.weight"
-        Bc = ctx["n_clouds"]
-        d_feats = ws.get("d_pp_out", (Bc * Pn, d), T) if ctx["has_points"] else None
-        if d_feats is not None:
-            d_feats.zero_()                                    # a cloud no sample received (text-only sample, skipped index) has a zero gradient
-        ops.embed_splice_bwd(dx.view(B, S, d), ctx["ids"], ctx["start_pos"], Pn, V,
-                             self.grad_buffer(emb_name) if emb_name in tr else None, d_feats, cloud_idx=ctx["cloud_idx"])
-        if ctx["has_points"]:
-            acts = ctx["pp_acts"]
-            nh = len(pb.projection_hidden_dim)
-            g = d_feats
-            for j in range(nh, -1, -1):
-                Wn, bn = f"model.point_proj.{2 * j}.weight", f"model.point_proj.{2 * j}.bias"
-                x_in = acts[2 * j]                     # input of linear j: feats (j=0) or gelu output
-                self._wgrad(Wn, g, x_in)
-                self._bgrad(bn, g)
-                if j > 0:
-                    if T == torch.bfloat16:
-                        # dX = dY . W on the tuned K-contiguous kernel: the (trainable, hence changing) projector weight is
-                        # transposed on the fly (a 16-MB pass) instead of running the transposing generic kernel (0.34 ms each)
-                        wt = ops.transpose(w[Wn], out=ws.get(f"pp_wT{j}", (w[Wn].shape[1], w[Wn].shape[0]), T))
-                        g_in = ops.mm(g, wt, out=ws.get(f"d_pp_act{j}", (Bc * Pn, w[Wn].shape[1]), T))
-                    else:
-                        g_in = ops.mm(g, w[Wn], out=ws.get(f"d_pp_act{j}", (Bc * Pn, w[Wn].shape[1]), T), b_layout=1)
-                    g = ops.gelu_bwd(g_in, acts[2 * j - 1], out=ws.get(f"d_pp_pre{j}", g_in.shape, T))
-                elif ctx.get("pb_ctx") is not None:
-                    d_backbone = ops.mm(g, w[Wn], b_layout=1)                  # gradient w.r.t. the PointBERT output
-                    self.pb_trainer.backward(d_backbone.view(Bc, Pn, pb.trans_dim), ctx["pb_ctx"])
-                    if self.grad_sync is not None:
-                        for nm in self.trainable:
-                            if nm.startswith("model.point_backbone."):
-                                self._notify(nm)
+        ctx, w, ws, pl = self.ctx, self.w, self.ws, self.ctx["plan"]
+        nf = "model.norm.weight"
+        dx = ops.rmsnorm_bwd(d_hn, ctx["x_last"], w[nf], ctx["rstd_f"], dw=self.grad_buffer(nf) if nf in self.trainable else None,
+                             out=ws.get("dx_a" + pl.layers[-1].sfx, ctx["x_last"].shape, self.dtype),
+                             window=(pl.S, pl.R) if pl.R else None)        # (compact rows: dw still summed in the full layout's order)
+        for l in reversed(range(len(pl.layers))):
+            dx = self._layer_bwd(l, dx, pl, ctx)
+        self._points_bwd(dx, ctx)
         if self.grad_sync is not None:                         # everything outside the decoder layers: one last bucket
-            self._notify(emb_name)
-            self._notify("model.norm.weight")
-            for j in range(len(pb.projection_hidden_dim) + 1):
+            self._notify("model.embed_tokens.weight")
+            self._notify(nf)
+            for j in range(len(self.dims.pb.projection_hidden_dim) + 1):
                 self._notify(f"model.point_proj.{2 * j}.weight")
                 self._notify(f"model.point_proj.{2 * j}.bias")
             self.grad_sync.flush()

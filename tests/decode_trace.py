@@ -9,13 +9,12 @@ on the commit before Decoder's cache layouts became objects; tests/test_gpu_deco
 
 Shapes: LLaMA-7B width (the slab-fused step needs it) with one decoder layer, 4 decoder rows (grouped modes: 2 prompts x 2), a text-only
 prompt of 24 tokens, 3 new tokens = two step() calls, eager (use_graph=False)."""
-import contextlib
-import ctypes
 import os
-import sys
 import types
 
 import torch
+
+from tests.launch_trace import Recorder, first_difference, trace  # noqa: F401  (the recording core: tests/launch_trace.py)
 
 ROWS, S0, T = 4, 24, 3
 PREFILL_ONLY = "egomi_kv_append"          # during prefill only the decoder's own launches are recorded, not the engine's
@@ -44,17 +43,19 @@ DECODER_BUFFERS = ("kc", "vc", "ks", "vs", "kp", "vp", "ksfx", "vsfx", "kv_row",
                    "run_score", "fin_score", "fin_flag", "heur", "ctl")
 
 
-def make_model(kind):
-    """bf16: LLaMA-7B width, one layer; lora: the same with r=8 adapters on q_proj and o_proj; tiny: dims_tiny in fp32.  The trace does
-    not depend on the weights' values: they are drawn on the device."""
+def make_model(kind, layers=1, **flags):
+    """bf16: LLaMA-7B width, `layers` decoder layers; lora: the same with r=8 adapters on q_proj and o_proj; tiny: dims_tiny in fp32.
+    flags: further fields of the model's args (tests/train_trace.py: what is trainable, other adapter targets).  The trace does not
+    depend on the weights' values: they are drawn on the device."""
     from egoscaler_amd.config import dims_7b, dims_tiny
     from egoscaler_amd.pointllm import TrajPointLLMForCausalLM
     dims = dims_tiny() if kind == "tiny" else dims_7b()
     if kind != "tiny":
-        dims.lm.num_hidden_layers = 1
+        dims.lm.num_hidden_layers = layers
     args = types.SimpleNamespace(unfreeze_pc_encoder=False, unfreeze_language_model=False, num_bins=dims.tok.num_bins, model_name=None)
     if kind == "lora":
         args.lora_r, args.lora_alpha, args.lora_target_modules = 8, 16, "q_proj,o_proj"
+    args.__dict__.update(flags)
     m = TrajPointLLMForCausalLM(args, dims, None, device="cuda", dtype=torch.float32 if kind == "tiny" else torch.bfloat16)
     g = torch.Generator(device="cuda").manual_seed(7)
     with torch.no_grad():
@@ -77,12 +78,6 @@ def prompt(n):
     return torch.randint(3, 200, (n, S0), generator=torch.Generator().manual_seed(11)).cuda()
 
 
-# -- recording -----------------------------------------------------------------------------------------
-def _extent(t):
-    """Bytes from t.data_ptr() to the end of t's last element (views included)."""
-    return (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size() if t.numel() else 0
-
-
 def named_buffers(dec):
     """[(name, tensor)] in resolution order: the decoder's buffers, its stacked / merged / quantized weights, then the engine's."""
     eng, out = dec.eng, []
@@ -100,59 +95,6 @@ def named_buffers(dec):
     out += [("eng.cos", eng.cos), ("eng.sin", eng.sin)]
     out += [(f"eng.ws[{n}]", t) for n, t in eng.ws.bufs.items()]
     return [(n, t) for n, t in out if isinstance(t, torch.Tensor) and t.is_cuda]
-
-
-def _raw(a):
-    """A ctypes argument -> a scalar, ("p", address or None) or ("s", [fields]) for a structure passed by reference."""
-    if a is None or isinstance(a, ctypes.c_void_p):     # a bare None is passed as NULL
-        return ("p", getattr(a, "value", None))
-    obj = getattr(a, "_obj", None)
-    if isinstance(obj, ctypes.Structure):
-        return ("s", [("p", getattr(obj, f)) if ty is ctypes.c_void_p else getattr(obj, f) for f, ty in obj._fields_])
-    return a.value
-
-
-class Recorder:
-    def __init__(self, inner, only):
-        self.inner, self.only, self.raw = inner, only, []
-
-    def __call__(self, name, *args):
-        if self.only is None or name.startswith(self.only):
-            from egoscaler_amd import _lib
-            self.raw.append([name] + [_raw(a) for a in _lib.marshal(name, args)])        # the ctypes values the library receives
-        return self.inner(name, *args)
-
-    def resolved(self, dec):
-        spans = [(n, t.data_ptr(), _extent(t)) for n, t in named_buffers(dec)]
-
-        def res(sym, i, v):
-            if not isinstance(v, tuple):
-                return v
-            if v[0] == "s":
-                return [res(sym, i, f) for f in v[1]]
-            if v[1] is None:
-                return None
-            for n, p0, nbytes in spans:
-                if p0 <= v[1] < p0 + nbytes:
-                    return [n, v[1] - p0]
-            raise AssertionError(f"{sym}: argument {i} points into no named buffer")
-        return [[r[0]] + [res(r[0], i, v) for i, v in enumerate(r[1:])] for r in self.raw]
-
-
-@contextlib.contextmanager
-def trace(only=None):
-    """Records the library calls of the block; -> the Recorder (resolve with .resolved(dec) before the buffers it saw can go away)."""
-    from egoscaler_amd import _lib
-    orig = _lib.call                                    # (_lib is one of the modules patched below: keep the function, not the attribute)
-    rec = Recorder(orig, only)
-    mods = [m for n, m in list(sys.modules.items()) if (n == "egoscaler_amd" or n.startswith("egoscaler_amd.")) and getattr(m, "call", None) is orig]
-    for m in mods:
-        m.call = rec
-    try:
-        yield rec
-    finally:
-        for m in mods:
-            m.call = orig
 
 
 def check_fused(dec, expect):
@@ -188,7 +130,7 @@ def run_case(models, name):
     out = {}
     with trace(PREFILL_ONLY) as rec:
         dec.prefill(ids, None, None, None, T, nb=nb)
-    out["prefill"] = rec.resolved(dec)
+    out["prefill"] = rec.resolved(named_buffers(dec))
     with trace() as rec:
         if loop == "greedy":
             dec.greedy(T, use_graph=False)
@@ -196,21 +138,11 @@ def run_case(models, name):
             dec.beam(T, eos=tok.eos, pad=tok.pad, use_graph=False)
         else:
             dec.sample(T, eos=tok.eos, pad=tok.pad, seed=5, use_graph=False, logprobs=loop == "sample_lp")
-    out["loop"] = rec.resolved(dec)
+    out["loop"] = rec.resolved(named_buffers(dec))
     if chunked:
         with trace(PREFILL_ONLY) as rec:
             dec.prefill_chunked(ids, None, None, None, T, chunk=1, nb=nb)
-        out["prefill_chunked"] = rec.resolved(dec)
+        out["prefill_chunked"] = rec.resolved(named_buffers(dec))
     torch.cuda.synchronize()
     assert out["prefill"] and out["loop"]
     return out
-
-
-def first_difference(got, want):
-    """None when equal, else a message naming the first differing launch."""
-    for i, (g, w) in enumerate(zip(got, want)):
-        if g != w:
-            return f"launch {i}: got {g}, recorded {w}"
-    if len(got) != len(want):
-        return f"{len(got)} launches, recorded {len(want)}"
-    return None
