@@ -141,7 +141,7 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
 
 
 @torch.no_grad()
-def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None):
+def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None):
     """Generation + metrics on the rank's shard (train.py:207-264, evaluate.py:104-154): prompts up to the first <tsep>,
     `generate` of the remaining positions (sampling with the reference's defaults top_k 50 / top_p 0.95 / T 1.0 unless
     args.val_sample is False -> greedy), cut at eos, de-tokenise, de-normalise (dataset.denorm), pad with the last step,
@@ -165,7 +165,14 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     'ADE_sel' / 'FDE_sel' (T.metrics_selected; means over the 'n_sel' clips whose pick parsed) and 'select'; the dump gains one key,
     "selected": {image id: picked sample index}.  "none" leaves the record and the dump as they are.
     args.rescore with select "logprob": the rank comes from model.score() on the generated samples (the exact model's teacher-forced
-    log-probs; one more pass over the K suffixes of every clip) instead of the sampling run's own log-probs."""
+    log-probs; one more pass over the K suffixes of every clip) instead of the sampling run's own log-probs.
+
+    num_modes = M > 0 (default: args.num_modes, else 0 = off) with 1 <= M <= K <= 64 and K > 1: a short list of M mutually different samples
+    per clip, each with a probability (T.select_modes on the de-normalised trajectories, all D dimensions; mode_radius, default
+    args.mode_radius, else 0, is in their units).  The order is that of the scores select "logprob" ranks by (with args.rescore those of
+    model.score()), otherwise centrality.  The record gains 'minADE_M' / 'minFDE_M' / 'brierADE_M' (T.metrics_modes; means over the clips
+    with a mode), 'n_modes' (mean number of modes per clip), 'M' and 'mode_radius'; the dump gains one key,
+    "modes": {image id: {"index": [sample indices in pick order], "conf": [their probabilities]}}.  0 leaves both as they are."""
     dims = model.dims
     K = int(num_samples if num_samples is not None else (getattr(args, "num_samples", 1) or 1))
     if K < 1:
@@ -180,10 +187,17 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     rescore = bool(getattr(args, "rescore", False))
     if rescore and select != "logprob":
         raise ValueError("--rescore re-ranks by log-prob: it needs --select logprob")
+    M = int(num_modes if num_modes is not None else (getattr(args, "num_modes", 0) or 0))
+    radius = float(mode_radius if mode_radius is not None else (getattr(args, "mode_radius", 0.0) or 0.0))
+    if M < 0 or (M > 0 and not (K > 1 and M <= K <= 64)):
+        raise ValueError(f"--num_modes M picks M of K samples: it needs --num_samples K > 1 and 1 <= M <= K <= 64, not M = {M}, K = {K}")
+    if radius != radius or radius < 0 or (radius > 0 and M == 0):
+        raise ValueError(f"--mode_radius is a distance >= 0 and needs --num_modes M > 0, not {radius} with M = {M}")
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
     sample = bool(getattr(args, "val_sample", True))
     sel_sums, picked = np.zeros(3), {}                   # ADE_sel, FDE_sel, n_sel
+    mode_sums, mode_dump = np.zeros(6), {}               # minADE_M, minFDE_M, brierADE_M, clips with a mode; modes, clips
     per = micro_batch_per_rank(args.bs, 1, world)
     model.eval()
     sums = np.zeros(8)                                   # ADE, FDE, ADE_as_called, GD, n; best-of-K: minADE, minFDE, n_min
@@ -248,24 +262,35 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
                 if best[j] >= 0:
                     sums[5:8] += [made[j], mfde[j], 1.0]
                 dump[int(ids_h[j])] = [gen[j * K + i].tolist() if n_h[j * K + i] > 0 else None for i in range(K)]
-            if select != "none":
+            if select != "none" or M:
                 gen_k, n_k = gen_d.view(len(idx), K, Tn, -1), (n > 0).to(torch.int32).view(len(idx), K) * Tn
+                ranked = None
                 if select == "logprob" and rescore:                          # the same samples, ranked on the model's own weights
-                    rank_k = model.score(prompts, batch["prompt_masks"], batch["pcrgbs"], all_ids.reshape(len(idx), K, -1),
-                                         fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device)).rank
-                else:
-                    rank_k = out.rank if select == "logprob" else None
-                pick = rank_k[:, 0].contiguous() if select == "logprob" else T.select_medoid(gen_k, n_k)[0]
+                    ranked = model.score(prompts, batch["prompt_masks"], batch["pcrgbs"], all_ids.reshape(len(idx), K, -1),
+                                         fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device))
+                elif select == "logprob":
+                    ranked = out
+            if select != "none":
+                pick = ranked.rank[:, 0].contiguous() if select == "logprob" else T.select_medoid(gen_k, n_k)[0]
                 sade, sfde = T.metrics_selected(gen_k, n_k, gt, None, pick)
                 sade, sfde, pick = sade.cpu().numpy(), sfde.cpu().numpy(), pick.cpu().numpy()
                 for j in range(len(idx)):
                     picked[int(ids_h[j])] = int(pick[j])
                     if not np.isnan(sade[j]):
                         sel_sums += [sade[j], sfde[j], 1.0]
+            if M:                                                            # M different ones of the K, ordered by the scores or by centrality
+                md, cf, _, nmd, _ = T.select_modes(gen_k, n_k, None if ranked is None else ranked.sample_scores, M, radius)
+                oade, ofde, slot, brier = (t.cpu().numpy() for t in T.metrics_modes(gen_k, n_k, gt, None, md, cf))
+                md, cf, nmd = md.cpu().numpy(), cf.cpu().numpy(), nmd.cpu().numpy()
+                for j in range(len(idx)):
+                    mode_dump[int(ids_h[j])] = {"index": md[j, :nmd[j]].tolist(), "conf": cf[j, :nmd[j]].tolist()}
+                    mode_sums[4:] += [float(nmd[j]), 1.0]
+                    if slot[j] >= 0:
+                        mode_sums[:4] += [oade[j], ofde[j], brier[j], 1.0]
     if world > 1:
-        t = torch.from_numpy(np.concatenate([sums, sel_sums])).to(device)
+        t = torch.from_numpy(np.concatenate([sums, sel_sums, mode_sums])).to(device)
         dist.all_reduce(t)
-        sums, sel_sums = t.cpu().numpy()[:8], t.cpu().numpy()[8:]
+        sums, sel_sums, mode_sums = t.cpu().numpy()[:8], t.cpu().numpy()[8:11], t.cpu().numpy()[11:]
     model.train()
     k = max(sums[4], 1.0)
     nan = float("nan")
@@ -278,6 +303,12 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
         rec.update({"ADE_sel": float(sel_sums[0] / sel_sums[2]) if sel_sums[2] else nan,
                     "FDE_sel": float(sel_sums[1] / sel_sums[2]) if sel_sums[2] else nan, "n_sel": int(sel_sums[2]), "select": select})
         dump["selected"] = picked
+    if M:
+        rec.update({"minADE_M": float(mode_sums[0] / mode_sums[3]) if mode_sums[3] else nan,
+                    "minFDE_M": float(mode_sums[1] / mode_sums[3]) if mode_sums[3] else nan,
+                    "brierADE_M": float(mode_sums[2] / mode_sums[3]) if mode_sums[3] else nan,
+                    "n_modes": float(mode_sums[4] / mode_sums[5]) if mode_sums[5] else nan, "M": M, "mode_radius": radius})
+        dump["modes"] = mode_dump
     return rec, dump
 
 
@@ -418,9 +449,10 @@ def evaluate(args, model, data, split="test", device="cuda"):
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, dump)
-        dump = {k: v for p in parts for k, v in p.items() if k != "selected"}
-        if any("selected" in p for p in parts):             # --select: the ranks' picks, merged like the trajectories
-            dump["selected"] = {k: v for p in parts for k, v in p.get("selected", {}).items()}
+        dump = {k: v for p in parts for k, v in p.items() if k not in ("selected", "modes")}
+        for key in ("selected", "modes"):                   # --select / --num_modes: the ranks' picks, merged like the trajectories
+            if any(key in p for p in parts):
+                dump[key] = {k: v for p in parts for k, v in p.get(key, {}).items()}
     if rank == 0:
         with open(os.path.join(args.checkpoint_dir, f"{split}_gen_trajs.json"), "w") as f:
             json.dump(dump, f)
@@ -483,7 +515,18 @@ def parse_args(argv=None):
                     help="validation / eval with --num_samples K > 1 --select logprob: rank the K samples by model.score() (teacher-forced "
                          "log-probs on the model's own weights, one suffix pass on the shared prompt) instead of the sampling run's own "
                          "log-probs, which are those of the quantized decoder under --decode_weight_dtype fp8 / int4")
+    ap.add_argument("--num_modes", type=int, default=0,
+                    help="validation / eval with --num_samples K > 1: also pick M <= K mutually different samples per clip, each with a "
+                         "probability, on the device (ordered by the --select logprob scores when given, else by centrality); adds minADE_M / "
+                         "minFDE_M / brierADE_M / n_modes to the record and the indices and probabilities per image id to the dump (0: off)")
+    ap.add_argument("--mode_radius", type=float, default=0.0,
+                    help="with --num_modes: a sample within this distance (mean displacement over all 6 dimensions, units of the de-normalised "
+                         "trajectories) of an earlier mode is not a mode of its own; 0 suppresses exact duplicates only")
     a = ap.parse_args(argv)
+    if a.num_modes != 0 and not (a.num_samples > 1 and 1 <= a.num_modes <= a.num_samples <= 64):
+        ap.error("--num_modes M picks M of K sampled trajectories: it needs --num_samples K > 1 and 1 <= M <= K <= 64")
+    if a.mode_radius != a.mode_radius or a.mode_radius < 0 or (a.mode_radius > 0 and a.num_modes == 0):
+        ap.error("--mode_radius is a distance >= 0 and needs --num_modes M > 0")
     if a.rescore and not (a.num_samples > 1 and a.select == "logprob"):
         ap.error("--rescore re-ranks sampled trajectories by log-prob: it needs --num_samples K > 1 and --select logprob")
     return a

@@ -131,6 +131,62 @@ def metrics_selected(gen, n_gen, gt, n_gt, pick):
     return torch.where(ok, ade, nan), torch.where(ok, fde, nan)
 
 
+def select_modes(gen, n_gen=None, scores=None, num_modes=6, radius=0.0, return_dist=False):
+    """M mutually different of K samples per clip, each with a probability, on the device (egomi_traj_modes): gen [B, K, T, D] with K <= 64,
+    n_gen [B, K] or None, scores [B, K] or None, 1 <= num_modes = M <= 64 -> (modes int32 [B, M], conf float64 [B, M], assign int32 [B, K],
+    n_modes int32 [B], n_nms int32 [B]), and dist float64 [B, K, K] with return_dist.
+    The distance between two samples is select_medoid's: the mean displacement with each sample padded by its own last step, over ALL D
+    dimensions, as ADE runs everywhere in this package; for position-only modes pass gen[..., :3].  A sample with n_gen <= 0 takes no part.
+    Order: descending scores (seq_rank's rules: ties to the lower index, NaN as -inf), or with scores=None ascending select_medoid cost.
+    A sample of the order becomes a mode when it is farther than `radius` from every mode picked before it (n_nms of them); free slots are
+    then filled with the sample farthest from the picked modes while that distance is > 0 (n_modes in all; modes[b, n_modes:] = -1).
+    assign = slot of the nearest mode (-1 for an unparsed sample), conf[b, m] = share of the clip's parsed samples assigned to slot m."""
+    gen = gen.to(torch.float32).contiguous()
+    if gen.dim() != 4 or gen.shape[1] < 1:
+        raise ValueError("gen must be [B,K,T,D] with K >= 1")
+    B, K, Tn, D = gen.shape
+    M = int(num_modes)
+    if K > 64:
+        raise ValueError(f"select_modes serves K <= 64 samples per clip, not {K}")
+    if not 1 <= M <= 64:
+        raise ValueError(f"num_modes must be in 1 .. 64, not {num_modes}")
+    if n_gen is not None and tuple(n_gen.shape) != (B, K):
+        raise ValueError("n_gen must be [B,K]")
+    if scores is not None and tuple(scores.shape) != (B, K):
+        raise ValueError("scores must be [B,K]")
+    radius = float(radius)
+    if radius != radius or radius < 0:
+        raise ValueError(f"radius must be a number >= 0, not {radius}")
+    dev = gen.device
+    modes = torch.empty(B, M, dtype=torch.int32, device=dev)
+    conf = torch.empty(B, M, dtype=torch.float64, device=dev)
+    assign = torch.empty(B, K, dtype=torch.int32, device=dev)
+    n_modes = torch.empty(B, dtype=torch.int32, device=dev)
+    n_nms = torch.empty(B, dtype=torch.int32, device=dev)
+    dist = torch.empty(B, K, K, dtype=torch.float64, device=dev) if return_dist else None
+    ng = None if n_gen is None else n_gen.to(device=dev, dtype=torch.int32).contiguous()
+    sc = None if scores is None else scores.to(device=dev, dtype=torch.float32).contiguous()
+    call("egomi_traj_modes", gen, ng, sc, B, K, Tn, D, M, radius, dist, modes, conf, assign, n_modes, n_nms, S())
+    out = (modes, conf, assign, n_modes, n_nms)
+    return out + (dist,) if return_dist else out
+
+
+def metrics_modes(gen, n_gen, gt, n_gt, modes, conf):
+    """Metrics of the chosen set: metrics_best_of on the gathered rows gen[b, modes[b, m]] (bit-equal to it; an unused slot, modes < 0,
+    takes no part: its n_gen is forced to 0) -> (min_ade [B], min_fde [B], best_slot int32 [B], brier_ade [B]), float64.
+    brier_ade = min_ade + (1 - conf[b, best_slot]) ** 2; NaN with best_slot -1 when nothing is left.
+    gen [B, K, T, D], n_gen [B, K] or None, gt [B, T, D], n_gt [B] or None, modes [B, M] int32, conf [B, M] float64."""
+    B, K, Tn = gen.shape[:3]
+    modes = modes.to(gen.device).long()
+    used = modes >= 0
+    rows = torch.arange(B, device=gen.device)[:, None], modes.clamp(min=0)
+    ng = torch.full((B, K), Tn, dtype=torch.int32, device=gen.device) if n_gen is None else n_gen.to(gen.device).to(torch.int32)
+    min_ade, min_fde, slot = metrics_best_of(gen[rows], torch.where(used, ng[rows], torch.zeros_like(ng[rows])), gt, n_gt)
+    c = conf.to(gen.device).to(torch.float64).gather(1, slot.long().clamp(min=0)[:, None])[:, 0]
+    brier = torch.where(slot >= 0, min_ade + (1.0 - c) ** 2, torch.full_like(min_ade, float("nan")))
+    return min_ade, min_fde, slot, brier
+
+
 # ------------------------------------------------------------------------------------------ host
 def discretize_action(action_vector, num_bins=256):
     """utils/utils.py:13-16."""

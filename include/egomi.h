@@ -518,6 +518,31 @@ int egomi_traj_metrics_min(const float* gen, const int32_t* n_gen, const float* 
  *              UNSUPPORTED (K > 1024). */
 int egomi_traj_medoid(const float* gen, const int32_t* n_gen, int B, int K, int Tmax, int D, double* cost, int32_t* pick,
                       egomi_stream_t stream);
+/* modes      : M mutually different of K samples, each with a probability (csrc/modes.hip): the short list between all K (`metrics_min`)
+ *              and one pick (`medoid`, seq_rank).  gen f32 [B,K,Tmax,D], n_gen i32 [B,K] (NULL = Tmax; values above Tmax count as Tmax),
+ *              score f32 [B,K] or NULL, K <= 64, M <= 64 (M > K is legal).  Sample j is valid when n_gen > 0; an invalid sample is never a
+ *              mode and has no place in the order.  Values of gen are expected finite.
+ *   dist     float64 [B,K,K], may be NULL: d(j,i) of `medoid`, each unordered pair computed once and stored to both halves (bit-symmetric);
+ *              diagonal of a valid sample 0.0; NaN wherever j or i is invalid.
+ *   order    with score: descending score, ties -> lower index, a NaN score ranks as -inf, -inf rows last in index order (seq_rank's rules).
+ *              score == NULL: ascending centrality c_j = mean of d(j,i) over the valid i != j, summed in index order and divided once
+ *              (`medoid`'s cost, the same expression in the same order; 0 for a single valid sample), ties -> lower index: with M = 1 the
+ *              pick is `medoid`'s pick.  That equality of picks is the contract; c_j is not returned, and its bits are not promised to be
+ *              those of `medoid`'s cost (the two kernels are separate compilations of the expression).
+ *   NMS      walk the order; a sample becomes the next mode when d(j,m) > radius for every mode m picked so far; stop at M modes or at the
+ *              end of the order.  n_nms[b] i32 = modes picked this way.
+ *   fill     while fewer than M: among the valid unpicked samples the one whose minimum distance to the picked modes is largest (ties ->
+ *              lower index); stop when that distance is <= 0 (what is left are exact duplicates) or no sample is left.  n_modes[b] i32 =
+ *              the total; modes[b, :n_modes] i32 = sample indices in pick order, the rest -1.
+ *   assign   i32 [B,K]: the slot m in 0 .. n_modes-1 of the nearest mode (ties -> lower slot; a mode is assigned to itself), invalid: -1.
+ *   conf     float64 [B,M]: (double)count(assign == m) / (double)n_valid, the Monte-Carlo mass of the mode under the distribution the
+ *              samples were drawn from; unused slots 0.0.  A clip without a valid sample: all -1 / 0.0, n_modes = n_nms = 0.
+ *              BADARG (NULL gen / modes / conf / assign / n_modes / n_nms; NaN or negative radius -- radius = 0 is legal and suppresses
+ *              exact duplicates only), SHAPE (B, K, Tmax, D or M <= 0), UNSUPPORTED (K > 64 or M > 64).  No atomics; the order of every
+ *              sum depends on (K, Tmax, D, n_gen) only: a replay is bit-equal. */
+int egomi_traj_modes(const float* gen, const int32_t* n_gen, const float* score, int B, int K, int Tmax, int D, int M, double radius,
+                     double* dist, int32_t* modes, double* conf, int32_t* assign, int32_t* n_modes, int32_t* n_nms,
+                     egomi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Trainable point backbone (--unfreeze_pc_encoder, models/pointllm/model_arch.py:33-36): the backward
