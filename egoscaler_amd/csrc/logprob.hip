@@ -23,6 +23,8 @@
 // egomi_seq_rank: one workgroup per clip; score = sum_lp / n_tok^length_penalty (HF's beam convention: 1 = mean log-prob, 0 = the sum),
 //   -inf for an empty row; order = the clip's K indices by descending score, by counting (rank of j = number of rows that beat it),
 //   ties -> lower index, -inf rows last in index order.  A NaN score ranks as -inf.
+// egomi_bin_stats: the same row pass (lp_row_max_sumexp, shared with egomi_token_logprob), then mass / mean / std / entropy of the step's
+//   distribution over the waypoint bin tokens; described at the kernel below.
 #include "common.h"
 #include <math.h>
 
@@ -79,15 +81,11 @@ struct LogprobArgs {
     float* sum_lp; int* n_tok;
 };
 
+// The row's maximum m and s = sum exp(x - m) over its V elements, as every thread of the 1024-thread workgroup gets them (see the top comment:
+// element e belongs to thread (e / 8) % 1024, aligned 16-byte loads, the row in registers for REG, accurate expf).  `red` is 16 floats of LDS.
 template <typename T, bool REG>
-__global__ __launch_bounds__(LPB_THREADS) void token_logprob_kernel(LogprobArgs a) {
-    __shared__ float red[16];
-    const int r = blockIdx.x, tid = threadIdx.x, V = a.V;
-    if (a.live && a.live[r] == 0) {                                      // uniform; thread 0 alone ever writes live[r], after the barriers below
-        if (tid == 0) a.tok_lp[(long long)r * a.ld_lp + a.col] = 0.f;
-        return;
-    }
-    const T* lg = (const T*)a.logits + (long long)r * a.ld;
+__device__ __forceinline__ void lp_row_max_sumexp(const T* lg, int V, float* red, float& m_out, float& s_out) {
+    const int tid = threadIdx.x;
     const uintptr_t row = (uintptr_t)lg, row_end = row + (uintptr_t)V * sizeof(T);
     const unsigned mb = (unsigned)(row & 15u);
     const int nchunk = (V + 7) >> 3;
@@ -120,7 +118,21 @@ __global__ __launch_bounds__(LPB_THREADS) void token_logprob_kernel(LogprobArgs 
             s += e == NEG_INF ? 0.f : expf(e - m);                       // (a NaN logit stays NaN: it is not -inf)
         }
     }
-    s = block_sum(s, red);
+    m_out = m;
+    s_out = block_sum(s, red);
+}
+
+template <typename T, bool REG>
+__global__ __launch_bounds__(LPB_THREADS) void token_logprob_kernel(LogprobArgs a) {
+    __shared__ float red[16];
+    const int r = blockIdx.x, tid = threadIdx.x, V = a.V;
+    if (a.live && a.live[r] == 0) {                                      // uniform; thread 0 alone ever writes live[r], after the barriers below
+        if (tid == 0) a.tok_lp[(long long)r * a.ld_lp + a.col] = 0.f;
+        return;
+    }
+    const T* lg = (const T*)a.logits + (long long)r * a.ld;
+    float m, s;
+    lp_row_max_sumexp<T, REG>(lg, V, red, m, s);
     if (tid == 0) {
         const long long t = a.tok[r];
         const bool bad = t < 0 || t >= V;
@@ -145,6 +157,76 @@ extern "C" int egomi_token_logprob(const void* logits, int64_t ld, int R, int V,
     a.sum_lp = sum_lp; a.n_tok = n_tok;
     if (V <= LPB_THREADS * LPB_NPT) EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((token_logprob_kernel<T, true>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
     else EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((token_logprob_kernel<T, false>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
+    return egomi_launch_status();
+}
+
+// egomi_bin_stats: what the step's distribution says about a waypoint coordinate, from the same raw row.  m and s as above (the same function);
+// then thread i < nb owns bin i: w_i = exp(x[p0 + i] - m) in fp32 (-inf -> 0; the element is re-read, its line is cache-hot), and Z = sum w,
+// sum w v, the centred sum w (v - mean)^2 and -sum q log q (q = w / Z) run in float64 through the workgroup in a fixed order (xor butterfly
+// per wave, the 16 wave results in index order).  Thread 0 stores mass = Z / s, mean, std, ent as fp32 at column `col`.  No state, no
+// atomics, nothing read outside [row, row + V): a row's bits depend on (V, p0, nb, dtype) and its values only.
+struct BinStatsArgs {
+    const void* logits; long long ld; int V, p0, nb;
+    const double* values;
+    float *mass, *mean, *std, *ent; long long ld_out; int col;
+};
+
+// two float64 sums over the workgroup at once; `red` is 32 doubles of LDS; every thread gets both
+__device__ __forceinline__ void block_sum2_f64(double& a, double& b, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { red[w] = a; red[16 + w] = b; }
+    __syncthreads();
+    double ta = 0.0, tb = 0.0;
+    for (int i = 0; i < LPB_THREADS / 64; ++i) { ta += red[i]; tb += red[16 + i]; }
+    a = ta; b = tb;
+}
+
+template <typename T, bool REG>
+__global__ __launch_bounds__(LPB_THREADS) void bin_stats_kernel(BinStatsArgs a) {
+    __shared__ float red[16];
+    __shared__ double red2[32];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const T* lg = (const T*)a.logits + (long long)r * a.ld;
+    float m, s;
+    lp_row_max_sumexp<T, REG>(lg, a.V, red, m, s);
+    const bool own = tid < a.nb;
+    double w = 0.0, v = 0.0;
+    if (own) {
+        const float xi = Cvt<T>::ld(lg + a.p0 + tid);
+        w = (double)(xi == -INFINITY ? 0.f : expf(xi - m));
+        v = a.values[tid];
+    }
+    double Z = w, wv = w * v;
+    block_sum2_f64(Z, wv, red2);
+    const double mean = wv / Z;                                          // Z = 0 (every bin -inf): NaN, and so are std and ent
+    const double d = v - mean, q = w / Z;
+    double m2 = own ? w * d * d : 0.0;
+    double h = (!own || q == 0.0) ? 0.0 : -q * log(q);                   // 0 log 0 = 0; a NaN q stays NaN
+    block_sum2_f64(m2, h, red2);
+    if (tid == 0) {
+        const long long o = (long long)r * a.ld_out + a.col;
+        a.mass[o] = (float)Z / s;
+        a.mean[o] = (float)mean;
+        a.std[o] = (float)sqrt(m2 / Z);
+        a.ent[o] = (float)h;
+    }
+}
+
+extern "C" int egomi_bin_stats(const void* logits, int64_t ld, int R, int V, int p0, int nb, const double* values, float* mass, float* mean,
+                               float* std, float* ent, int64_t ld_out, int col, int dtype, egomi_stream_t stream) {
+    if (!logits || !values || !mass || !mean || !std || !ent) return EGOMI_E_BADARG;
+    if (dtype != EGOMI_F32 && dtype != EGOMI_BF16) return EGOMI_E_BADARG;
+    if (R <= 0 || V <= 0 || ld < V || col < 0 || ld_out <= col) return EGOMI_E_SHAPE;
+    if (nb < 1 || nb > LPB_THREADS || p0 < 0 || (long long)p0 + nb > V) return EGOMI_E_SHAPE;
+    if (((uintptr_t)logits) % (dtype == EGOMI_F32 ? 4 : 2)) return EGOMI_E_UNSUPPORTED;      // elements must be naturally aligned
+    BinStatsArgs a;
+    a.logits = logits; a.ld = ld; a.V = V; a.p0 = p0; a.nb = nb; a.values = values;
+    a.mass = mass; a.mean = mean; a.std = std; a.ent = ent; a.ld_out = ld_out; a.col = col;
+    if (V <= LPB_THREADS * LPB_NPT) EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((bin_stats_kernel<T, true>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
+    else EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((bin_stats_kernel<T, false>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
     return egomi_launch_status();
 }
 

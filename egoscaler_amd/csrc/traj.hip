@@ -79,6 +79,51 @@ __global__ __launch_bounds__(64) void traj_detokenize_kernel(const int64_t* ids,
     n_steps[b] = n;
 }
 
+// traj_detokenize_kernel's scan (cut at the first eos, split on <tsep>, first run of six bin ids per segment, copy-forward), gathering
+// the per-token statistics of egomi_bin_stats instead of bin centres: a step parsed from ids hit .. hit+5 takes mean / std of columns
+// hit .. hit+5 and, with bin_mass, the smallest of their six masses; a copied step repeats all three.  n_steps is that kernel's.
+__global__ __launch_bounds__(64) void traj_detokenize_soft_kernel(const int64_t* ids, int B, int L, int nb, int64_t p0, int64_t tsep, int64_t eos,
+                                                                  const float* bin_mean, const float* bin_std, const float* bin_mass,
+                                                                  long long ld_stat, int Tmax, float* mean, float* std, float* mass,
+                                                                  int32_t* n_steps) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const int64_t* r = ids + (long long)b * L;
+    const long long sr = (long long)b * ld_stat;
+    int n = 0, end = L;
+    for (int j = 0; j < L; ++j) if (r[j] == eos) { end = j; break; }
+    int seg0 = 0;
+    bool have_last = false;
+    float lm[6], ls[6], lmass = 0.f;
+    while (seg0 <= end && n < Tmax) {
+        int seg1 = seg0;
+        while (seg1 < end && r[seg1] != tsep) ++seg1;
+        int run = 0, hit = -1;
+        for (int j = seg0; j < seg1; ++j) {
+            if (r[j] >= p0 && r[j] < p0 + nb) { if (++run == 6) { hit = j - 5; break; } } else run = 0;
+        }
+        if (hit >= 0) {
+            for (int c = 0; c < 6; ++c) { lm[c] = bin_mean[sr + hit + c]; ls[c] = bin_std[sr + hit + c]; }
+            if (bin_mass) {
+                lmass = bin_mass[sr + hit];
+                for (int c = 1; c < 6; ++c) { const float x = bin_mass[sr + hit + c]; lmass = (x < lmass || x != x) ? x : lmass; }   // a NaN mass wins
+            }
+            have_last = true;
+        }
+        if (hit >= 0 || have_last) {
+            for (int c = 0; c < 6; ++c) {
+                mean[((long long)b * Tmax + n) * 6 + c] = lm[c];
+                std[((long long)b * Tmax + n) * 6 + c] = ls[c];
+            }
+            if (mass) mass[(long long)b * Tmax + n] = lmass;
+            ++n;
+        }
+        if (seg1 >= end) break;
+        seg0 = seg1 + 1;
+    }
+    n_steps[b] = n;
+}
+
 // per sample: gen padded with its last step / cut to len_gt (metrics.py:40-52), then
 // ade = mean_t ||gt_t - gen_t||_2, fde = ||gt_last - gen_last||_2 over all D dims (float64 like numpy)
 __global__ __launch_bounds__(64) void traj_metrics_kernel(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int Tmax,
@@ -206,6 +251,16 @@ extern "C" int egomi_traj_detokenize(const int64_t* ids, int B, int L, const dou
     if (!ids || !bins || !out || !n_steps) return EGOMI_E_BADARG;
     if (B <= 0 || L <= 0 || Tmax <= 0 || num_bins <= 1) return EGOMI_E_SHAPE;
     EGOMI_LAUNCH(traj_detokenize_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, ids, B, L, bins, num_bins, p0, tsep, eos, Tmax, out, n_steps);
+    return egomi_launch_status();
+}
+
+extern "C" int egomi_traj_detokenize_soft(const int64_t* ids, int B, int L, int num_bins, int64_t p0, int64_t tsep, int64_t eos,
+                                          const float* bin_mean, const float* bin_std, const float* bin_mass, int64_t ld_stat, int Tmax,
+                                          float* mean, float* std, float* mass, int32_t* n_steps, egomi_stream_t stream) {
+    if (!ids || !bin_mean || !bin_std || !mean || !std || !n_steps || (bin_mass != nullptr) != (mass != nullptr)) return EGOMI_E_BADARG;
+    if (B <= 0 || L <= 0 || Tmax <= 0 || num_bins <= 1 || ld_stat < L) return EGOMI_E_SHAPE;
+    EGOMI_LAUNCH(traj_detokenize_soft_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, ids, B, L, num_bins, p0, tsep, eos, bin_mean,
+                 bin_std, bin_mass, (long long)ld_stat, Tmax, mean, std, mass, n_steps);
     return egomi_launch_status();
 }
 

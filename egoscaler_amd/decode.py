@@ -139,6 +139,24 @@ def token_logprob(logits, tok, eos, live, tok_lp, col, sum_lp, n_tok):
          n_tok, dt(logits.dtype), S())
 
 
+def bin_stats_rows(logits, p0, nb, values, mass, mean, std, ent, col):
+    """The step's distribution over the bin tokens p0 .. p0 + nb - 1 (values float64 [nb]) under the RAW logits, per row (include/egomi.h
+    egomi_bin_stats): mass / mean / std / ent [:, col]."""
+    R, V = logits.shape
+    call("egomi_bin_stats", logits, logits.stride(0), R, V, p0, nb, values, mass, mean, std, ent, mass.stride(0), col, dt(logits.dtype), S())
+
+
+def bin_window(bin_token_ids, V):
+    """(p0, nb) of `bin_token_ids`, checked against a vocabulary of V ids (egomi_bin_stats' limits, raised before any launch)."""
+    try:
+        p0, nb = (int(v) for v in bin_token_ids)
+    except (TypeError, ValueError):
+        raise ValueError(f"`bin_token_ids` must be (first bin id, number of bins), not {bin_token_ids!r}") from None
+    if not 1 <= nb <= 1024 or p0 < 0 or p0 + nb > V:
+        raise ValueError(f"`bin_token_ids` = ({p0}, {nb}) is not a window of 1 .. 1024 ids inside the vocabulary of {V}")
+    return p0, nb
+
+
 def seq_rank(sum_lp, n_tok, B, K, length_penalty=1.0):
     """Per clip, the K rows b * K + j by descending sum_lp / n_tok ** length_penalty (include/egomi.h egomi_seq_rank):
     -> (score fp32 [B, K], order int32 [B, K])."""
@@ -392,6 +410,8 @@ class Decoder:
         self.done_buf = z(B, dtype=torch.int32)
         self._graphs, self._scores = {}, {}
         self.lp_tok = self.lp_sum = self.lp_n = self.lp_live = None      # sample() / greedy() with logprobs=True: made on first use (_lp_buffers)
+        self.bs_mass = self.bs_mean = self.bs_std = self.bs_ent = None   # sample() / greedy() / score() with bin_stats=(p0, nb) (_bs_buffers)
+        self._bs_values = {}
         self._score_act = None                              # score(): the activations of a suffix pass, made on first use (_score_buffers)
         self.kv_row = None                                  # beam mode: [B, Smax] int32, physical cache row of every key of every logical row
         if self.nb > 1:
@@ -450,6 +470,18 @@ class Decoder:
         self.lp_sum.zero_()
         self.lp_n.zero_()
         self.lp_live.fill_(1)
+
+    def _bs_buffers(self, bin_stats):
+        """Static buffers of sample() / greedy() / score() with bin_stats=(p0, nb), made on first use: bs_mass / bs_mean / bs_std / bs_ent
+        [B, max_len] (column t = step t) and the float64 bin values of nb bins.  -> (p0, nb, values, (mass, mean, std, ent))."""
+        p0, nb = bin_window(bin_stats, self.lg.shape[1])
+        dev = self.eng.device
+        if self.bs_mass is None:
+            self.bs_mass, self.bs_mean, self.bs_std, self.bs_ent = (torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev) for _ in range(4))
+        if nb not in self._bs_values:
+            from .traj import bin_edges
+            self._bs_values[nb] = bin_edges(nb, dev)
+        return p0, nb, self._bs_values[nb], (self.bs_mass, self.bs_mean, self.bs_std, self.bs_ent)
 
     def _merge_lora(self):
         """LoRA: the decode steps multiply merged copies W + s B A of the adapted projections (one fp32 sum, rounded once; csrc/lora.hip);
@@ -637,14 +669,18 @@ class Decoder:
         return self._scores[T_new]
 
     def sample(self, T_new, do_sample=True, temperature=1.0, top_k=50, top_p=0.95, repetition_penalty=1.0, eos=None, pad=None, seed=None,
-               use_graph=True, logprobs=False):
+               use_graph=True, logprobs=False, bin_stats=None):
         """After prefill(): T_new steps of HF generate's token loop (model_arch.py:82-108 -> GenerationMixin: logits processors, warpers,
         multinomial / arg-max, eos bookkeeping), every step one egomi_sample_rows launch + one cached decode step, all of them captured
         into ONE hipGraph (the draw counter and `pos` are launch constants, seed and done flags live in device memory).
         Returns (sequences [B, S0+T_new], processed scores fp32 [T_new, B, V]); rows that emitted `eos` continue with `pad`.
         logprobs=True: every step also runs one egomi_token_logprob launch on the raw logits, after the token kernel: self.lp_tok[:, t] is
         the chosen token's log-prob (0 once the row has finished), self.lp_sum / self.lp_n the row's sum and token count (its eos counted,
-        the pads not).  A graph of its own (the flag is part of the key); with False the loop has the launches it had."""
+        the pads not).  A graph of its own (the flag is part of the key); with False the loop has the launches it had.
+        bin_stats=(p0, nb): every step also runs one egomi_bin_stats launch on the raw logits, after those: self.bs_mass / bs_mean / bs_std /
+        bs_ent[:, t] describe the distribution token t was chosen from, over the bin ids p0 .. p0 + nb - 1 (values linspace(-1, 1, nb)); rows
+        that have finished are computed like any other (the caller cuts at the eos).  Again a graph of its own; None: no launch, no buffer."""
+        bs = self._bs_buffers(bin_stats) if bin_stats is not None else None
         S0, sc_buf = self.pos, self._score_buf(T_new)
         self._seed(seed)
         self.done_buf.zero_()
@@ -660,16 +696,24 @@ class Decoder:
                 sample_rows(self.lg, sc_buf[t], self.seq, S0 + t, 0, self.tok.view(-1), self.done, draw=t, **kw)
                 if logprobs:
                     token_logprob(self.lg, self.tok.view(-1), eos, lp_live, self.lp_tok, t, self.lp_sum, self.lp_n)
+                if bs is not None:
+                    bin_stats_rows(self.lg, *bs[:3], *bs[3], t)
                 if t + 1 < T_new:
                     self.step(S0 + t)
         key = (S0, T_new, kw["repetition_penalty"], kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], eos, pad)
-        self._run(steps, use_graph, key + ("logprobs",) if logprobs else key)
+        if logprobs:
+            key += ("logprobs",)
+        if bs is not None:
+            key += ("bin_stats", bs[0], bs[1])
+        self._run(steps, use_graph, key)
         self.pos = S0 + T_new
         return self.seq, sc_buf
 
-    def greedy(self, T_new, use_graph=True, keep_scores=True, logprobs=False):
+    def greedy(self, T_new, use_graph=True, keep_scores=True, logprobs=False, bin_stats=None):
         """After prefill(): T_new greedy tokens.  Returns (sequences [B,S0+T], scores list or None).  logprobs=True: one egomi_token_logprob
-        launch per step after the arg-max, into self.lp_tok / lp_sum / lp_n as in sample() (no eos here: every row counts every step)."""
+        launch per step after the arg-max, into self.lp_tok / lp_sum / lp_n as in sample() (no eos here: every row counts every step).
+        bin_stats=(p0, nb): one egomi_bin_stats launch per step after those, into self.bs_mass / bs_mean / bs_std / bs_ent as in sample()."""
+        bs = self._bs_buffers(bin_stats) if bin_stats is not None else None
         S0 = self.pos
         scores = None                                       # eager: fp32 clones; captured: views of one buffer the graph writes
         if keep_scores:
@@ -686,6 +730,8 @@ class Decoder:
                 argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
                 if logprobs:
                     token_logprob(self.lg, self.tok.view(-1), None, None, self.lp_tok, t, self.lp_sum, self.lp_n)
+                if bs is not None:
+                    bin_stats_rows(self.lg, *bs[:3], *bs[3], t)
                 if t + 1 < T_new:
                     self.step(S0 + t)
         self._run(steps, use_graph)                         # a fresh capture per call
@@ -741,27 +787,35 @@ class Decoder:
         ops.mm(h, w["lm_head.weight"], out=lg)
         return lg
 
-    def score(self, cand, eos, keep_logits=False, row_budget=16384):
+    def score(self, cand, eos, keep_logits=False, row_budget=16384, bin_stats=None):
         """After prefill() on a score_cache decoder: the log-probs of GIVEN suffix tokens cand int64 [B, T] (row r = b * K + j, candidate j
         of clip b) under teacher forcing, on the model's own weights.  Column 0 is read from the prefill logits; columns 1 .. T-1 come
         from ONE suffix pass over tokens 0 .. T-2 of every row (_suffix_pass), clips in groups of at most `row_budget` token rows (at
         least one clip), then one egomi_token_logprob launch per column on that pass's logits (row stride Tq * V) with the buffers, the
         eos rule and the column order of sample(logprobs=True): self.lp_tok[:, :T] (0 after a row's eos), self.lp_sum, self.lp_n.
         Columns past the longest candidate (candidate_lengths) are zero for every row: the pass and the launches stop there.
-        keep_logits: -> the pass's logits [B, Tq, V] (Tq = longest candidate - 1; row (r, t) scores token t + 1), else None."""
+        keep_logits: -> the pass's logits [B, Tq, V] (Tq = longest candidate - 1; row (r, t) scores token t + 1), else None.
+        bin_stats=(p0, nb): one egomi_bin_stats launch beside every egomi_token_logprob launch, on the same logits: self.bs_mass / bs_mean /
+        bs_std / bs_ent[:, :T], column t = the distribution candidate token t is scored under; 0 at and after a row's length, like lp_tok."""
         if not self.split or self.nb != 1:
             raise ValueError("score() needs a Decoder(score_cache=True)")
+        bs = self._bs_buffers(bin_stats) if bin_stats is not None else None
         K, S0, dev = self.cache.G, self.pos, self.eng.device
         R, T = cand.shape
         if R != self.B or T < 1 or T > self.cache.Tmax:
             raise ValueError(f"score(): candidates [{R}, {T}] do not fit the decoder's {self.B} rows / {self.cache.Tmax} suffix tokens")
         cand = cand.to(dev, torch.int64)
-        Tn = int(candidate_lengths(cand, eos).max())        # columns >= Tn count for no row
+        lens = candidate_lengths(cand, eos)
+        Tn = int(lens.max())                                # columns >= Tn count for no row
         toks = cand.t().contiguous()                        # [T, R]: a column's tokens are contiguous
         self._lp_buffers()
         self.lp_tok[:, :T].zero_()
         live = self.lp_live if eos is not None else None
         token_logprob(self.lg, toks[0], eos, live, self.lp_tok, 0, self.lp_sum, self.lp_n)
+        if bs is not None:
+            for buf in bs[3]:
+                buf[:, :T].zero_()
+            bin_stats_rows(self.lg, *bs[:3], *bs[3], 0)
         Tq, V, kept = Tn - 1, self.lg.shape[1], None
         if Tq > 0:
             per = max(1, int(row_budget) // (K * Tq))       # clips per pass
@@ -774,8 +828,14 @@ class Decoder:
                 for t in range(1, Tn):
                     token_logprob(lg[:, t - 1], toks[t, r0:r1], eos, None if live is None else live[r0:r1], self.lp_tok[r0:r1], t,
                                   self.lp_sum[r0:r1], self.lp_n[r0:r1])
+                    if bs is not None:
+                        bin_stats_rows(lg[:, t - 1], *bs[:3], *(buf[r0:r1] for buf in bs[3]), t)
                 if keep_logits:
                     kept[r0:r1] = lg
+        if bs is not None:                                  # the launches know no eos: cut every row at its length
+            past = torch.arange(T, device=dev)[None, :] >= lens[:, None]
+            for buf in bs[3]:
+                buf[:, :T].masked_fill_(past, 0.0)
         return kept
 
     # -- beam search / beam sampling ---------------------------------------------------------------

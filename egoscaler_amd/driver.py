@@ -141,7 +141,8 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
 
 
 @torch.no_grad()
-def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None):
+def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None,
+                   soft_decode=None):
     """Generation + metrics on the rank's shard (train.py:207-264, evaluate.py:104-154): prompts up to the first <tsep>,
     `generate` of the remaining positions (sampling with the reference's defaults top_k 50 / top_p 0.95 / T 1.0 unless
     args.val_sample is False -> greedy), cut at eos, de-tokenise, de-normalise (dataset.denorm), pad with the last step,
@@ -172,8 +173,20 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     args.mode_radius, else 0, is in their units).  The order is that of the scores select "logprob" ranks by (with args.rescore those of
     model.score()), otherwise centrality.  The record gains 'minADE_M' / 'minFDE_M' / 'brierADE_M' (T.metrics_modes; means over the clips
     with a mode), 'n_modes' (mean number of modes per clip), 'M' and 'mode_radius'; the dump gains one key,
-    "modes": {image id: {"index": [sample indices in pick order], "conf": [their probabilities]}}.  0 leaves both as they are."""
+    "modes": {image id: {"index": [sample indices in pick order], "conf": [their probabilities]}}.  0 leaves both as they are.
+
+    soft_decode (default: args.soft_decode, else False; num_beams == 1): generate(output_bin_stats=True) and, for sample 0 of every clip, the
+    soft trajectory beside the hard one: every coordinate is the conditional mean over the bins of the distribution its token was drawn
+    from (T.detokenize_soft; the step held by the prompt takes its bin centres, std 0, mass 1) instead of the drawn bin's centre.  It goes
+    through the same norm.denorm; the std is scaled by |its linear factor| (TargetNorm.denorm_scale: denorm is affine per dimension in every
+    mode).  The record gains 'ADE_soft' / 'FDE_soft' / 'n_soft' (T.metrics_batch, means over the parsed rows exactly as 'ADE' / 'FDE' / 'n'),
+    'sigma_mean' (the mean std over the parsed waypoints' x, y, z, in denorm's units) and 'bin_mass_min' (the mean over the parsed clips of
+    the smallest per-step bin mass); the dump gains one key, "soft": {image id: {"mean": [[6] per step], "std": [[6] per step]}}."""
     dims = model.dims
+    soft = bool(soft_decode if soft_decode is not None else getattr(args, "soft_decode", False))
+    if soft and num_beams != 1:
+        raise ValueError("--soft_decode reads the per-step distribution of sampled or greedy decoding: it needs num_beams == 1")
+    soft_sums, soft_dump = np.zeros(6), {}               # ADE_soft, FDE_soft, n_soft; sum and count of the stds; sum of the smallest masses
     K = int(num_samples if num_samples is not None else (getattr(args, "num_samples", 1) or 1))
     if K < 1:
         raise ValueError(f"num_samples has to be a strictly positive integer, but is {K}")
@@ -221,6 +234,8 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
             beam = {"num_return_sequences": K, "share_prompt": True}
             if select == "logprob":
                 beam["output_logprobs"] = True
+        if soft:
+            beam.update(output_bin_stats=True, bin_token_ids=(dims.tok.p0, dims.tok.num_bins))
         out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"], max_length=max_new,
                              do_sample=sample, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device),
                              kv_cache_dtype=getattr(args, "kv_cache_dtype", None),
@@ -247,6 +262,29 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
             sums[:5] += [ade[j], fde[j], T.average_displacement_error(gen[j][None], gt_h[j][None]),
                      T.anglar_distance(gen[j][:, 3:6].astype(np.float64), gt_h[j][:, 3:6].astype(np.float64)), 1.0]
             dump[int(ids_h[j])] = gen[j].tolist()                            # evaluate.py:150: keyed by image_id.item(), not by the dataset index
+        if soft:                                                             # sample 0 again, from the distributions its tokens were drawn from
+            head = prompts[:, -7:]                                           # the prompt's step: its bin centres, std 0, mass 1
+            isbin = (head >= dims.tok.p0) & (head < dims.tok.p0 + dims.tok.num_bins)
+            centre = T.bin_edges(dims.tok.num_bins, device)[(head - dims.tok.p0).clamp(0, dims.tok.num_bins - 1)].float()
+            zero = torch.zeros_like(centre)
+            smean, sstd, smass, sn = T.detokenize_soft(torch.cat([head, gen_ids], 1), dims.tok, args.num_steps + 4,
+                                                       torch.cat([torch.where(isbin, centre, zero), out.bin_mean[::K]], 1),
+                                                       torch.cat([zero, out.bin_std[::K]], 1), torch.cat([zero + 1, out.bin_mass[::K]], 1))
+            sn_h = torch.clamp(sn, max=Tn).cpu().numpy()
+            smean_h, sstd_h, smass_h = smean[:, :Tn].cpu().numpy(), sstd[:, :Tn].cpu().numpy(), smass[:, :Tn].cpu().numpy()
+            for j in range(len(idx)):
+                if 0 < sn_h[j] < Tn:
+                    smean_h[j, sn_h[j]:], sstd_h[j, sn_h[j]:] = smean_h[j, sn_h[j] - 1], sstd_h[j, sn_h[j] - 1]
+            mabs = batch["max_abs"].cpu().numpy()
+            sgen = norm.denorm(smean_h, mabs)
+            sstd_h = sstd_h * norm.denorm_scale(mabs)[:, None, :]
+            sade, sfde = T.metrics_batch(torch.from_numpy(np.ascontiguousarray(sgen, dtype=np.float32)).to(device), None, gt)
+            sade, sfde = sade.cpu().numpy(), sfde.cpu().numpy()
+            for j in range(len(idx)):
+                if sn_h[j] <= 0:
+                    continue
+                soft_sums += [sade[j], sfde[j], 1.0, float(sstd_h[j, :sn_h[j], :3].sum()), 3.0 * sn_h[j], float(smass_h[j, :sn_h[j]].min())]
+                soft_dump[int(ids_h[j])] = {"mean": sgen[j].tolist(), "std": sstd_h[j].tolist()}
         if K > 1:                                                            # all K samples of every clip: rows b * K + j
             vals, n = T.detokenize_batch(torch.cat([prompts[:, -7:].repeat_interleave(K, 0), all_ids], 1), dims.tok, args.num_steps + 4)
             n = torch.clamp(n, max=Tn)
@@ -288,9 +326,9 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
                     if slot[j] >= 0:
                         mode_sums[:4] += [oade[j], ofde[j], brier[j], 1.0]
     if world > 1:
-        t = torch.from_numpy(np.concatenate([sums, sel_sums, mode_sums])).to(device)
+        t = torch.from_numpy(np.concatenate([sums, sel_sums, mode_sums, soft_sums])).to(device)
         dist.all_reduce(t)
-        sums, sel_sums, mode_sums = t.cpu().numpy()[:8], t.cpu().numpy()[8:11], t.cpu().numpy()[11:]
+        sums, sel_sums, mode_sums, soft_sums = t.cpu().numpy()[:8], t.cpu().numpy()[8:11], t.cpu().numpy()[11:17], t.cpu().numpy()[17:]
     model.train()
     k = max(sums[4], 1.0)
     nan = float("nan")
@@ -309,6 +347,12 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
                     "brierADE_M": float(mode_sums[2] / mode_sums[3]) if mode_sums[3] else nan,
                     "n_modes": float(mode_sums[4] / mode_sums[5]) if mode_sums[5] else nan, "M": M, "mode_radius": radius})
         dump["modes"] = mode_dump
+    if soft:
+        ns = soft_sums[2]
+        rec.update({"ADE_soft": float(soft_sums[0] / ns) if ns else nan, "FDE_soft": float(soft_sums[1] / ns) if ns else nan, "n_soft": int(ns),
+                    "sigma_mean": float(soft_sums[3] / soft_sums[4]) if soft_sums[4] else nan,
+                    "bin_mass_min": float(soft_sums[5] / ns) if ns else nan})
+        dump["soft"] = soft_dump
     return rec, dump
 
 
@@ -449,8 +493,8 @@ def evaluate(args, model, data, split="test", device="cuda"):
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, dump)
-        dump = {k: v for p in parts for k, v in p.items() if k not in ("selected", "modes")}
-        for key in ("selected", "modes"):                   # --select / --num_modes: the ranks' picks, merged like the trajectories
+        dump = {k: v for p in parts for k, v in p.items() if k not in ("selected", "modes", "soft")}
+        for key in ("selected", "modes", "soft"):           # --select / --num_modes / --soft_decode: the ranks' entries, merged like the trajectories
             if any(key in p for p in parts):
                 dump[key] = {k: v for p in parts for k, v in p.get(key, {}).items()}
     if rank == 0:
@@ -522,7 +566,13 @@ def parse_args(argv=None):
     ap.add_argument("--mode_radius", type=float, default=0.0,
                     help="with --num_modes: a sample within this distance (mean displacement over all 6 dimensions, units of the de-normalised "
                          "trajectories) of an earlier mode is not a mode of its own; 0 suppresses exact duplicates only")
+    ap.add_argument("--soft_decode", action="store_true",
+                    help="validation / eval with --num_beams 1: also decode sample 0 of every clip softly, every coordinate as the mean over the "
+                         "bins of the distribution its token was drawn from; adds ADE_soft / FDE_soft / n_soft, sigma_mean (mean std of x, y, z) "
+                         "and bin_mass_min to the record and the soft trajectory with its std per image id to the dump")
     a = ap.parse_args(argv)
+    if a.soft_decode and a.num_beams != 1:
+        ap.error("--soft_decode reads the per-step distribution of sampled or greedy decoding: it needs --num_beams 1")
     if a.num_modes != 0 and not (a.num_samples > 1 and 1 <= a.num_modes <= a.num_samples <= 64):
         ap.error("--num_modes M picks M of K sampled trajectories: it needs --num_samples K > 1 and 1 <= M <= K <= 64")
     if a.mode_radius != a.mode_radius or a.mode_radius < 0 or (a.mode_radius > 0 and a.num_modes == 0):

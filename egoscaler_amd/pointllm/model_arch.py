@@ -148,6 +148,11 @@ class GenerateOutput:
     sequences_lengths: Optional[torch.Tensor] = None    # int32 [rows]: tokens counted (the eos included, the pads after it not)
     sample_scores: Optional[torch.Tensor] = None        # num_return_sequences = K > 1: fp32 [B, K], sum / length ** rank_length_penalty
     rank: Optional[torch.Tensor] = None                 # int32 [B, K]: the clip's sample indices by descending sample_scores
+    # generate(output_bin_stats=True) only: fp32 [rows, T'], column t = the raw distribution token t was drawn from, over the bin tokens; 0 after a row's eos
+    bin_mass: Optional[torch.Tensor] = None             # probability that the token is a bin token at all
+    bin_mean: Optional[torch.Tensor] = None             # E[value | bin token]
+    bin_std: Optional[torch.Tensor] = None              # the standard deviation of that conditional distribution
+    bin_entropy: Optional[torch.Tensor] = None          # its entropy in nats
 
 
 @dataclass
@@ -571,7 +576,8 @@ class TrajPointLLMForCausalLM(nn.Module):
     def generate(self, input_ids=None, attention_mask=None, point_clouds=None, max_length=20, temperature=1.0, top_k=50,
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
                  eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
-                 decode_weight_dtype=None, share_prompt=False, kv_cache_layout=None, output_logprobs=False, rank_length_penalty=1.0, **kwargs):
+                 decode_weight_dtype=None, share_prompt=False, kv_cache_layout=None, output_logprobs=False, rank_length_penalty=1.0, output_bin_stats=False,
+                 bin_token_ids=None, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -627,10 +633,23 @@ class TrajPointLLMForCausalLM(nn.Module):
         sum / length ** rank_length_penalty (HF's beam convention: 1.0 = mean log-prob, 0.0 = the sum) and rank int32 [B, K], the clip's
         sample indices by descending score (egomi_seq_rank): rows[b * K + rank[b, 0]] is the sample the model finds most probable.  Every
         other field, the row order and the drawn tokens are those of the call without it; no row is dropped.  Works in every non-beam mode;
-        num_beams > 1 raises ValueError (beams return sequences_scores)."""
+        num_beams > 1 raises ValueError (beams return sequences_scores).
+
+        output_bin_stats=True with bin_token_ids=(p0, nb) (num_beams == 1): the per-waypoint view of the same raw distribution.  The nb
+        contiguous token ids p0 .. p0 + nb - 1 stand for the values linspace(-1, 1, nb) (the tokenizer's first bin id and num_bins, as
+        traj.tokenize_batch / detokenize_batch take them; the model does not know its tokenizer, so the tuple is required).  One
+        egomi_bin_stats launch per step inside the token loop (csrc/logprob.hip; no raw logits are kept) fills four fp32 [rows, T'] fields,
+        column t describing the distribution token t was drawn from: bin_mass (the probability that the token is a bin token at all),
+        bin_mean (E[value | bin token]: a continuous estimate without the quantisation step 2 / (nb - 1)), bin_std and bin_entropy (nats) of
+        that conditional distribution; 0 after a row's eos.  It reports and changes nothing: the fed-back token, every other field and the
+        graphs of the calls without it are what they were; it combines with output_logprobs (two launches per step).  traj.detokenize_soft
+        turns bin_mean / bin_std / bin_mass into trajectories.  num_beams > 1 raises ValueError."""
         if output_logprobs and int(num_beams) > 1:
             raise ValueError("output_logprobs=True is for num_beams == 1; beam search returns `sequences_scores` (length-penalised sums of "
                              "the beams' log-probs)")
+        if output_bin_stats and int(num_beams) > 1:
+            raise ValueError("output_bin_stats=True is for num_beams == 1; beam search keeps no per-step distribution of its hypotheses")
+        bins = self._bin_window(bin_token_ids) if output_bin_stats else None
         if kv_cache_layout not in (None, "dense", "split"):
             raise ValueError(f"`kv_cache_layout` must be None, 'dense' or 'split', but is {kv_cache_layout!r}")
         split = kv_cache_layout == "split"
@@ -708,7 +727,7 @@ class TrajPointLLMForCausalLM(nn.Module):
             temperature, top_k, top_p = 1.0, 0, 1.0
         seq, sc = dec.sample(T, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                              eos=eos_token_id, pad=pad_token_id, seed=seed, use_graph=kwargs.get("use_graph", True),
-                             logprobs=bool(output_logprobs))
+                             logprobs=bool(output_logprobs), bin_stats=bins)
         stop = T
         if eos_token_id is not None and T > 0:             # HF leaves the loop after the step at which the last unfinished row emitted eos
             hit = seq[:, S0:] == eos_token_id
@@ -722,11 +741,23 @@ class TrajPointLLMForCausalLM(nn.Module):
             if n_ret > 1:
                 from ..decode import seq_rank
                 out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B // n_ret, n_ret, float(rank_length_penalty))
+        if bins is not None:
+            from ..decode import candidate_lengths
+            past = torch.arange(stop, device=dev)[None, :] >= candidate_lengths(out.sequences[:, S0:], eos_token_id)[:, None]
+            out.bin_mass, out.bin_mean, out.bin_std, out.bin_entropy = (
+                buf[:, :stop].masked_fill(past, 0.0) for buf in (dec.bs_mass, dec.bs_mean, dec.bs_std, dec.bs_ent))
         return out
+
+    def _bin_window(self, bin_token_ids):
+        from ..decode import bin_window
+        if bin_token_ids is None:
+            raise ValueError("output_bin_stats=True needs `bin_token_ids` = (first bin token id, number of bins), the tokenizer's p0 and "
+                             "num_bins: the model does not know which of its ids are bins")
+        return bin_window(bin_token_ids, self.dims.lm.vocab_size)
 
     @torch.no_grad()
     def score(self, input_ids, attention_mask, point_clouds, candidates, fps_start=None, eos_token_id="config", rank_length_penalty=1.0,
-              row_budget=16384):
+              row_budget=16384, output_bin_stats=False, bin_token_ids=None):
         """Teacher-forced log-probs of GIVEN trajectories on a shared prompt: candidates int64 [B, K, T] are K token suffixes per prompt
         (1 <= K <= 32; sampled by another call, another seed or a quantized decoder, proposed by a planner, or the ground truth at K = 1).
         Every prompt is prefilled once; ONE further pass over tokens 0 .. T-2 of all B * K candidates gives the logits of tokens 1 .. T-1
@@ -738,6 +769,9 @@ class TrajPointLLMForCausalLM(nn.Module):
         ignored and scores 0.  None counts all T tokens.  Returns a GenerateOutput with the fields, dtypes and row order (b * K + j) of
         generate(output_logprobs=True): token_logprobs fp32 [B*K, T], sequences_logprobs fp32 [B*K], sequences_lengths int32 [B*K],
         sample_scores fp32 [B, K] = sum / length ** rank_length_penalty, rank int32 [B, K]; sequences = the candidates [B*K, T], scores = ().
+        output_bin_stats=True with bin_token_ids=(p0, nb) (generate()'s arguments): also bin_mass / bin_mean / bin_std / bin_entropy fp32
+        [B, K, T] -- where the model would have put each waypoint coordinate of a proposal and how sure it was there (egomi_bin_stats on
+        the logits every token is scored under, clip group by clip group; no [B*K*T, V] logits are kept); 0 at and after a candidate's eos.
         ValueError: K > 32, T < 1, candidates of another rank / dtype / batch, S0 + T beyond max_position_embeddings.
         NotImplementedError: a list of ragged clouds."""
         from ..decode import Decoder, seq_rank
@@ -759,6 +793,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                              f"({self.dims.lm.max_position_embeddings})")
         if isinstance(eos_token_id, str):
             eos_token_id = self.dims.tok.eos
+        bins = self._bin_window(bin_token_ids) if output_bin_stats else None
         eng = self.engine
         eng.wait_param_updates()
         if fps_start is None and point_clouds is not None:
@@ -778,8 +813,11 @@ class TrajPointLLMForCausalLM(nn.Module):
                 cache[key] = dec
         self._prefill_prompts(dec, ids, attention_mask, point_clouds, fps_start, T)
         cand = candidates.to(eng.device).reshape(B * K, T)
-        dec.score(cand, eos_token_id, row_budget=row_budget)
+        dec.score(cand, eos_token_id, row_budget=row_budget, bin_stats=bins)
         out = GenerateOutput(sequences=cand.clone(), scores=())
+        if bins is not None:
+            out.bin_mass, out.bin_mean, out.bin_std, out.bin_entropy = (
+                buf[:, :T].reshape(B, K, T).clone() for buf in (dec.bs_mass, dec.bs_mean, dec.bs_std, dec.bs_ent))
         out.token_logprobs = dec.lp_tok[:, :T].clone()
         out.sequences_logprobs, out.sequences_lengths = dec.lp_sum.clone(), dec.lp_n.clone()
         out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B, K, float(rank_length_penalty))

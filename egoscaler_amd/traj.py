@@ -57,6 +57,30 @@ def detokenize_batch(ids: torch.Tensor, tok, max_steps: int):
     return out, n
 
 
+def detokenize_soft(ids: torch.Tensor, tok, max_steps: int, bin_mean, bin_std, bin_mass=None):
+    """detokenize_batch with the per-token statistics of generate(output_bin_stats=True) / egomi_bin_stats in place of the bin centres
+    (egomi_traj_detokenize_soft): the same scan of the same ids, and a step parsed from ids hit .. hit+5 takes
+    mean[b, n, c] = bin_mean[b, hit + c], std[b, n, c] = bin_std[b, hit + c], mass[b, n] = min over c of bin_mass[b, hit + c];
+    a copied-forward step repeats all three.  -> (mean f32 [B,max_steps,6], std f32 [B,max_steps,6], mass f32 [B,max_steps] or None without
+    bin_mass, n_steps i32 [B] = detokenize_batch's); steps >= n_steps are 0.
+    ids i64 [B,L] and the statistics [B, >= L] share their column numbering: pass the GENERATED part only (out.sequences[:, S0:] beside
+    out.bin_mean), or prepend the same number of columns to both."""
+    ids = ids.to(torch.int64).contiguous()
+    B, L = ids.shape
+    dev = ids.device
+    stats = [None if s is None else s.to(device=dev, dtype=torch.float32) for s in (bin_mean, bin_std, bin_mass)]
+    for s in stats:
+        if s is not None and (s.dim() != 2 or s.shape[0] != B or s.shape[1] < L):
+            raise ValueError(f"the bin statistics must be [B, >= L] = [{B}, >= {L}] like ids, not {tuple(s.shape)}")
+    bm, bsd, bms = (None if s is None else s[:, :L].contiguous() for s in stats)
+    mean = torch.zeros(B, max_steps, 6, dtype=torch.float32, device=dev)
+    std = torch.zeros(B, max_steps, 6, dtype=torch.float32, device=dev)
+    mass = None if bms is None else torch.zeros(B, max_steps, dtype=torch.float32, device=dev)
+    n = torch.empty(B, dtype=torch.int32, device=dev)
+    call("egomi_traj_detokenize_soft", ids, B, L, tok.num_bins, tok.p0, tok.tsep, tok.eos, bm, bsd, bms, L, max_steps, mean, std, mass, n, S())
+    return mean, std, mass, n
+
+
 def metrics_batch(gen, n_gen, gt, n_gt=None):
     """ADE / FDE per sample (float64), generated trajectories padded with their last step or cut to
     the ground-truth length (models/utils/metrics.py:40-52)."""
@@ -411,3 +435,15 @@ class TargetNorm:
             t = t * np.asarray(max_abs)[:, None, :]
             return t * self.std + self.mean
         return t
+
+    def denorm_scale(self, max_abs):
+        """|d denorm / d value| per sample and dimension, [B,6]: denorm is affine in every mode and every dimension (norm: v -> (v + 1) / 2 *
+        (max - min) + min on x, y, z and v -> pi v on the rotations; standard: v -> v max_abs std + mean; none: the identity), so a
+        standard deviation in normalised units becomes one in denorm's units by this factor."""
+        m = np.asarray(max_abs, dtype=np.float64)
+        if self.mode == "norm":
+            f = [(WORKSPACE["max_" + k] - WORKSPACE["min_" + k]) / 2.0 for k in "xyz"] + [np.pi] * 3
+            return np.broadcast_to(np.asarray(f), m.shape).copy()
+        if self.mode == "standard":
+            return np.abs(m * self.std)
+        return np.ones_like(m)

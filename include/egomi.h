@@ -326,6 +326,22 @@ int egomi_token_logprob(const void* logits, int64_t ld, int R, int V, const int6
                         int64_t ld_lp, int col, float* sum_lp, int32_t* n_tok, int dtype, egomi_stream_t stream);
 int egomi_seq_rank(const float* sum_lp, const int32_t* n_tok, int B, int K, float length_penalty, float* score, int32_t* order,
                    egomi_stream_t stream);
+/* bin_stats: the step's distribution over the waypoint bins (csrc/logprob.hip).  Token ids p0 .. p0 + nb - 1 stand for the values
+ * values[0 .. nb-1] (float64 [nb], device memory: numpy.linspace(-1, 1, nb) for the trajectory tokens, the table the A14 entry points
+ * take as `bins`).  One launch per decode step on the RAW logits token_logprob reads (bf16 or fp32 [R, V], row stride ld >= V); it keeps
+ * no state and reads no token, so it may run anywhere after the logits exist.  Per row: m = max x, s = sum exp(x - m) over all V
+ * (token_logprob's pass, the same code); w_i = exp(x[p0 + i] - m) in fp32 (-inf -> 0), Z = sum w_i, and in float64, in a fixed order:
+ *   mass[r*ld_out + col] = Z / s                          the probability that the step's token is a bin token at all
+ *   mean[r*ld_out + col] = sum w_i v_i / Z                E[v | bin]
+ *   std [r*ld_out + col] = sqrt(sum w_i (v_i - mean)^2 / Z)   (the centred second pass, not E[v^2] - mean^2)
+ *   ent [r*ld_out + col] = -sum q_i log q_i, q_i = w_i / Z, 0 log 0 = 0, in nats
+ * all stored as fp32.  Every bin -inf (Z = 0): mass = 0, mean = std = ent = NaN.  A NaN logit anywhere in the row: mass = NaN; inside
+ * the window: all four NaN.  Nothing outside [row, row + V) is read.  `col` is a launch constant; no atomics; a row's bits depend on
+ * (V, p0, nb, dtype) and its values only, not on R, its slot, its alignment or ld; a replay is bit-equal.
+ * Returns BADARG (a NULL pointer, unknown dtype), SHAPE (R, V <= 0, ld < V, nb outside 1 .. 1024, p0 < 0, p0 + nb > V, col outside
+ * [0, ld_out)), UNSUPPORTED (logits not aligned to their element size). */
+int egomi_bin_stats(const void* logits, int64_t ld, int R, int V, int p0, int nb, const double* values, float* mass, float* mean,
+                    float* std, float* ent, int64_t ld_out, int col, int dtype, egomi_stream_t stream);
 /* Beam search / beam sampling (num_beams > 1): HF GenerationMixin._beam_search, transformers 5.15 generation/utils.py:3208-3560.
  * Logical rows r = b * nb + j (item b, beam j), R = B * nb.  Every step is one beam_rows + one beam_update launch; ctl (int32 [6], device)
  * holds the loop-open flag [0] and the iteration count [1]: once a step closes the loop, both return at once, so T captured steps
@@ -500,6 +516,16 @@ int egomi_traj_tokenize(const float* traj, const int32_t* steps, int B, int Tmax
                         int32_t* err, egomi_stream_t stream);
 int egomi_traj_detokenize(const int64_t* ids, int B, int L, const double* bins, int num_bins, int64_t p0, int64_t tsep, int64_t eos,
                           int Tmax, float* out, int32_t* n_steps, egomi_stream_t stream);
+/* detokenize_soft: `detokenize`'s scan on the same ids (cut at the first eos, split on <tsep>, first run of six bin ids per segment,
+ *              copy-forward), gathering egomi_bin_stats' per-token results instead of bin centres.  bin_mean, bin_std f32 [B, >= L] (row
+ *              stride ld_stat; column j describes ids[:, j]), bin_mass likewise or NULL.  A step parsed from ids hit .. hit+5:
+ *              mean[b,n,c] = bin_mean[b,hit+c], std[b,n,c] = bin_std[b,hit+c], mass[b,n] = min over c of bin_mass[b,hit+c] (a NaN among
+ *              them gives NaN); a copied step repeats all three.  mean, std f32 [B,Tmax,6], mass f32 [B,Tmax] (NULL exactly when bin_mass
+ *              is), n_steps i32 [B] = `detokenize`'s on the same ids; steps >= n_steps are not written.  BADARG (NULL ids / bin_mean /
+ *              bin_std / mean / std / n_steps, bin_mass without mass or the reverse), SHAPE (a size <= 0, num_bins <= 1, ld_stat < L). */
+int egomi_traj_detokenize_soft(const int64_t* ids, int B, int L, int num_bins, int64_t p0, int64_t tsep, int64_t eos, const float* bin_mean,
+                               const float* bin_std, const float* bin_mass, int64_t ld_stat, int Tmax, float* mean, float* std,
+                               float* mass, int32_t* n_steps, egomi_stream_t stream);
 int egomi_traj_metrics(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int Tmax, int D, double* ade,
                        double* fde, egomi_stream_t stream);
 /* metrics_min: best-of-K (minADE_K / minFDE_K; the reference's run_validation, train.py:207-264, scores one draw per clip with
