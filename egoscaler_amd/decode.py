@@ -483,6 +483,23 @@ class Decoder:
             self._bs_values[nb] = bin_edges(nb, dev)
         return p0, nb, self._bs_values[nb], (self.bs_mass, self.bs_mean, self.bs_std, self.bs_ent)
 
+    def _readouts(self, logprobs, bin_stats, eos):
+        """The per-step readouts of sample() / greedy() / score(): prepares their buffers (_lp_buffers, _bs_buffers) and -> (emit, key).
+        emit(logits, tokens, col, rows=slice(None)) issues, for decoder rows `rows`, the egomi_token_logprob launch of logprobs=True (into
+        lp_tok[:, col], lp_sum, lp_n; lp_live stops a row's count after its `eos`) and then the egomi_bin_stats launch of bin_stats=(p0, nb)
+        (into bs_mass / bs_mean / bs_std / bs_ent[:, col]), both on the raw `logits`.  key: what the readouts add to a graph key."""
+        bs = self._bs_buffers(bin_stats) if bin_stats is not None else None
+        if logprobs:
+            self._lp_buffers()
+        live = self.lp_live if logprobs and eos is not None else None
+
+        def emit(logits, tokens, col, rows=slice(None)):
+            if logprobs:
+                token_logprob(logits, tokens, eos, None if live is None else live[rows], self.lp_tok[rows], col, self.lp_sum[rows], self.lp_n[rows])
+            if bs is not None:
+                bin_stats_rows(logits, *bs[:3], *(buf[rows] for buf in bs[3]), col)
+        return emit, (("logprobs",) if logprobs else ()) + (("bin_stats", bs[0], bs[1]) if bs is not None else ())
+
     def _merge_lora(self):
         """LoRA: the decode steps multiply merged copies W + s B A of the adapted projections (one fp32 sum, rounded once; csrc/lora.hip);
         the prefill runs through the engine on the unmerged adapters.  A decoder is made for one set of adapter values: the model's decoder
@@ -680,32 +697,22 @@ class Decoder:
         bin_stats=(p0, nb): every step also runs one egomi_bin_stats launch on the raw logits, after those: self.bs_mass / bs_mean / bs_std /
         bs_ent[:, t] describe the distribution token t was chosen from, over the bin ids p0 .. p0 + nb - 1 (values linspace(-1, 1, nb)); rows
         that have finished are computed like any other (the caller cuts at the eos).  Again a graph of its own; None: no launch, no buffer."""
-        bs = self._bs_buffers(bin_stats) if bin_stats is not None else None
+        emit, readout_key = self._readouts(logprobs, bin_stats, eos)
         S0, sc_buf = self.pos, self._score_buf(T_new)
         self._seed(seed)
         self.done_buf.zero_()
         self.done = self.done_buf if eos is not None else None
-        if logprobs:
-            self._lp_buffers()
-        lp_live = self.lp_live if logprobs and eos is not None else None
         kw = dict(repetition_penalty=float(repetition_penalty or 1.0), temperature=float(temperature or 1.0), top_k=int(top_k or 0),
                   top_p=float(1.0 if top_p is None else top_p), do_sample=bool(do_sample), rng=self.rng, eos=eos, pad=pad)
 
         def steps():
             for t in range(T_new):
                 sample_rows(self.lg, sc_buf[t], self.seq, S0 + t, 0, self.tok.view(-1), self.done, draw=t, **kw)
-                if logprobs:
-                    token_logprob(self.lg, self.tok.view(-1), eos, lp_live, self.lp_tok, t, self.lp_sum, self.lp_n)
-                if bs is not None:
-                    bin_stats_rows(self.lg, *bs[:3], *bs[3], t)
+                emit(self.lg, self.tok.view(-1), t)
                 if t + 1 < T_new:
                     self.step(S0 + t)
         key = (S0, T_new, kw["repetition_penalty"], kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], eos, pad)
-        if logprobs:
-            key += ("logprobs",)
-        if bs is not None:
-            key += ("bin_stats", bs[0], bs[1])
-        self._run(steps, use_graph, key)
+        self._run(steps, use_graph, key + readout_key)
         self.pos = S0 + T_new
         return self.seq, sc_buf
 
@@ -713,13 +720,11 @@ class Decoder:
         """After prefill(): T_new greedy tokens.  Returns (sequences [B,S0+T], scores list or None).  logprobs=True: one egomi_token_logprob
         launch per step after the arg-max, into self.lp_tok / lp_sum / lp_n as in sample() (no eos here: every row counts every step).
         bin_stats=(p0, nb): one egomi_bin_stats launch per step after those, into self.bs_mass / bs_mean / bs_std / bs_ent as in sample()."""
-        bs = self._bs_buffers(bin_stats) if bin_stats is not None else None
+        emit, _ = self._readouts(logprobs, bin_stats, None)
         S0 = self.pos
         scores = None                                       # eager: fp32 clones; captured: views of one buffer the graph writes
         if keep_scores:
             scores = list(torch.zeros(T_new, self.B, self.lg.shape[1], dtype=torch.float32, device=self.eng.device)) if use_graph else []
-        if logprobs:
-            self._lp_buffers()
 
         def steps():
             for t in range(T_new):
@@ -728,10 +733,7 @@ class Decoder:
                 elif keep_scores:
                     scores.append(self.lg.float().clone())
                 argmax_rows(self.lg, self.tok.view(-1), self.seq, S0 + t)
-                if logprobs:
-                    token_logprob(self.lg, self.tok.view(-1), None, None, self.lp_tok, t, self.lp_sum, self.lp_n)
-                if bs is not None:
-                    bin_stats_rows(self.lg, *bs[:3], *bs[3], t)
+                emit(self.lg, self.tok.view(-1), t)
                 if t + 1 < T_new:
                     self.step(S0 + t)
         self._run(steps, use_graph)                         # a fresh capture per call
@@ -799,7 +801,8 @@ class Decoder:
         bs_std / bs_ent[:, :T], column t = the distribution candidate token t is scored under; 0 at and after a row's length, like lp_tok."""
         if not self.split or self.nb != 1:
             raise ValueError("score() needs a Decoder(score_cache=True)")
-        bs = self._bs_buffers(bin_stats) if bin_stats is not None else None
+        emit, _ = self._readouts(True, bin_stats, eos)
+        bs_bufs = (self.bs_mass, self.bs_mean, self.bs_std, self.bs_ent) if bin_stats is not None else ()
         K, S0, dev = self.cache.G, self.pos, self.eng.device
         R, T = cand.shape
         if R != self.B or T < 1 or T > self.cache.Tmax:
@@ -808,14 +811,9 @@ class Decoder:
         lens = candidate_lengths(cand, eos)
         Tn = int(lens.max())                                # columns >= Tn count for no row
         toks = cand.t().contiguous()                        # [T, R]: a column's tokens are contiguous
-        self._lp_buffers()
-        self.lp_tok[:, :T].zero_()
-        live = self.lp_live if eos is not None else None
-        token_logprob(self.lg, toks[0], eos, live, self.lp_tok, 0, self.lp_sum, self.lp_n)
-        if bs is not None:
-            for buf in bs[3]:
-                buf[:, :T].zero_()
-            bin_stats_rows(self.lg, *bs[:3], *bs[3], 0)
+        for buf in (self.lp_tok, *bs_bufs):
+            buf[:, :T].zero_()
+        emit(self.lg, toks[0], 0)
         Tq, V, kept = Tn - 1, self.lg.shape[1], None
         if Tq > 0:
             per = max(1, int(row_budget) // (K * Tq))       # clips per pass
@@ -826,15 +824,12 @@ class Decoder:
                 r0, r1 = b0 * K, b1 * K
                 lg = self._suffix_pass(cand[r0:r1, :Tq].contiguous(), b0, b1).view(r1 - r0, Tq, V)
                 for t in range(1, Tn):
-                    token_logprob(lg[:, t - 1], toks[t, r0:r1], eos, None if live is None else live[r0:r1], self.lp_tok[r0:r1], t,
-                                  self.lp_sum[r0:r1], self.lp_n[r0:r1])
-                    if bs is not None:
-                        bin_stats_rows(lg[:, t - 1], *bs[:3], *(buf[r0:r1] for buf in bs[3]), t)
+                    emit(lg[:, t - 1], toks[t, r0:r1], t, slice(r0, r1))
                 if keep_logits:
                     kept[r0:r1] = lg
-        if bs is not None:                                  # the launches know no eos: cut every row at its length
+        if bs_bufs:                                         # the launches know no eos: cut every row at its length
             past = torch.arange(T, device=dev)[None, :] >= lens[:, None]
-            for buf in bs[3]:
+            for buf in bs_bufs:
                 buf[:, :T].masked_fill_(past, 0.0)
         return kept
 

@@ -140,6 +140,228 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
     return max(1, -(-int(bs) // (max(1, int(grad_accum_steps)) * max(1, int(world)))))
 
 
+def check_val_options(K, num_beams, sample, select, rescore, M, radius, soft, decoding_rules=True):
+    """The rules of --num_samples / --select / --rescore / --num_modes / --mode_radius / --soft_decode on their resolved values, one text
+    per rule; raises ValueError.  run_validation applies all of them; parse_args applies the first four (decoding_rules=False) and exits
+    on them: the last four stay errors of the run itself (main() raises ValueError there, and tests pin that)."""
+    if soft and num_beams != 1:
+        raise ValueError("--soft_decode reads the per-step distribution of sampled or greedy decoding: it needs num_beams == 1")
+    if M < 0 or (M > 0 and not (K > 1 and M <= K <= 64)):
+        raise ValueError(f"--num_modes M picks M of K samples: it needs --num_samples K > 1 and 1 <= M <= K <= 64, not M = {M}, K = {K}")
+    if radius != radius or radius < 0 or (radius > 0 and M == 0):
+        raise ValueError(f"--mode_radius is a distance >= 0 and needs --num_modes M > 0, not {radius} with M = {M}")
+    if rescore and not (K > 1 and select == "logprob"):
+        raise ValueError("--rescore re-ranks sampled trajectories by log-prob: it needs --num_samples K > 1 and --select logprob")
+    if not decoding_rules:
+        return
+    if K < 1:
+        raise ValueError(f"num_samples has to be a strictly positive integer, but is {K}")
+    if K > 1 and (num_beams != 1 or not sample):
+        raise ValueError("num_samples > 1 draws samples: it cannot be combined with --val_greedy or --num_beams > 1")
+    if select not in ("none", "logprob", "medoid"):
+        raise ValueError(f"select must be none, logprob or medoid, not {select!r}")
+    if select != "none" and K < 2:
+        raise ValueError("--select chooses among samples: it needs --num_samples K > 1")
+
+
+def val_options(args, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None, soft_decode=None):
+    """run_validation's options, each resolved as: the explicit keyword, else `args`, else its default; checked (check_val_options)."""
+    pick = lambda explicit, name, default: explicit if explicit is not None else (getattr(args, name, default) or default)
+    o = types.SimpleNamespace(K=int(pick(num_samples, "num_samples", 1)), num_beams=num_beams, sample=bool(getattr(args, "val_sample", True)),
+                              select=str(pick(select, "select", "none")), rescore=bool(getattr(args, "rescore", False)),
+                              M=int(pick(num_modes, "num_modes", 0)), radius=float(pick(mode_radius, "mode_radius", 0.0)),
+                              soft=bool(pick(soft_decode, "soft_decode", False)))
+    check_val_options(**vars(o))
+    return o
+
+
+# what run_validation sums over the parsed clips of every rank, by name and in the order of the all-reduced tensor
+BASE_SUMS = ("ADE", "FDE", "ADE_as_called", "GD", "n")
+BEST_SUMS = ("minADE", "minFDE", "n_min")
+SEL_SUMS = ("ADE_sel", "FDE_sel", "n_sel")
+MODE_SUMS = ("minADE_M", "minFDE_M", "brierADE_M", "n_M", "modes", "clips_M")      # n_M: clips with a mode; modes over clips_M clips
+SOFT_SUMS = ("ADE_soft", "FDE_soft", "n_soft", "std", "n_std", "mass_min")        # std over n_std coordinates; the smallest masses
+
+
+def _add(sums, **terms):
+    for name, v in terms.items():
+        sums[name] += float(v)                               # float64, whatever the term's own type
+
+
+def _mean(sums, name, count):
+    """sums[name] / sums[count] as a plain float (the records go into checkpoints read with weights_only=True), NaN without a count."""
+    return float(sums[name] / sums[count]) if sums[count] else float("nan")
+
+
+def reduce_sums(sums, device):
+    """The sums of all ranks: one float64 tensor in the mapping's order, all-reduced and read back by name."""
+    t = torch.tensor(list(sums.values()), dtype=torch.float64).to(device)
+    dist.all_reduce(t)
+    return dict(zip(sums, t.cpu().tolist()))
+
+
+def pad_last_step(vals, n):
+    """Rows of vals [R, Tn, ...] (numpy, in place) with 0 < n[r] < Tn parsed steps repeat step n[r] - 1 from n[r] on (train.py:252-256)."""
+    for r in range(len(vals)):
+        if 0 < n[r] < vals.shape[1]:
+            vals[r, n[r]:] = vals[r, n[r] - 1]
+    return vals
+
+
+def parse_trajectories(ids, tok, num_steps, Tn, norm, max_abs, device):
+    """Token ids (the prompt's last seven tokens, which hold step 0 + <tsep>, then the generated ones) [R, L] -> the de-normalised
+    trajectories: de-tokenise, clamp to the Tn ground-truth steps, pad with the last parsed step, norm.denorm with max_abs [R, 6] (numpy).
+    -> (numpy [R, Tn, 6], its fp32 device copy, parsed steps per row numpy [R]; 0 = detokenize_traj returned None, train.py:249-250)."""
+    vals, n = T.detokenize_batch(ids, tok, num_steps + 4)
+    n_h = torch.clamp(n, max=Tn).cpu().numpy()
+    gen = norm.denorm(pad_last_step(vals[:, :Tn].cpu().numpy(), n_h), max_abs)
+    return gen, torch.from_numpy(np.ascontiguousarray(gen, dtype=np.float32)).to(device), n_h
+
+
+def generate_kwargs(o, args, tok):
+    """generate()'s keyword arguments for the decoding mode: K samples on a shared prompt, beams, or neither; the bin statistics."""
+    kw = {"output_bin_stats": True, "bin_token_ids": (tok.p0, tok.num_bins)} if o.soft else {}
+    if o.K > 1:
+        kw.update(num_return_sequences=o.K, share_prompt=True, **({"output_logprobs": True} if o.select == "logprob" else {}))
+    elif o.num_beams != 1:
+        kw.update(num_beams=o.num_beams, kv_cache_layout=getattr(args, "kv_cache_layout", None))
+    return kw
+
+
+def generate_batch(model, data, args, device, o, idx, norm):
+    """One batch of the pass: generate() for the clips idx, and all its K * len(idx) rows parsed (row b * K + j = sample j of clip b)."""
+    tok = model.dims.tok
+    batch = data.batch(idx, device, args.max_traj_token)
+    prompts, gt = batch["prompts"], batch["trajectories"]
+    fps0 = torch.zeros(len(idx), dtype=torch.int32, device=device)
+    out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"],
+                         max_length=batch["tokens"].shape[1] - prompts.shape[1], do_sample=o.sample, fps_start=fps0,
+                         kv_cache_dtype=getattr(args, "kv_cache_dtype", None),
+                         decode_weight_dtype=getattr(args, "decode_weight_dtype", None), **generate_kwargs(o, args, tok))
+    all_ids = out.sequences[:, prompts.shape[1]:]
+    head = prompts[:, -7:]                                   # the prompt holds the first step; with its <tsep> it is parsed like the rest
+    mabs = batch["max_abs"].cpu().numpy()
+    gen, gen_d, n_h = parse_trajectories(torch.cat([head.repeat_interleave(o.K, 0), all_ids], 1), tok, args.num_steps, gt.shape[1], norm,
+                                         np.repeat(mabs, o.K, axis=0), device)
+    return types.SimpleNamespace(batch=batch, prompts=prompts, head=head, gt=gt, gt_h=gt.cpu().numpy(), mabs=mabs, fps0=fps0, out=out,
+                                 all_ids=all_ids, ids_h=batch["image_ids"].cpu().numpy(), gen=gen, gen_d=gen_d, n_h=n_h,
+                                 gen_k=gen_d.view(len(idx), o.K, gt.shape[1], -1),
+                                 n_k=torch.from_numpy((n_h > 0).astype(np.int32) * gt.shape[1]).to(device).view(len(idx), o.K))
+
+
+# -- the parts: each adds one batch to the sums and the dump, and turns its sums into its record keys -----------------------------------
+def base_batch(o, b, sums, dump):
+    """Sample 0 of every clip (K = 1: every row): ADE / FDE / ADE_as_called / GD over the parsed ones; the dump's trajectory."""
+    gen, n_h = b.gen[::o.K], b.n_h[::o.K]
+    ade, fde = (t.cpu().numpy() for t in T.metrics_batch(b.gen_d[::o.K], None, b.gt))
+    for j in range(len(gen)):
+        if n_h[j] <= 0:
+            continue
+        _add(sums, ADE=ade[j], FDE=fde[j], ADE_as_called=T.average_displacement_error(gen[j][None], b.gt_h[j][None]),
+             GD=T.anglar_distance(gen[j][:, 3:6].astype(np.float64), b.gt_h[j][:, 3:6].astype(np.float64)), n=1)
+        dump[int(b.ids_h[j])] = gen[j].tolist()              # evaluate.py:150: keyed by image_id.item(), not by the dataset index
+
+
+def base_record(o, sums):
+    return {"ADE": _mean(sums, "ADE", "n"), "FDE": _mean(sums, "FDE", "n"), "ADE_as_called": _mean(sums, "ADE_as_called", "n"),
+            "GD": _mean(sums, "GD", "n"), "n": int(sums["n"])}
+
+
+def best_of_batch(o, b, sums, dump):
+    """All K samples of every clip: minADE / minFDE; the dump keeps the K trajectories (None for an unparsed one)."""
+    made, mfde, best = (t.cpu().numpy() for t in T.metrics_best_of(b.gen_k, b.n_k, b.gt))
+    for j in range(len(best)):
+        if best[j] >= 0:
+            _add(sums, minADE=made[j], minFDE=mfde[j], n_min=1)
+        dump[int(b.ids_h[j])] = [b.gen[j * o.K + i].tolist() if b.n_h[j * o.K + i] > 0 else None for i in range(o.K)]
+
+
+def best_of_record(o, sums):
+    return {"minADE": _mean(sums, "minADE", "n_min"), "minFDE": _mean(sums, "minFDE", "n_min"), "n_min": int(sums["n_min"]), "K": o.K}
+
+
+def sample_ranking(model, o, b):
+    """What ranks the K samples of select "logprob" (and orders the modes): generate()'s own log-probs, with o.rescore model.score() on
+    the same samples (the model's own weights); None for any other select."""
+    if o.select != "logprob":
+        return None
+    if not o.rescore:
+        return b.out
+    return model.score(b.prompts, b.batch["prompt_masks"], b.batch["pcrgbs"], b.all_ids.reshape(len(b.ids_h), o.K, -1), fps_start=b.fps0)
+
+
+def select_batch(o, b, ranked, sums, picked):
+    """The one of K a user without the ground truth would keep: its ADE / FDE; picked[image id] = its index."""
+    pick = ranked.rank[:, 0].contiguous() if o.select == "logprob" else T.select_medoid(b.gen_k, b.n_k)[0]
+    sade, sfde, pick = (t.cpu().numpy() for t in (*T.metrics_selected(b.gen_k, b.n_k, b.gt, None, pick), pick))
+    for j in range(len(pick)):
+        picked[int(b.ids_h[j])] = int(pick[j])
+        if not np.isnan(sade[j]):
+            _add(sums, ADE_sel=sade[j], FDE_sel=sfde[j], n_sel=1)
+
+
+def select_record(o, sums):
+    return {"ADE_sel": _mean(sums, "ADE_sel", "n_sel"), "FDE_sel": _mean(sums, "FDE_sel", "n_sel"), "n_sel": int(sums["n_sel"]),
+            "select": o.select}
+
+
+def modes_batch(o, b, ranked, sums, mode_dump):
+    """M different ones of the K, ordered by the ranking's scores or by centrality: their best-of metrics; indices and probabilities."""
+    md, cf, _, nmd, _ = T.select_modes(b.gen_k, b.n_k, None if ranked is None else ranked.sample_scores, o.M, o.radius)
+    oade, ofde, slot, brier = (t.cpu().numpy() for t in T.metrics_modes(b.gen_k, b.n_k, b.gt, None, md, cf))
+    md, cf, nmd = md.cpu().numpy(), cf.cpu().numpy(), nmd.cpu().numpy()
+    for j in range(len(nmd)):
+        mode_dump[int(b.ids_h[j])] = {"index": md[j, :nmd[j]].tolist(), "conf": cf[j, :nmd[j]].tolist()}
+        _add(sums, modes=nmd[j], clips_M=1)
+        if slot[j] >= 0:
+            _add(sums, minADE_M=oade[j], minFDE_M=ofde[j], brierADE_M=brier[j], n_M=1)
+
+
+def modes_record(o, sums):
+    return {"minADE_M": _mean(sums, "minADE_M", "n_M"), "minFDE_M": _mean(sums, "minFDE_M", "n_M"),
+            "brierADE_M": _mean(sums, "brierADE_M", "n_M"), "n_modes": _mean(sums, "modes", "clips_M"), "M": o.M, "mode_radius": o.radius}
+
+
+def soft_batch(o, b, tok, num_steps, norm, sums, soft_dump):
+    """Sample 0 of every clip again, from the distributions its tokens were drawn from: the soft trajectory and its std."""
+    device, Tn = b.head.device, b.gt.shape[1]
+    isbin = (b.head >= tok.p0) & (b.head < tok.p0 + tok.num_bins)   # the prompt's step: its bin centres, std 0, mass 1
+    centre = T.bin_edges(tok.num_bins, device)[(b.head - tok.p0).clamp(0, tok.num_bins - 1)].float()
+    zero = torch.zeros_like(centre)
+    smean, sstd, smass, sn = T.detokenize_soft(torch.cat([b.head, b.all_ids[::o.K]], 1), tok, num_steps + 4,
+                                               torch.cat([torch.where(isbin, centre, zero), b.out.bin_mean[::o.K]], 1),
+                                               torch.cat([zero, b.out.bin_std[::o.K]], 1), torch.cat([zero + 1, b.out.bin_mass[::o.K]], 1))
+    sn_h, smass_h = torch.clamp(sn, max=Tn).cpu().numpy(), smass[:, :Tn].cpu().numpy()
+    sgen = norm.denorm(pad_last_step(smean[:, :Tn].cpu().numpy(), sn_h), b.mabs)
+    sstd_h = pad_last_step(sstd[:, :Tn].cpu().numpy(), sn_h) * norm.denorm_scale(b.mabs)[:, None, :]
+    sade, sfde = (t.cpu().numpy() for t in T.metrics_batch(torch.from_numpy(np.ascontiguousarray(sgen, dtype=np.float32)).to(device), None, b.gt))
+    for j in range(len(sn_h)):
+        if sn_h[j] <= 0:
+            continue
+        _add(sums, ADE_soft=sade[j], FDE_soft=sfde[j], n_soft=1, std=sstd_h[j, :sn_h[j], :3].sum(), n_std=3.0 * sn_h[j],
+             mass_min=smass_h[j, :sn_h[j]].min())
+        soft_dump[int(b.ids_h[j])] = {"mean": sgen[j].tolist(), "std": sstd_h[j].tolist()}
+
+
+def soft_record(o, sums):
+    return {"ADE_soft": _mean(sums, "ADE_soft", "n_soft"), "FDE_soft": _mean(sums, "FDE_soft", "n_soft"), "n_soft": int(sums["n_soft"]),
+            "sigma_mean": _mean(sums, "std", "n_std"), "bin_mass_min": _mean(sums, "mass_min", "n_soft")}
+
+
+def rank_batches(n, per, rank, world, max_batches=None):
+    """The clips of this rank, batch by batch.  The reference's val / test DataLoader (train.py:79-82, evaluate.py:93-100: batch_size=bs,
+    shuffle=False, NO drop_last) keeps the short last batch: every sample is generated for and lands in the dump.  A batch is dealt over
+    the ranks; the short one is split raggedly and a rank whose share is empty skips it (the only collective of the pass is the
+    all-reduce of the sums)."""
+    gb = per * world
+    nb = -(-n // gb)
+    for bi in range(nb if max_batches is None else min(nb, max_batches)):
+        n_here = min(gb, n - bi * gb)
+        lo, hi = shard_range(gb, rank, world) if n_here == gb else ragged_shard_range(n_here, rank, world)
+        if hi > lo:
+            yield list(range(bi * gb + lo, bi * gb + hi))
+
+
 @torch.no_grad()
 def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None,
                    soft_decode=None):
@@ -182,176 +404,38 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     mode).  The record gains 'ADE_soft' / 'FDE_soft' / 'n_soft' (T.metrics_batch, means over the parsed rows exactly as 'ADE' / 'FDE' / 'n'),
     'sigma_mean' (the mean std over the parsed waypoints' x, y, z, in denorm's units) and 'bin_mass_min' (the mean over the parsed clips of
     the smallest per-step bin mass); the dump gains one key, "soft": {image id: {"mean": [[6] per step], "std": [[6] per step]}}."""
-    dims = model.dims
-    soft = bool(soft_decode if soft_decode is not None else getattr(args, "soft_decode", False))
-    if soft and num_beams != 1:
-        raise ValueError("--soft_decode reads the per-step distribution of sampled or greedy decoding: it needs num_beams == 1")
-    soft_sums, soft_dump = np.zeros(6), {}               # ADE_soft, FDE_soft, n_soft; sum and count of the stds; sum of the smallest masses
-    K = int(num_samples if num_samples is not None else (getattr(args, "num_samples", 1) or 1))
-    if K < 1:
-        raise ValueError(f"num_samples has to be a strictly positive integer, but is {K}")
-    if K > 1 and (num_beams != 1 or not bool(getattr(args, "val_sample", True))):
-        raise ValueError("num_samples > 1 draws samples: it cannot be combined with --val_greedy or --num_beams > 1")
-    select = str(select if select is not None else (getattr(args, "select", "none") or "none"))
-    if select not in ("none", "logprob", "medoid"):
-        raise ValueError(f"select must be none, logprob or medoid, not {select!r}")
-    if select != "none" and K < 2:
-        raise ValueError("--select chooses among samples: it needs --num_samples K > 1")
-    rescore = bool(getattr(args, "rescore", False))
-    if rescore and select != "logprob":
-        raise ValueError("--rescore re-ranks by log-prob: it needs --select logprob")
-    M = int(num_modes if num_modes is not None else (getattr(args, "num_modes", 0) or 0))
-    radius = float(mode_radius if mode_radius is not None else (getattr(args, "mode_radius", 0.0) or 0.0))
-    if M < 0 or (M > 0 and not (K > 1 and M <= K <= 64)):
-        raise ValueError(f"--num_modes M picks M of K samples: it needs --num_samples K > 1 and 1 <= M <= K <= 64, not M = {M}, K = {K}")
-    if radius != radius or radius < 0 or (radius > 0 and M == 0):
-        raise ValueError(f"--mode_radius is a distance >= 0 and needs --num_modes M > 0, not {radius} with M = {M}")
+    o = val_options(args, num_beams, num_samples, select, num_modes, mode_radius, soft_decode)
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
-    sample = bool(getattr(args, "val_sample", True))
-    sel_sums, picked = np.zeros(3), {}                   # ADE_sel, FDE_sel, n_sel
-    mode_sums, mode_dump = np.zeros(6), {}               # minADE_M, minFDE_M, brierADE_M, clips with a mode; modes, clips
-    per = micro_batch_per_rank(args.bs, 1, world)
+    sums = dict.fromkeys(BASE_SUMS + BEST_SUMS + SEL_SUMS + MODE_SUMS + SOFT_SUMS, 0.0)
+    dump, picked, mode_dump, soft_dump = {}, {}, {}, {}
     model.eval()
-    sums = np.zeros(8)                                   # ADE, FDE, ADE_as_called, GD, n; best-of-K: minADE, minFDE, n_min
-    dump = {}
-    # the reference's val / test DataLoader (train.py:79-82, evaluate.py:93-100: batch_size=bs, shuffle=False, NO drop_last) keeps the
-    # short last batch: every sample is generated for and lands in the dump.  A batch is dealt over the ranks; the short one is split
-    # raggedly and a rank whose share is empty skips it (the only collective of this pass is the all-reduce of the sums below)
-    gb = per * world
-    nb = -(-len(data) // gb)
-    for bi in range(nb if max_batches is None else min(nb, max_batches)):
-        n_here = min(gb, len(data) - bi * gb)
-        lo, hi = shard_range(gb, rank, world) if n_here == gb else ragged_shard_range(n_here, rank, world)
-        idx = list(range(bi * gb + lo, bi * gb + hi))
-        if not idx:
-            continue
-        batch = data.batch(idx, device, args.max_traj_token)
-        prompts, tokens = batch["prompts"], batch["tokens"]
-        max_new = tokens.shape[1] - prompts.shape[1]
-        beam = {} if num_beams == 1 else {"num_beams": num_beams, "kv_cache_layout": getattr(args, "kv_cache_layout", None)}
-        if K > 1:
-            beam = {"num_return_sequences": K, "share_prompt": True}
-            if select == "logprob":
-                beam["output_logprobs"] = True
-        if soft:
-            beam.update(output_bin_stats=True, bin_token_ids=(dims.tok.p0, dims.tok.num_bins))
-        out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"], max_length=max_new,
-                             do_sample=sample, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device),
-                             kv_cache_dtype=getattr(args, "kv_cache_dtype", None),
-                             decode_weight_dtype=getattr(args, "decode_weight_dtype", None), **beam)
-        all_ids = out.sequences[:, prompts.shape[1]:]
-        gen_ids = all_ids[::K]                                                  # sample 0 of every clip (K = 1: every row)
-        # the prompt holds the first step; prepend its six tokens + <tsep> so step 0 is parsed like the rest
-        vals, n = T.detokenize_batch(torch.cat([prompts[:, -7:], gen_ids], 1), dims.tok, args.num_steps + 4)
-        gt = batch["trajectories"]
-        Tn = gt.shape[1]
-        n = torch.clamp(n, max=Tn)
-        vals_h, n_h = vals[:, :Tn].cpu().numpy(), n.cpu().numpy()
-        for j in range(len(idx)):                                           # pad with the last parsed step (train.py:252-256)
-            if 0 < n_h[j] < Tn:
-                vals_h[j, n_h[j]:] = vals_h[j, n_h[j] - 1]
-        gen = norm.denorm(vals_h, batch["max_abs"].cpu().numpy())
-        gen_d = torch.from_numpy(np.ascontiguousarray(gen, dtype=np.float32)).to(device)
-        ade, fde = T.metrics_batch(gen_d, None, gt)
-        ade, fde, gt_h = ade.cpu().numpy(), fde.cpu().numpy(), gt.cpu().numpy()
-        ids_h = batch["image_ids"].cpu().numpy()
-        for j in range(len(idx)):
-            if n_h[j] <= 0:
-                continue                                                     # detokenize_traj returned None (train.py:249-250)
-            sums[:5] += [ade[j], fde[j], T.average_displacement_error(gen[j][None], gt_h[j][None]),
-                     T.anglar_distance(gen[j][:, 3:6].astype(np.float64), gt_h[j][:, 3:6].astype(np.float64)), 1.0]
-            dump[int(ids_h[j])] = gen[j].tolist()                            # evaluate.py:150: keyed by image_id.item(), not by the dataset index
-        if soft:                                                             # sample 0 again, from the distributions its tokens were drawn from
-            head = prompts[:, -7:]                                           # the prompt's step: its bin centres, std 0, mass 1
-            isbin = (head >= dims.tok.p0) & (head < dims.tok.p0 + dims.tok.num_bins)
-            centre = T.bin_edges(dims.tok.num_bins, device)[(head - dims.tok.p0).clamp(0, dims.tok.num_bins - 1)].float()
-            zero = torch.zeros_like(centre)
-            smean, sstd, smass, sn = T.detokenize_soft(torch.cat([head, gen_ids], 1), dims.tok, args.num_steps + 4,
-                                                       torch.cat([torch.where(isbin, centre, zero), out.bin_mean[::K]], 1),
-                                                       torch.cat([zero, out.bin_std[::K]], 1), torch.cat([zero + 1, out.bin_mass[::K]], 1))
-            sn_h = torch.clamp(sn, max=Tn).cpu().numpy()
-            smean_h, sstd_h, smass_h = smean[:, :Tn].cpu().numpy(), sstd[:, :Tn].cpu().numpy(), smass[:, :Tn].cpu().numpy()
-            for j in range(len(idx)):
-                if 0 < sn_h[j] < Tn:
-                    smean_h[j, sn_h[j]:], sstd_h[j, sn_h[j]:] = smean_h[j, sn_h[j] - 1], sstd_h[j, sn_h[j] - 1]
-            mabs = batch["max_abs"].cpu().numpy()
-            sgen = norm.denorm(smean_h, mabs)
-            sstd_h = sstd_h * norm.denorm_scale(mabs)[:, None, :]
-            sade, sfde = T.metrics_batch(torch.from_numpy(np.ascontiguousarray(sgen, dtype=np.float32)).to(device), None, gt)
-            sade, sfde = sade.cpu().numpy(), sfde.cpu().numpy()
-            for j in range(len(idx)):
-                if sn_h[j] <= 0:
-                    continue
-                soft_sums += [sade[j], sfde[j], 1.0, float(sstd_h[j, :sn_h[j], :3].sum()), 3.0 * sn_h[j], float(smass_h[j, :sn_h[j]].min())]
-                soft_dump[int(ids_h[j])] = {"mean": sgen[j].tolist(), "std": sstd_h[j].tolist()}
-        if K > 1:                                                            # all K samples of every clip: rows b * K + j
-            vals, n = T.detokenize_batch(torch.cat([prompts[:, -7:].repeat_interleave(K, 0), all_ids], 1), dims.tok, args.num_steps + 4)
-            n = torch.clamp(n, max=Tn)
-            vals_h, n_h = vals[:, :Tn].cpu().numpy(), n.cpu().numpy()
-            for r in range(len(idx) * K):
-                if 0 < n_h[r] < Tn:
-                    vals_h[r, n_h[r]:] = vals_h[r, n_h[r] - 1]
-            gen = norm.denorm(vals_h, np.repeat(batch["max_abs"].cpu().numpy(), K, axis=0))
-            gen_d = torch.from_numpy(np.ascontiguousarray(gen, dtype=np.float32)).to(device)
-            made, mfde, best = T.metrics_best_of(gen_d.view(len(idx), K, Tn, -1), (n > 0).to(torch.int32).view(len(idx), K) * Tn, gt)
-            made, mfde, best = made.cpu().numpy(), mfde.cpu().numpy(), best.cpu().numpy()
-            for j in range(len(idx)):
-                if best[j] >= 0:
-                    sums[5:8] += [made[j], mfde[j], 1.0]
-                dump[int(ids_h[j])] = [gen[j * K + i].tolist() if n_h[j * K + i] > 0 else None for i in range(K)]
-            if select != "none" or M:
-                gen_k, n_k = gen_d.view(len(idx), K, Tn, -1), (n > 0).to(torch.int32).view(len(idx), K) * Tn
-                ranked = None
-                if select == "logprob" and rescore:                          # the same samples, ranked on the model's own weights
-                    ranked = model.score(prompts, batch["prompt_masks"], batch["pcrgbs"], all_ids.reshape(len(idx), K, -1),
-                                         fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device))
-                elif select == "logprob":
-                    ranked = out
-            if select != "none":
-                pick = ranked.rank[:, 0].contiguous() if select == "logprob" else T.select_medoid(gen_k, n_k)[0]
-                sade, sfde = T.metrics_selected(gen_k, n_k, gt, None, pick)
-                sade, sfde, pick = sade.cpu().numpy(), sfde.cpu().numpy(), pick.cpu().numpy()
-                for j in range(len(idx)):
-                    picked[int(ids_h[j])] = int(pick[j])
-                    if not np.isnan(sade[j]):
-                        sel_sums += [sade[j], sfde[j], 1.0]
-            if M:                                                            # M different ones of the K, ordered by the scores or by centrality
-                md, cf, _, nmd, _ = T.select_modes(gen_k, n_k, None if ranked is None else ranked.sample_scores, M, radius)
-                oade, ofde, slot, brier = (t.cpu().numpy() for t in T.metrics_modes(gen_k, n_k, gt, None, md, cf))
-                md, cf, nmd = md.cpu().numpy(), cf.cpu().numpy(), nmd.cpu().numpy()
-                for j in range(len(idx)):
-                    mode_dump[int(ids_h[j])] = {"index": md[j, :nmd[j]].tolist(), "conf": cf[j, :nmd[j]].tolist()}
-                    mode_sums[4:] += [float(nmd[j]), 1.0]
-                    if slot[j] >= 0:
-                        mode_sums[:4] += [oade[j], ofde[j], brier[j], 1.0]
+    for idx in rank_batches(len(data), micro_batch_per_rank(args.bs, 1, world), rank, world, max_batches):
+        b = generate_batch(model, data, args, device, o, idx, norm)
+        base_batch(o, b, sums, dump)
+        if o.soft:
+            soft_batch(o, b, model.dims.tok, args.num_steps, norm, sums, soft_dump)
+        if o.K > 1:
+            best_of_batch(o, b, sums, dump)
+        ranked = sample_ranking(model, o, b)
+        if o.select != "none":
+            select_batch(o, b, ranked, sums, picked)
+        if o.M:
+            modes_batch(o, b, ranked, sums, mode_dump)
     if world > 1:
-        t = torch.from_numpy(np.concatenate([sums, sel_sums, mode_sums, soft_sums])).to(device)
-        dist.all_reduce(t)
-        sums, sel_sums, mode_sums, soft_sums = t.cpu().numpy()[:8], t.cpu().numpy()[8:11], t.cpu().numpy()[11:17], t.cpu().numpy()[17:]
+        sums = reduce_sums(sums, device)
     model.train()
-    k = max(sums[4], 1.0)
-    nan = float("nan")
-    mean = lambda i: float(sums[i] / k) if sums[4] else nan            # plain floats: the records go into checkpoints read with weights_only=True
-    rec = {"ADE": mean(0), "FDE": mean(1), "ADE_as_called": mean(2), "GD": mean(3), "n": int(sums[4])}
-    if K > 1:
-        rec.update({"minADE": float(sums[5] / sums[7]) if sums[7] else nan, "minFDE": float(sums[6] / sums[7]) if sums[7] else nan,
-                    "n_min": int(sums[7]), "K": K})
-    if select != "none":
-        rec.update({"ADE_sel": float(sel_sums[0] / sel_sums[2]) if sel_sums[2] else nan,
-                    "FDE_sel": float(sel_sums[1] / sel_sums[2]) if sel_sums[2] else nan, "n_sel": int(sel_sums[2]), "select": select})
+    rec = base_record(o, sums)
+    if o.K > 1:
+        rec.update(best_of_record(o, sums))
+    if o.select != "none":
+        rec.update(select_record(o, sums))
         dump["selected"] = picked
-    if M:
-        rec.update({"minADE_M": float(mode_sums[0] / mode_sums[3]) if mode_sums[3] else nan,
-                    "minFDE_M": float(mode_sums[1] / mode_sums[3]) if mode_sums[3] else nan,
-                    "brierADE_M": float(mode_sums[2] / mode_sums[3]) if mode_sums[3] else nan,
-                    "n_modes": float(mode_sums[4] / mode_sums[5]) if mode_sums[5] else nan, "M": M, "mode_radius": radius})
+    if o.M:
+        rec.update(modes_record(o, sums))
         dump["modes"] = mode_dump
-    if soft:
-        ns = soft_sums[2]
-        rec.update({"ADE_soft": float(soft_sums[0] / ns) if ns else nan, "FDE_soft": float(soft_sums[1] / ns) if ns else nan, "n_soft": int(ns),
-                    "sigma_mean": float(soft_sums[3] / soft_sums[4]) if soft_sums[4] else nan,
-                    "bin_mass_min": float(soft_sums[5] / ns) if ns else nan})
+    if o.soft:
+        rec.update(soft_record(o, sums))
         dump["soft"] = soft_dump
     return rec, dump
 
@@ -475,6 +559,17 @@ def check_adapter_keys(model, sd, path):
                      f"{','.join(model.lora_cfg.targets)} (first difference: {diff[0]})")
 
 
+def merge_dumps(parts):
+    """One dump of the ranks' dumps, in rank order: a top-level value that is a dict is a per-image-id sub-dump (--select / --num_modes /
+    --soft_decode) and is merged with the other ranks' of its key; anything else is a trajectory entry.  Trajectories come first."""
+    dump = {k: v for p in parts for k, v in p.items() if not isinstance(v, dict)}
+    for p in parts:
+        for key, sub in p.items():
+            if isinstance(sub, dict):
+                dump.setdefault(key, {}).update(sub)
+    return dump
+
+
 def evaluate(args, model, data, split="test", device="cuda"):
     """evaluate.py:70-170: load best_model_ade.pt, generate on the split, dump {split}_gen_trajs.json
     ({image_id: [[x,y,z,rx,ry,rz], ...]}, evaluate.py:150,167-170); --do_standard statistics come from
@@ -493,10 +588,7 @@ def evaluate(args, model, data, split="test", device="cuda"):
     if world > 1:
         parts = [None] * world
         dist.all_gather_object(parts, dump)
-        dump = {k: v for p in parts for k, v in p.items() if k not in ("selected", "modes", "soft")}
-        for key in ("selected", "modes", "soft"):           # --select / --num_modes / --soft_decode: the ranks' entries, merged like the trajectories
-            if any(key in p for p in parts):
-                dump[key] = {k: v for p in parts for k, v in p.get(key, {}).items()}
+        dump = merge_dumps(parts)
     if rank == 0:
         with open(os.path.join(args.checkpoint_dir, f"{split}_gen_trajs.json"), "w") as f:
             json.dump(dump, f)
@@ -571,14 +663,11 @@ def parse_args(argv=None):
                          "bins of the distribution its token was drawn from; adds ADE_soft / FDE_soft / n_soft, sigma_mean (mean std of x, y, z) "
                          "and bin_mass_min to the record and the soft trajectory with its std per image id to the dump")
     a = ap.parse_args(argv)
-    if a.soft_decode and a.num_beams != 1:
-        ap.error("--soft_decode reads the per-step distribution of sampled or greedy decoding: it needs --num_beams 1")
-    if a.num_modes != 0 and not (a.num_samples > 1 and 1 <= a.num_modes <= a.num_samples <= 64):
-        ap.error("--num_modes M picks M of K sampled trajectories: it needs --num_samples K > 1 and 1 <= M <= K <= 64")
-    if a.mode_radius != a.mode_radius or a.mode_radius < 0 or (a.mode_radius > 0 and a.num_modes == 0):
-        ap.error("--mode_radius is a distance >= 0 and needs --num_modes M > 0")
-    if a.rescore and not (a.num_samples > 1 and a.select == "logprob"):
-        ap.error("--rescore re-ranks sampled trajectories by log-prob: it needs --num_samples K > 1 and --select logprob")
+    try:
+        check_val_options(int(a.num_samples or 1), a.num_beams, a.val_sample, a.select, a.rescore, a.num_modes, a.mode_radius, a.soft_decode,
+                          decoding_rules=False)
+    except ValueError as e:
+        ap.error(str(e))
     return a
 
 

@@ -209,6 +209,24 @@ class _LogitsFn(torch.autograd.Function):
         return (torch.zeros_like(model._anchor), None, None, None, None, None, None)
 
 
+def _fill_logprobs(out, dec, cols, rank, rank_length_penalty):
+    """The log-prob fields of a GenerateOutput from the decoder's static buffers, as copies: token_logprobs [rows, cols], sequences_logprobs
+    and sequences_lengths [rows]; rank = (B, K): also sample_scores and rank [B, K] (egomi_seq_rank); None: they stay None."""
+    out.token_logprobs = dec.lp_tok[:, :cols].clone()
+    out.sequences_logprobs, out.sequences_lengths = dec.lp_sum.clone(), dec.lp_n.clone()
+    if rank is not None:
+        from ..decode import seq_rank
+        out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, *rank, float(rank_length_penalty))
+
+
+def _fill_bin_stats(out, dec, cols, past=None, shape=None):
+    """The four bin_* fields of a GenerateOutput from the decoder's static buffers, as copies of their first `cols` columns: [rows, cols],
+    zero where the bool mask `past` [rows, cols] is set; shape: reshaped to it."""
+    for field, buf in (("bin_mass", dec.bs_mass), ("bin_mean", dec.bs_mean), ("bin_std", dec.bs_std), ("bin_entropy", dec.bs_ent)):
+        t = buf[:, :cols].clone() if past is None else buf[:, :cols].masked_fill(past, 0.0)
+        setattr(out, field, t if shape is None else t.reshape(shape))
+
+
 class TrajPointLLMForCausalLM(nn.Module):
     def __init__(self, args, config, model_name: Optional[str] = None, device=None, dtype=torch.float32):
         super().__init__()
@@ -681,12 +699,8 @@ class TrajPointLLMForCausalLM(nn.Module):
         if decode_weight_dtype not in (None, "auto", "fp8", "int4"):
             raise ValueError(f"`decode_weight_dtype` must be None, 'auto', 'fp8' or 'int4', but is {decode_weight_dtype!r}")
         wd = decode_weight_dtype if decode_weight_dtype in ("fp8", "int4") else None
-        eng = self.engine
-        eng.wait_param_updates()                           # the decoder reads the weights outside the engine's forward pass
-        dev = eng.device
-        ids = input_ids.to(dev)
-        if fps_start is None and point_clouds is not None:
-            fps_start = torch.randint(0, point_clouds.shape[1], (ids.shape[0],), dtype=torch.long)
+        dev = self.engine.device
+        ids, fps_start = self._decode_inputs(input_ids, point_clouds, fps_start)
         n_ret = int(num_return_sequences)
         nb = int(num_beams)
         if nb < 1:
@@ -736,17 +750,22 @@ class TrajPointLLMForCausalLM(nn.Module):
         sc = sc[:stop].clone()                              # the decoder's buffers are static (and the decoder may be reused by the next call):
         out = GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
         if output_logprobs:
-            out.token_logprobs = dec.lp_tok[:, :stop].clone()
-            out.sequences_logprobs, out.sequences_lengths = dec.lp_sum.clone(), dec.lp_n.clone()
-            if n_ret > 1:
-                from ..decode import seq_rank
-                out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B // n_ret, n_ret, float(rank_length_penalty))
+            _fill_logprobs(out, dec, stop, (B // n_ret, n_ret) if n_ret > 1 else None, rank_length_penalty)
         if bins is not None:
             from ..decode import candidate_lengths
             past = torch.arange(stop, device=dev)[None, :] >= candidate_lengths(out.sequences[:, S0:], eos_token_id)[:, None]
-            out.bin_mass, out.bin_mean, out.bin_std, out.bin_entropy = (
-                buf[:, :stop].masked_fill(past, 0.0) for buf in (dec.bs_mass, dec.bs_mean, dec.bs_std, dec.bs_ent))
+            _fill_bin_stats(out, dec, stop, past=past)
         return out
+
+    def _decode_inputs(self, input_ids, point_clouds, fps_start):
+        """The start of generate() and score(): pending parameter updates are waited for (the decoder reads the weights outside the engine's
+        forward pass); -> (the ids on the device, fps_start or its default draw from torch's CPU generator, misc.py:52)."""
+        eng = self.engine
+        eng.wait_param_updates()
+        ids = input_ids.to(eng.device)
+        if fps_start is None and point_clouds is not None:
+            fps_start = torch.randint(0, point_clouds.shape[1], (ids.shape[0],), dtype=torch.long)
+        return ids, fps_start
 
     def _bin_window(self, bin_token_ids):
         from ..decode import bin_window
@@ -774,13 +793,12 @@ class TrajPointLLMForCausalLM(nn.Module):
         the logits every token is scored under, clip group by clip group; no [B*K*T, V] logits are kept); 0 at and after a candidate's eos.
         ValueError: K > 32, T < 1, candidates of another rank / dtype / batch, S0 + T beyond max_position_embeddings.
         NotImplementedError: a list of ragged clouds."""
-        from ..decode import Decoder, seq_rank
+        from ..decode import Decoder
         if isinstance(point_clouds, (list, tuple)):
             raise NotImplementedError("score() with a list of ragged clouds is not built")
-        ids = input_ids.to(self.engine.device)
         if not torch.is_tensor(candidates) or candidates.dim() != 3 or candidates.dtype != torch.int64:
             raise ValueError("score(): `candidates` must be an int64 tensor [B, K, T]")
-        B, S0 = ids.shape
+        B, S0 = input_ids.shape
         Bc, K, T = candidates.shape
         if Bc != B:
             raise ValueError(f"score(): {Bc} candidate sets for {B} prompts")
@@ -794,33 +812,17 @@ class TrajPointLLMForCausalLM(nn.Module):
         if isinstance(eos_token_id, str):
             eos_token_id = self.dims.tok.eos
         bins = self._bin_window(bin_token_ids) if output_bin_stats else None
-        eng = self.engine
-        eng.wait_param_updates()
-        if fps_start is None and point_clouds is not None:
-            fps_start = torch.randint(0, point_clouds.shape[1], (B,), dtype=torch.long)
-        if not eng.prepared:
-            eng.prepare()
-        # scorer decoders have a cache of their own (same key rule as _decoder's): generate()'s two cached decoders stay what they were
-        key = (id(eng), eng.prepare_epoch, B, K, S0, T, eng.lora_key())
-        cache = self.__dict__.setdefault("_scorers", {})
-        reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
-        dec = cache.get(key) if reuse else None
-        if dec is None:
-            dec = Decoder(eng, B * K, S0 + T, samples_per_prompt=K, max_new_tokens=T, score_cache=True)
-            if reuse:
-                while len(cache) >= 2:
-                    cache.pop(next(iter(cache)))
-                cache[key] = dec
+        ids, fps_start = self._decode_inputs(input_ids, point_clouds, fps_start)
+        # scorer decoders have a cache of their own (_cached_decoder's rule): generate()'s two cached decoders stay what they were
+        dec = self._cached_decoder("_scorers", (B, K, S0, T), lambda eng: Decoder(eng, B * K, S0 + T, samples_per_prompt=K, max_new_tokens=T,
+                                                                                   score_cache=True))
         self._prefill_prompts(dec, ids, attention_mask, point_clouds, fps_start, T)
-        cand = candidates.to(eng.device).reshape(B * K, T)
+        cand = candidates.to(ids.device).reshape(B * K, T)
         dec.score(cand, eos_token_id, row_budget=row_budget, bin_stats=bins)
         out = GenerateOutput(sequences=cand.clone(), scores=())
         if bins is not None:
-            out.bin_mass, out.bin_mean, out.bin_std, out.bin_entropy = (
-                buf[:, :T].reshape(B, K, T).clone() for buf in (dec.bs_mass, dec.bs_mean, dec.bs_std, dec.bs_ent))
-        out.token_logprobs = dec.lp_tok[:, :T].clone()
-        out.sequences_logprobs, out.sequences_lengths = dec.lp_sum.clone(), dec.lp_n.clone()
-        out.sample_scores, out.rank = seq_rank(out.sequences_logprobs, out.sequences_lengths, B, K, float(rank_length_penalty))
+            _fill_bin_stats(out, dec, T, shape=(B, K, T))
+        _fill_logprobs(out, dec, T, (B, K), rank_length_penalty)
         return out
 
     def _sampling_args(self, eos_token_id, pad_token_id, temperature, repetition_penalty, top_p):
@@ -839,9 +841,7 @@ class TrajPointLLMForCausalLM(nn.Module):
 
     def _prefill_prompts(self, dec, ids, attention_mask, point_clouds, fps_start, T, nb=1):
         """Prefill of a decoder whose prompts are fewer than its rows (beams, shared prompt): more than 16 prompts run chunked."""
-        if ids.shape[0] > 16:
-            return dec.prefill_chunked(ids, attention_mask, point_clouds, fps_start, T, chunk=16, nb=nb)
-        return dec.prefill(ids, attention_mask, point_clouds, fps_start, T, nb=nb)
+        return dec.prefill(ids, attention_mask, point_clouds, fps_start, T, nb=nb, chunk=16 if ids.shape[0] > 16 else None)
 
     def _decoder(self, B, max_len, nb=1, kv=None, wd=None, share=None, split=None):
         """The cached Decoder of this geometry.  The key holds the engine's identity and the epoch of its prepared weights, taken AFTER
@@ -850,26 +850,32 @@ class TrajPointLLMForCausalLM(nn.Module):
         stand in for each other.  share = (K, Tmax): the shared-prompt decoder of K samples per prompt; the key holds the mode and K.
         split = Tmax: the beam decoder on the prompt / suffix cache layout; the key holds the layout and Tmax."""
         from ..decode import Decoder
+        kw, layout = dict(kv_dtype=kv, weight_dtype=wd), ()
+        if share is not None:
+            kw.update(samples_per_prompt=share[0], max_new_tokens=share[1])
+            layout = ("share", *share)
+        elif split is not None:
+            kw.update(split_cache=True, max_new_tokens=split)
+            layout = ("split", split)
+        return self._cached_decoder("_decoders", (B, max_len, nb, kv, wd), lambda eng: Decoder(eng, B * nb, max_len, num_beams=nb, **kw), layout)
+
+    def _cached_decoder(self, attr, geometry, build, layout=()):
+        """The one rule of both decoder caches (self._decoders, self._scorers: plain dicts, made on first use, dropped by _build_engine):
+        prepare the engine FIRST, then key on its identity, the epoch of its prepared weights, `geometry`, the LoRA key (adapters: a decoder
+        holds merged copies of their values) and `layout`; reuse a decoder only while no decoder layer is trainable and EGOMI_DECODER_CACHE
+        is not "0", else build(engine) a fresh one every call and keep nothing; keep at most two per cache, the oldest goes first (the full
+        batch and the short last one; a KV cache is 2 * L * B * H * Smax * hd elements)."""
         eng = self.engine
         if not eng.prepared:
             eng.prepare()
-        key = (id(eng), eng.prepare_epoch, B, max_len, nb, kv, wd, eng.lora_key())     # adapters: merged decode copies of their values
-        if share is not None:
-            key = key + ("share",) + tuple(share)
-        if split is not None:
-            key = key + ("split", split)
-        cache = self.__dict__.setdefault("_decoders", {})
+        key = (id(eng), eng.prepare_epoch, *geometry, eng.lora_key(), *layout)
+        cache = self.__dict__.setdefault(attr, {})
         reuse = not eng.any_layer_trainable and os.environ.get("EGOMI_DECODER_CACHE", "1") != "0"
         dec = cache.get(key) if reuse else None
         if dec is None:
-            kw = dict(kv_dtype=kv, weight_dtype=wd)
-            if share is not None:
-                kw.update(samples_per_prompt=share[0], max_new_tokens=share[1])
-            elif split is not None:
-                kw.update(split_cache=True, max_new_tokens=split)
-            dec = Decoder(eng, B * nb, max_len, num_beams=nb, **kw)
+            dec = build(eng)
             if reuse:
-                while len(cache) >= 2:                     # the full batch and the split's short last one; a cache is 2 * L * B * H * Smax * hd elements
+                while len(cache) >= 2:
                     cache.pop(next(iter(cache)))
                 cache[key] = dec
         return dec

@@ -5,7 +5,8 @@ value, device pointers as [buffer name, byte offset] (named through the Decoder'
 and workspace), NULL as None, a descriptor passed by reference as the list of its fields.  A pointer into no named buffer is an error.
 Two decoders that record the same trace for a case issue the same launches in the same order with the same arguments: same results, same
 speed.  tests/golden/decode_launch_trace.json holds the trace of every case in CASES as recorded by tools/debug/record_decode_trace.py
-on the commit before Decoder's cache layouts became objects; tests/test_gpu_decode_trace.py replays the cases against it.
+on the commit before Decoder's cache layouts became objects (the two *_bs cases: on the commit before the per-step readouts of sample() /
+greedy() / score() were written once); tests/test_gpu_decode_trace.py replays the cases against it.
 
 Shapes: LLaMA-7B width (the slab-fused step needs it) with one decoder layer, 4 decoder rows (grouped modes: 2 prompts x 2), a text-only
 prompt of 24 tokens, 3 new tokens = two step() calls, eager (use_graph=False)."""
@@ -36,9 +37,12 @@ CASES = {
     "split_beam2_w8": ("bf16", dict(num_beams=2, split_cache=True, weight_dtype="fp8", **GROUP), "1", "beam", NO_QKV, False),
     "lora_greedy": ("lora", {}, "1", "greedy", ALL, False),
     "fp32_tiny_greedy": ("tiny", {}, "1", "greedy", NONE, False),
+    "sample_lp_bs": ("bf16", {}, "1", "sample_lp_bs", ALL, False),
+    "greedy_bs": ("bf16", {}, "1", "greedy_bs", ALL, False),
 }
 
-DECODER_BUFFERS = ("kc", "vc", "ks", "vs", "kp", "vp", "ksfx", "vsfx", "kv_row", "lp_tok", "lp_sum", "lp_n", "lp_live", "lg", "seq_buf", "mask_buf",
+DECODER_BUFFERS = ("kc", "vc", "ks", "vs", "kp", "vp", "ksfx", "vsfx", "kv_row", "lp_tok", "lp_sum", "lp_n", "lp_live", "bs_mass", "bs_mean", "bs_std",
+                   "bs_ent", "lg", "seq_buf", "mask_buf",
                    "x", "h", "qkv", "ao", "x_mid", "h2", "gu", "act", "hn", "tok", "gws", "rng", "done_buf", "fin_seq", "bidx", "fin_bidx",
                    "run_score", "fin_score", "fin_flag", "heur", "ctl")
 
@@ -85,6 +89,8 @@ def named_buffers(dec):
         out.append((n, getattr(dec, n, None)))
     for T_new, t in dec._scores.items():
         out.append((f"scores[{T_new}]", t))
+    for nb, t in dec._bs_values.items():
+        out.append((f"bs_values[{nb}]", t))
     for K, ts in getattr(dec, "_cands", {}).items():
         out += [(f"cands[{K}][{i}]", t) for i, t in enumerate(ts)]
     for name in ("wqkv", "wgu", "wo", "wdown"):
@@ -131,13 +137,14 @@ def run_case(models, name):
     with trace(PREFILL_ONLY) as rec:
         dec.prefill(ids, None, None, None, T, nb=nb)
     out["prefill"] = rec.resolved(named_buffers(dec))
+    bins = (tok.p0, tok.num_bins) if loop.endswith("_bs") else None
     with trace() as rec:
-        if loop == "greedy":
-            dec.greedy(T, use_graph=False)
+        if loop in ("greedy", "greedy_bs"):
+            dec.greedy(T, use_graph=False, bin_stats=bins)
         elif loop == "beam":
             dec.beam(T, eos=tok.eos, pad=tok.pad, use_graph=False)
         else:
-            dec.sample(T, eos=tok.eos, pad=tok.pad, seed=5, use_graph=False, logprobs=loop == "sample_lp")
+            dec.sample(T, eos=tok.eos, pad=tok.pad, seed=5, use_graph=False, logprobs=loop.startswith("sample_lp"), bin_stats=bins)
     out["loop"] = rec.resolved(named_buffers(dec))
     if chunked:
         with trace(PREFILL_ONLY) as rec:
