@@ -15,8 +15,9 @@ LIB = os.path.join(LIBDIR, "libegomi.so")
 ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-I", os.path.join(os.path.dirname(HERE), "include")]
-# per-file extras: the index-contract kernels must not fuse mul+add (bit-exact FPS / kNN indices)
-EXTRA = {"pointcloud.hip": ["-ffp-contract=off"]}
+# per-file extras: the index-contract kernels must not fuse mul+add (bit-exact FPS / kNN indices); the full metric suite spells its one
+# fused multiply-add out (csrc/traj_disp.h), so that its ADE / FDE bits are traj.hip's
+EXTRA = {"pointcloud.hip": ["-ffp-contract=off"], "traj_full.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -9,6 +9,7 @@
 //       K samples under the same displacement (metrics.py:38-55 between two samples instead of a sample and the ground truth)
 // The bin edges are computed once on the host in float64 exactly as numpy.linspace does and passed in.
 #include "common.h"
+#include "traj_disp.h"
 #include <math.h>
 
 // ids[b, :] = <ts> (p p p p p p <tsep>) x steps[b] <te> <eos> pad...   ; mask = 1 on non-pad
@@ -135,12 +136,7 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const float* gen, cons
     double acc = 0.0, lastd = 0.0;
     for (int t = 0; t < nt; ++t) {
         const int tg = t < ng ? t : ng - 1;
-        double s = 0.0;
-        for (int c = 0; c < D; ++c) {
-            const double df = (double)gt[((long long)b * Tmax + t) * D + c] - (double)gen[((long long)b * Tmax + tg) * D + c];
-            s += df * df;
-        }
-        lastd = sqrt(s);
+        lastd = traj_step_dist(gt + ((long long)b * Tmax + t) * D, gen + ((long long)b * Tmax + tg) * D, D);
         acc += lastd;
     }
     ade[b] = acc / nt;
@@ -163,12 +159,7 @@ __global__ __launch_bounds__(64) void traj_metrics_min_kernel(const float* gen, 
         double acc = 0.0, lastd = 0.0;
         for (int t = 0; t < nt; ++t) {
             const int tg = t < ng ? t : ng - 1;
-            double s = 0.0;
-            for (int c = 0; c < D; ++c) {
-                const double df = (double)gt[((long long)b * Tmax + t) * D + c] - (double)g[(long long)tg * D + c];
-                s += df * df;
-            }
-            lastd = sqrt(s);
+            lastd = traj_step_dist(gt + ((long long)b * Tmax + t) * D, g + (long long)tg * D, D);
             acc += lastd;
         }
         const double ade = acc / nt;

@@ -140,10 +140,11 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
     return max(1, -(-int(bs) // (max(1, int(grad_accum_steps)) * max(1, int(world)))))
 
 
-def check_val_options(K, num_beams, sample, select, rescore, M, radius, soft, decoding_rules=True):
+def check_val_options(K, num_beams, sample, select, rescore, M, radius, soft, decoding_rules=True, full=False):
     """The rules of --num_samples / --select / --rescore / --num_modes / --mode_radius / --soft_decode on their resolved values, one text
     per rule; raises ValueError.  run_validation applies all of them; parse_args applies the first four (decoding_rules=False) and exits
-    on them: the last four stay errors of the run itself (main() raises ValueError there, and tests pin that)."""
+    on them: the last four stay errors of the run itself (main() raises ValueError there, and tests pin that).  --full_metrics goes with
+    every decoding mode: `full` has no rule."""
     if soft and num_beams != 1:
         raise ValueError("--soft_decode reads the per-step distribution of sampled or greedy decoding: it needs num_beams == 1")
     if M < 0 or (M > 0 and not (K > 1 and M <= K <= 64)):
@@ -164,13 +165,13 @@ def check_val_options(K, num_beams, sample, select, rescore, M, radius, soft, de
         raise ValueError("--select chooses among samples: it needs --num_samples K > 1")
 
 
-def val_options(args, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None, soft_decode=None):
+def val_options(args, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None, soft_decode=None, full_metrics=None):
     """run_validation's options, each resolved as: the explicit keyword, else `args`, else its default; checked (check_val_options)."""
     pick = lambda explicit, name, default: explicit if explicit is not None else (getattr(args, name, default) or default)
     o = types.SimpleNamespace(K=int(pick(num_samples, "num_samples", 1)), num_beams=num_beams, sample=bool(getattr(args, "val_sample", True)),
                               select=str(pick(select, "select", "none")), rescore=bool(getattr(args, "rescore", False)),
                               M=int(pick(num_modes, "num_modes", 0)), radius=float(pick(mode_radius, "mode_radius", 0.0)),
-                              soft=bool(pick(soft_decode, "soft_decode", False)))
+                              soft=bool(pick(soft_decode, "soft_decode", False)), full=bool(pick(full_metrics, "full_metrics", False)))
     check_val_options(**vars(o))
     return o
 
@@ -181,6 +182,7 @@ BEST_SUMS = ("minADE", "minFDE", "n_min")
 SEL_SUMS = ("ADE_sel", "FDE_sel", "n_sel")
 MODE_SUMS = ("minADE_M", "minFDE_M", "brierADE_M", "n_M", "modes", "clips_M")      # n_M: clips with a mode; modes over clips_M clips
 SOFT_SUMS = ("ADE_soft", "FDE_soft", "n_soft", "std", "n_std", "mass_min")        # std over n_std coordinates; the smallest masses
+FULL_SUMS = ("IDE", "DTW", "GD_dev", "n_full", "minIDE", "minGD", "minDTW", "n_fmin", "GD_sel", "DTW_sel", "n_fsel", "minGD_M", "minDTW_M", "n_fM")
 
 
 def _add(sums, **terms):
@@ -348,6 +350,42 @@ def soft_record(o, sums):
             "sigma_mean": _mean(sums, "std", "n_std"), "bin_mass_min": _mean(sums, "mass_min", "n_soft")}
 
 
+def full_batch(o, b, sums, full_dump, picked, mode_dump):
+    """All K samples of every clip once more, through the whole metric module (T.metrics_full, one launch): IDE / DTW / GD of sample 0, the
+    per-clip minima, and the values at the pick (picked) and over the modes (mode_dump) that select_batch / modes_batch left for the clip.
+    The rows carry their parsed step counts, 0 for an unparsed one: they are padded with their last step already, which ADE, FDE and GD
+    would repeat anyway and DTW must not see."""
+    n = torch.from_numpy(np.ascontiguousarray(b.n_h, dtype=np.int32)).to(b.gen_k.device).view(len(b.ids_h), o.K)
+    m = T.metrics_full(b.gen_k, n, b.gt)
+    vals = np.stack([t.cpu().numpy() for t in m[:len(T.FULL_METRICS)]], axis=-1)          # [clips, K, 5]
+    mins, args = m.mins.cpu().numpy(), m.args.cpu().numpy()
+    IDE, GD, DTW = (T.FULL_METRICS.index(c) for c in ("IDE", "GD", "DTW"))
+    for j in range(len(b.ids_h)):
+        iid = int(b.ids_h[j])
+        full_dump[iid] = {name: [None if np.isnan(v) else float(v) for v in vals[j, :, c]] for c, name in enumerate(T.FULL_METRICS)}
+        if b.n_h[j * o.K] > 0:
+            _add(sums, IDE=vals[j, 0, IDE], DTW=vals[j, 0, DTW], GD_dev=vals[j, 0, GD], n_full=1)
+        if o.K > 1 and args[j, 0] >= 0:
+            _add(sums, minIDE=mins[j, IDE], minGD=mins[j, GD], minDTW=mins[j, DTW], n_fmin=1)
+        if o.select != "none" and picked[iid] >= 0 and b.n_h[j * o.K + picked[iid]] > 0:
+            _add(sums, GD_sel=vals[j, picked[iid], GD], DTW_sel=vals[j, picked[iid], DTW], n_fsel=1)
+        if o.M and mode_dump[iid]["index"]:
+            rows = vals[j, mode_dump[iid]["index"]]
+            _add(sums, minGD_M=rows[:, GD].min(), minDTW_M=rows[:, DTW].min(), n_fM=1)
+
+
+def full_record(o, sums):
+    rec = {"IDE": _mean(sums, "IDE", "n_full"), "DTW": _mean(sums, "DTW", "n_full"), "GD_dev": _mean(sums, "GD_dev", "n_full"),
+           "n_full": int(sums["n_full"])}
+    if o.K > 1:
+        rec.update({"min" + c: _mean(sums, "min" + c, "n_fmin") for c in ("IDE", "GD", "DTW")})
+    if o.select != "none":
+        rec.update(GD_sel=_mean(sums, "GD_sel", "n_fsel"), DTW_sel=_mean(sums, "DTW_sel", "n_fsel"))
+    if o.M:
+        rec.update(minGD_M=_mean(sums, "minGD_M", "n_fM"), minDTW_M=_mean(sums, "minDTW_M", "n_fM"))
+    return rec
+
+
 def rank_batches(n, per, rank, world, max_batches=None):
     """The clips of this rank, batch by batch.  The reference's val / test DataLoader (train.py:79-82, evaluate.py:93-100: batch_size=bs,
     shuffle=False, NO drop_last) keeps the short last batch: every sample is generated for and lands in the dump.  A batch is dealt over
@@ -364,7 +402,7 @@ def rank_batches(n, per, rank, world, max_batches=None):
 
 @torch.no_grad()
 def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None,
-                   soft_decode=None):
+                   soft_decode=None, full_metrics=None):
     """Generation + metrics on the rank's shard (train.py:207-264, evaluate.py:104-154): prompts up to the first <tsep>,
     `generate` of the remaining positions (sampling with the reference's defaults top_k 50 / top_p 0.95 / T 1.0 unless
     args.val_sample is False -> greedy), cut at eos, de-tokenise, de-normalise (dataset.denorm), pad with the last step,
@@ -403,12 +441,20 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     through the same norm.denorm; the std is scaled by |its linear factor| (TargetNorm.denorm_scale: denorm is affine per dimension in every
     mode).  The record gains 'ADE_soft' / 'FDE_soft' / 'n_soft' (T.metrics_batch, means over the parsed rows exactly as 'ADE' / 'FDE' / 'n'),
     'sigma_mean' (the mean std over the parsed waypoints' x, y, z, in denorm's units) and 'bin_mass_min' (the mean over the parsed clips of
-    the smallest per-step bin mass); the dump gains one key, "soft": {image id: {"mean": [[6] per step], "std": [[6] per step]}}."""
-    o = val_options(args, num_beams, num_samples, select, num_modes, mode_radius, soft_decode)
+    the smallest per-step bin mass); the dump gains one key, "soft": {image id: {"mean": [[6] per step], "std": [[6] per step]}}.
+
+    full_metrics (default: args.full_metrics, else False; every decoding mode): the reference's whole metric module for all K samples of
+    every clip in one launch per batch (T.metrics_full on the parsed step counts; DTW sees no padding).  The record gains 'IDE' / 'DTW' /
+    'GD_dev' / 'n_full' (sample 0, means over the parsed rows as 'ADE' / 'n'; 'GD_dev' is the device's value of the host-computed 'GD',
+    which stays), with K > 1 'minIDE' / 'minGD' / 'minDTW' (means over the clips with a parsed sample), with select 'GD_sel' / 'DTW_sel'
+    (the pick's values) and with num_modes 'minGD_M' / 'minDTW_M' (minima over the chosen samples); the dump gains one key,
+    "full": {image id: {"ADE": [K values], "FDE": ..., "IDE": ..., "GD": ..., "DTW": ...}} with None for an unparsed sample.  Off, the
+    record and the dump are what they are without it."""
+    o = val_options(args, num_beams, num_samples, select, num_modes, mode_radius, soft_decode, full_metrics)
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
-    sums = dict.fromkeys(BASE_SUMS + BEST_SUMS + SEL_SUMS + MODE_SUMS + SOFT_SUMS, 0.0)
-    dump, picked, mode_dump, soft_dump = {}, {}, {}, {}
+    sums = dict.fromkeys(BASE_SUMS + BEST_SUMS + SEL_SUMS + MODE_SUMS + SOFT_SUMS + FULL_SUMS, 0.0)
+    dump, picked, mode_dump, soft_dump, full_dump = {}, {}, {}, {}, {}
     model.eval()
     for idx in rank_batches(len(data), micro_batch_per_rank(args.bs, 1, world), rank, world, max_batches):
         b = generate_batch(model, data, args, device, o, idx, norm)
@@ -422,6 +468,8 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
             select_batch(o, b, ranked, sums, picked)
         if o.M:
             modes_batch(o, b, ranked, sums, mode_dump)
+        if o.full:
+            full_batch(o, b, sums, full_dump, picked, mode_dump)
     if world > 1:
         sums = reduce_sums(sums, device)
     model.train()
@@ -437,6 +485,9 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     if o.soft:
         rec.update(soft_record(o, sums))
         dump["soft"] = soft_dump
+    if o.full:
+        rec.update(full_record(o, sums))
+        dump["full"] = full_dump
     return rec, dump
 
 
@@ -561,7 +612,8 @@ def check_adapter_keys(model, sd, path):
 
 def merge_dumps(parts):
     """One dump of the ranks' dumps, in rank order: a top-level value that is a dict is a per-image-id sub-dump (--select / --num_modes /
-    --soft_decode) and is merged with the other ranks' of its key; anything else is a trajectory entry.  Trajectories come first."""
+    --soft_decode / --full_metrics) and is merged with the other ranks' of its key; anything else is a trajectory entry.  Trajectories come
+    first."""
     dump = {k: v for p in parts for k, v in p.items() if not isinstance(v, dict)}
     for p in parts:
         for key, sub in p.items():
@@ -662,6 +714,11 @@ def parse_args(argv=None):
                     help="validation / eval with --num_beams 1: also decode sample 0 of every clip softly, every coordinate as the mean over the "
                          "bins of the distribution its token was drawn from; adds ADE_soft / FDE_soft / n_soft, sigma_mean (mean std of x, y, z) "
                          "and bin_mass_min to the record and the soft trajectory with its std per image id to the dump")
+    ap.add_argument("--full_metrics", action="store_true",
+                    help="validation / eval, every decoding mode: all five measures of the reference's metric module (ADE, FDE, IDE, GD, DTW) "
+                         "for every sample on the device, one launch per batch; adds IDE / DTW / GD_dev / n_full (with --num_samples K > 1 "
+                         "minIDE / minGD / minDTW, with --select GD_sel / DTW_sel, with --num_modes minGD_M / minDTW_M) to the record and the "
+                         "per-sample values per image id to the dump")
     a = ap.parse_args(argv)
     try:
         check_val_options(int(a.num_samples or 1), a.num_beams, a.val_sample, a.select, a.rescore, a.num_modes, a.mode_radius, a.soft_decode,

@@ -9,6 +9,7 @@ Two layers, mirroring where the reference does this work:
     (utils.py, models/utils/traj_utils.py, models/utils/metrics.py), numpy like the reference.
 Nothing here imports oracle/.
 """
+import collections
 import re
 
 import numpy as np
@@ -119,6 +120,47 @@ def metrics_best_of(gen, n_gen, gt, n_gt=None):
     nt = None if n_gt is None else n_gt.to(torch.int32).contiguous()
     call("egomi_traj_metrics_min", gen, ng, gt, nt, B, K, T, D, min_ade, min_fde, best, S())
     return min_ade, min_fde, best
+
+
+FULL_METRICS = ("ADE", "FDE", "IDE", "GD", "DTW")                              # the columns of metrics_full's mins / args
+FULL_MAX_STEPS = 256
+FullMetrics = collections.namedtuple("FullMetrics", ("ade", "fde", "ide", "gd", "dtw", "mins", "args"))
+
+
+def metrics_full(gen, n_gen, gt, n_gt=None, rot0=3):
+    """All five measures of the reference's metric module per sample, on the device in one launch (egomi_traj_metrics_full):
+    gen [B, K, T, D] (or [B, T, D] for K = 1), n_gen [B, K] ([B]) or None, gt [B, T, D], n_gt [B] or None, T <= 256 ->
+    FullMetrics(ade, fde, ide, gd, dtw, mins, args): the first five float64 and shaped like gen's leading dimensions (views of the one
+    [B, K, 5] result), mins float64 [B, 5] and args int32 [B, 5] the per-clip minimum of every column over the samples whose value is not
+    NaN and that sample's index (lowest index on ties; NaN and -1 when there is none), columns in the order of FULL_METRICS.
+    ade / fde are metrics_batch's, bit for bit, and mins[:, :2], args[:, 0] metrics_best_of's.  ide = ||gt[0] - gen[0]||; gd = the
+    reference's angular distance on the rotation vectors in columns rot0 .. rot0 + 2 of the padded rows (NaN everywhere when they do not
+    exist: rot0 = -1 with gen[..., :3]); dtw = dynamic_time_warping on gen[:n_gen] and gt[:n_gt], which sees no padding: pass the parsed
+    step counts.  A sample with n_gen <= 0 (or a clip with n_gt <= 0) is NaN in all five."""
+    gen, gt = gen.to(torch.float32).contiguous(), gt.to(torch.float32).contiguous()
+    B, T, D = gt.shape
+    single = gen.dim() == 3
+    if single:
+        gen = gen[:, None]
+        n_gen = None if n_gen is None else n_gen.reshape(-1, 1)
+    if gen.dim() != 4 or gen.shape[0] != B or tuple(gen.shape[2:]) != (T, D):
+        raise ValueError("gen must be [B,K,T,D] for gt [B,T,D]")
+    K = gen.shape[1]
+    if K < 1:
+        raise ValueError("gen holds no sample")
+    if n_gen is not None and tuple(n_gen.shape) != (B, K):
+        raise ValueError("n_gen must be [B,K]")
+    if T > FULL_MAX_STEPS:
+        raise ValueError(f"metrics_full serves T <= {FULL_MAX_STEPS} steps, not {T}")
+    dev = gt.device
+    out = torch.empty(B, K, len(FULL_METRICS), dtype=torch.float64, device=dev)
+    mins = torch.empty(B, len(FULL_METRICS), dtype=torch.float64, device=dev)
+    args = torch.empty(B, len(FULL_METRICS), dtype=torch.int32, device=dev)
+    ng = None if n_gen is None else n_gen.to(device=dev, dtype=torch.int32).contiguous()
+    nt = None if n_gt is None else n_gt.to(device=dev, dtype=torch.int32).contiguous()
+    call("egomi_traj_metrics_full", gen, ng, gt, nt, B, K, T, D, int(rot0), out, mins, args, S())
+    cols = out[:, 0] if single else out
+    return FullMetrics(*(cols[..., m] for m in range(len(FULL_METRICS))), mins, args)
 
 
 def select_medoid(gen, n_gen=None):
@@ -349,6 +391,28 @@ def final_displacement_error(gen_traj, gt_traj) -> float:
 def initial_displacement_error(gen_traj, gt_traj) -> float:
     """models/utils/metrics.py:29-36."""
     return np.linalg.norm(gt_traj[0] - gen_traj[0], ord=2)
+
+
+def dynamic_time_warping(gen_traj, gt_traj) -> float:
+    """models/utils/metrics.py:57-59 as the exact dynamic programme, float64: gen_traj [n, D] and gt_traj [m, D] as they are (no padding,
+    no cut), local cost c(i, k) = ||gen_i - gt_k||_2 over all D dims, Dp(i, k) = c(i, k) + min(Dp(i-1, k), Dp(i, k-1), Dp(i-1, k-1)),
+    Dp(0, 0) = c(0, 0); the value is Dp(n-1, m-1), not normalised by the path length.
+    Relation to the reference, which calls fastdtw(gen, gt, dist=euclidean)[0] at its default radius=1: fastdtw is exact when either
+    sequence has fewer than radius + 2 = 3 steps (it then runs this very programme); on longer sequences it searches a window of the same
+    table, so its value is an upper bound of this one.  fastdtw is not installed beside this package: how far the two lie apart on longer
+    sequences is NOT measured."""
+    x, y = np.asarray(gen_traj, dtype=np.float64), np.asarray(gt_traj, dtype=np.float64)
+    n, m = len(x), len(y)
+    cost = np.sqrt(((x[:, None, :] - y[None, :, :]) ** 2).sum(-1))
+    dp = np.full((n, m), np.inf)
+    for i in range(n):
+        for k in range(m):
+            if i == 0 and k == 0:
+                dp[i, k] = cost[i, k]
+                continue
+            best = min(dp[i - 1, k] if i else np.inf, dp[i, k - 1] if k else np.inf, dp[i - 1, k - 1] if i and k else np.inf)
+            dp[i, k] = cost[i, k] + best
+    return float(dp[n - 1, m - 1])
 
 
 def anglar_distance(gen_rot, gt_rot) -> float:

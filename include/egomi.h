@@ -569,6 +569,27 @@ int egomi_traj_medoid(const float* gen, const int32_t* n_gen, int B, int K, int 
 int egomi_traj_modes(const float* gen, const int32_t* n_gen, const float* score, int B, int K, int Tmax, int D, int M, double radius,
                      double* dist, int32_t* modes, double* conf, int32_t* assign, int32_t* n_modes, int32_t* n_nms,
                      egomi_stream_t stream);
+/* metrics_full: the five measures of models/utils/metrics.py per sample, one launch (csrc/traj_full.hip).  gen f32 [B,K,Tmax,D], n_gen i32 [B,K]
+ *              (NULL = Tmax), gt f32 [B,Tmax,D], n_gt i32 [B] (NULL = Tmax); lengths above Tmax count as Tmax; nothing of a row beyond its
+ *              length is read.  out float64 [B,K,5] = ADE, FDE, IDE, GD, DTW; all five NaN when n_gen <= 0 or n_gt <= 0.
+ *   ADE, FDE   `metrics` on the same row, bit for bit (gen padded with its last step / cut to n_gt).
+ *   IDE        ||gt[0] - gen[0]||_2 over all D dims (metrics.py:29-36).
+ *   GD         metrics.py:61-87 on columns rot0 .. rot0+2 as rotation vectors, gen padded / cut as for ADE: the sum over t < n_gt, in index
+ *              order, of 2 acos(clip(<q(gen_t), q(gt_t)>, -1, 1)), divided by n_gt; q(r) = (s r, cos(|r|/2)), s = sin(|r|/2) / |r| for
+ *              |r| > 1e-3, else 0.5 - |r|^2/48 + |r|^4/3840 (scipy's from_rotvec).  The dot product is used as it is, not its absolute
+ *              value.  rot0 < 0 or rot0 + 3 > D: NaN for every row (position-only input).
+ *   DTW        metrics.py:57-59 as the exact dynamic programme on x = gen[:n_gen], y = gt[:n_gt], no padding and no cut: c(i,k) =
+ *              ||x_i - y_k||_2 over all D dims, Dp(i,k) = c(i,k) + min(Dp(i-1,k), Dp(i,k-1), Dp(i-1,k-1)), Dp(0,0) = c(0,0); the value is
+ *              Dp(n_gen-1, n_gt-1), not normalised by the path length.  (The reference calls fastdtw(radius=1): exact while either
+ *              sequence has fewer than 3 steps, otherwise an upper bound of this value.)
+ *   mins, args float64 / i32 [B,5], NULL together: per column the minimum over the clip's samples whose value is not NaN and that sample's
+ *              index (lowest index on ties); no such sample: NaN, -1.  Columns 0, 1 are `metrics_min`'s min_ade, min_fde bit for bit,
+ *              args[b,0] its best.
+ *              BADARG (NULL gen / gt / out, one of mins / args NULL), SHAPE (B <= 0, K < 1, Tmax outside 1 .. 256, D outside 1 .. 64).
+ *              No atomics, no state between launches: a replay is bit-equal, and a row's bits depend on neither K, its slot, B nor the
+ *              lengths of its neighbours. */
+int egomi_traj_metrics_full(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int K, int Tmax, int D, int rot0,
+                            double* out, double* mins, int32_t* args, egomi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Trainable point backbone (--unfreeze_pc_encoder, models/pointllm/model_arch.py:33-36): the backward
