@@ -933,6 +933,8 @@ extern "C" int egomi_ce_fwd_bwd(const void* logits, int64_t ld, const int64_t* t
 // ------------------------------------------------------------------------------------------------
 // AdamW (torch.optim.AdamW semantics, reference optimizer: train.py:107-111).  fp32 master/moments;
 // optional low-precision model copy written in the same pass.
+// adamw_kernel, adamw_vec4_kernel and adamw_launch have copies below that read the gradient scale from device
+// memory (adamw_ds_kernel, adamw_vec4_ds_kernel, adamw_ds_launch): a change to either must be made in both.
 // ------------------------------------------------------------------------------------------------
 template <typename G> __device__ __forceinline__ float adamw_g(const G* g, long long i);
 template <> __device__ __forceinline__ float adamw_g<float>(const float* g, long long i) { return g[i]; }
@@ -1030,6 +1032,91 @@ extern "C" int egomi_adamw_g16(float* master, void* model_copy, const void* grad
                                float beta2, float eps, float weight_decay, int step, float grad_scale, int copy_dtype, egomi_stream_t stream) {
     return adamw_launch<bf16_t>(master, model_copy, (const bf16_t*)grad_bf16, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, copy_dtype,
                                 (hipStream_t)stream);
+}
+
+// The same two kernels with the gradient scale read from device memory (egomi_clip_scale's out[2]: the step's scale times the clipping
+// coefficient, known only on the device).  They are separate kernels, not a template parameter of the two above, so that those keep their
+// code; the loops, the element-to-lane mapping and adamw_elem are the same, so a device value equal to the host value gives the same bits.
+template <typename T, typename G>
+__global__ __launch_bounds__(256) void adamw_ds_kernel(float* p, T* p_model, const G* g, float* m, float* v, long long n, float lr, float b1,
+                                                       float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* gscale_dev) {
+    const float gscale = *gscale_dev;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_elem(pi, mi, vi, adamw_g<G>(g, i), lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if (p_model) Cvt<T>::st(p_model + i, pi);
+    }
+}
+
+template <typename T, typename G>
+__global__ __launch_bounds__(256) void adamw_vec4_ds_kernel(float* p, T* p_model, const G* g, float* m, float* v, long long n4, float lr, float b1,
+                                                            float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* gscale_dev) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const float gscale = *gscale_dev;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        f32x4 g4;
+        if constexpr (sizeof(G) == 4) g4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
+        else {
+            const u32x2 r = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(g) + i);
+            g4[0] = __uint_as_float(r[0] << 16); g4[1] = __uint_as_float(r[0] & 0xFFFF0000u);
+            g4[2] = __uint_as_float(r[1] << 16); g4[3] = __uint_as_float(r[1] & 0xFFFF0000u);
+        }
+        f32x4 p4 = reinterpret_cast<f32x4*>(p)[i], m4 = reinterpret_cast<f32x4*>(m)[i], v4 = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pi = p4[j], mi = m4[j], vi = v4[j];
+            adamw_elem(pi, mi, vi, g4[j], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+            p4[j] = pi; m4[j] = mi; v4[j] = vi;
+        }
+        reinterpret_cast<f32x4*>(p)[i] = p4; reinterpret_cast<f32x4*>(m)[i] = m4; reinterpret_cast<f32x4*>(v)[i] = v4;
+        if (p_model) {
+            T o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Cvt<T>::st(o + j, p4[j]);
+            typedef T tx4 __attribute__((ext_vector_type(4)));
+            reinterpret_cast<tx4*>(p_model)[i] = tx4{o[0], o[1], o[2], o[3]};
+        }
+    }
+}
+
+template <typename G>
+static int adamw_ds_launch(float* master, void* model_copy, const G* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype, hipStream_t stream) {
+    if (!master || !grad || !m || !v || !grad_scale_dev) return EGOMI_E_BADARG;
+    if (n <= 0 || step <= 0) return EGOMI_E_SHAPE;
+    if (model_copy && copy_dtype != EGOMI_F32 && copy_dtype != EGOMI_BF16) return EGOMI_E_BADARG;
+    const float bc1 = 1.0f - powf(beta1, (float)step), bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+    const long long n4 = n / 4, rest = n - 4 * n4;
+    const bool vec = n4 > 0 && (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && ((uintptr_t)grad & (4 * sizeof(G) - 1)) == 0 &&
+                     (!model_copy || (copy_dtype == EGOMI_BF16 && ((uintptr_t)model_copy & 7) == 0));
+    if (vec) {
+        EGOMI_LAUNCH((adamw_vec4_ds_kernel<bf16_t, G>), dim3(ew_grid(n4)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
+                           n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev);
+        if (rest == 0) return egomi_launch_status();
+        master += 4 * n4; grad += 4 * n4; m += 4 * n4; v += 4 * n4; n = rest;
+        if (model_copy) model_copy = (bf16_t*)model_copy + 4 * n4;
+    }
+    if (!model_copy || copy_dtype == EGOMI_F32)
+        EGOMI_LAUNCH((adamw_ds_kernel<float, G>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (float*)model_copy, grad, m, v,
+                           (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev);
+    else
+        EGOMI_LAUNCH((adamw_ds_kernel<bf16_t, G>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
+                           (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev);
+    return egomi_launch_status();
+}
+
+extern "C" int egomi_adamw_ds(float* master, void* model_copy, const float* grad, float* m, float* v, int64_t n, float lr, float beta1,
+                              float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype,
+                              egomi_stream_t stream) {
+    return adamw_ds_launch<float>(master, model_copy, grad, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, copy_dtype,
+                                  (hipStream_t)stream);
+}
+extern "C" int egomi_adamw_g16_ds(float* master, void* model_copy, const void* grad_bf16, float* m, float* v, int64_t n, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype,
+                                  egomi_stream_t stream) {
+    return adamw_ds_launch<bf16_t>(master, model_copy, (const bf16_t*)grad_bf16, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev,
+                                   copy_dtype, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------

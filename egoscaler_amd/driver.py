@@ -508,7 +508,8 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
     rank, world = _rank_world()
     accum = max(1, int(getattr(args, "grad_accum_steps", 1) or 1))
     micro = micro_batch_per_rank(args.bs, accum, world)
-    opt = EgoAdamW(model, lr=float(args.lr_llm))
+    clip = float(getattr(args, "max_grad_norm", 0) or 0)                              # 0: no clipping, nothing below changes
+    opt = EgoAdamW(model, lr=float(args.lr_llm), max_grad_norm=clip) if clip > 0 else EgoAdamW(model, lr=float(args.lr_llm))
     sync = GradSync(wire_dtype=torch.bfloat16 if model.engine.dtype == torch.bfloat16 else None, resident=True) if world > 1 else None     # EgoAdamW reads the wire
     if sync is None and model.engine.dtype == torch.bfloat16 and model.engine.any_layer_trainable and model.engine.device.type == "cuda":
         sync = GradSync(wire_dtype=torch.bfloat16, resident=True, local=True)      # one rank, --unfreeze_language_model: bf16 weight gradients in per-layer wire buffers (dp.py), nothing exchanged
@@ -569,10 +570,19 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
             opt.step(grad_scale=1.0 / (n_mb * world), lr=lr_now, overlap=model.engine.any_layer_trainable)    # --unfreeze_language_model: on a side stream,
                                                                                                               # under the next step's forward pass (optim.py)
             if step_log is not None:
-                step_log({"epoch": epoch, "step": global_step, "learning_rate": lr_now, "loss": float(loss) if n_mb == 1 else None})
+                entry = {"epoch": epoch, "step": global_step, "learning_rate": lr_now, "loss": float(loss) if n_mb == 1 else None}
+                if clip > 0:
+                    entry["grad_norm"] = float(opt.last_grad_norm)
+                step_log(entry)
             global_step += 1
         rec = {"epoch": epoch, "train_loss": float(run) / max(1, steps_per_epoch), "global_step": global_step,
                "learning_rate": linear_warmup_lr(float(args.lr_llm), global_step, total_steps)}
+        if clip > 0:                                                                   # one read of the device-side statistics per epoch
+            gs = opt.grad_stats(reset=True)
+            rec.update({k: gs[k] for k in ("grad_norm_mean", "grad_norm_max", "clipped_steps", "nonfinite_steps")})
+            if gs["nonfinite_steps"]:                                                  # before the checkpoint: a poisoned state must not replace a good file
+                raise FloatingPointError(f"epoch {epoch}: the gradient norm was not finite in {gs['nonfinite_steps']} of {gs['steps']} optimizer "
+                                         f"steps; masters and moments are poisoned, no checkpoint written")
         if val_data is not None:
             m, _ = run_validation(model, val_data, args, device, max_batches=getattr(args, "val_batches", None))
             rec.update(m)
@@ -666,6 +676,10 @@ def parse_args(argv=None):
     ap.add_argument("--bs", type=int, default=8)
     ap.add_argument("--grad_accum_steps", type=int, default=1)
     ap.add_argument("--lr_llm", type=float, default=2e-5)
+    ap.add_argument("--max_grad_norm", type=float, default=0.0,
+                    help="train: clip the global gradient norm of every optimizer step to this value on the device (HF Trainer's "
+                         "max_grad_norm / DeepSpeed's gradient_clipping); 'inf' only measures it; adds grad_norm_mean / grad_norm_max / "
+                         "clipped_steps / nonfinite_steps to the epoch record and grad_norm to the step log (0: off, the reference does not clip)")
     ap.add_argument("--num_bins", type=int, default=256)
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", 0)))
@@ -720,6 +734,8 @@ def parse_args(argv=None):
                          "minIDE / minGD / minDTW, with --select GD_sel / DTW_sel, with --num_modes minGD_M / minDTW_M) to the record and the "
                          "per-sample values per image id to the dump")
     a = ap.parse_args(argv)
+    if not a.max_grad_norm >= 0:
+        ap.error("--max_grad_norm must be >= 0 (0: off)")
     try:
         check_val_options(int(a.num_samples or 1), a.num_beams, a.val_sample, a.select, a.rescore, a.num_modes, a.mode_radius, a.soft_decode,
                           decoding_rules=False)

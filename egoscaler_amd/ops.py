@@ -565,11 +565,67 @@ def cross_entropy(logits, targets, ignore_index, dlogits=None, grad_scale=1.0):
     return ls, cnt
 
 
-def adamw(master, model_copy, grad, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
+def adamw(master, model_copy, grad, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, grad_scale_dev=None):
+    """grad_scale_dev (a device fp32 scalar, clip_scale's out[2:3]): the scale is read on the device and `grad_scale` is not used."""
     if grad.dtype not in (torch.float32, torch.bfloat16) or not grad.is_contiguous() or grad.numel() != master.numel():
         raise _lib.EgomiError("adamw: the gradient must be a contiguous fp32 or bf16 tensor of the parameter's size")
+    if grad_scale_dev is not None:
+        if grad_scale_dev.dtype != torch.float32 or grad_scale_dev.numel() != 1:
+            raise _lib.EgomiError("adamw: grad_scale_dev must be one fp32 value on the device")
+        call("egomi_adamw_ds" if grad.dtype == torch.float32 else "egomi_adamw_g16_ds", master, model_copy, grad, m, v, master.numel(), lr, beta1,
+             beta2, eps, wd, step, grad_scale_dev, dt(model_copy.dtype) if model_copy is not None else F32, S())
+        return
     call("egomi_adamw" if grad.dtype == torch.float32 else "egomi_adamw_g16", master, model_copy, grad, m, v, master.numel(), lr, beta1, beta2, eps,
          wd, step, grad_scale, dt(model_copy.dtype) if model_copy is not None else F32, S())
+
+
+def grad_sumsq_chunk():
+    """Elements per stage-1 workgroup of grad_sumsq (a constant of the library)."""
+    return query("egomi_grad_sumsq_chunk")
+
+
+class GradTable:
+    """The device-resident segment table of grad_sumsq for a list of contiguous fp32 / bf16 tensors, with its outputs and workspace.
+    `key` is the tuple of (address, numel, dtype) it was built from: the caller rebuilds the table when that changes.  Building it
+    copies three small host arrays to the device; using it never syncs."""
+
+    def __init__(self, tensors):
+        if not tensors:
+            raise _lib.EgomiError("grad_sumsq: no gradient tensors")
+        for g in tensors:
+            if not g.is_cuda or g.dtype not in (torch.float32, torch.bfloat16) or not g.is_contiguous() or g.numel() <= 0:
+                raise _lib.EgomiError("grad_sumsq: every segment must be a non-empty contiguous fp32 or bf16 device tensor")
+        self.key = self.key_of(tensors)
+        self.tensors = list(tensors)                            # the table holds addresses: keep what they point at alive
+        dev, ch = tensors[0].device, grad_sumsq_chunk()
+        self.n_seg = len(tensors)
+        self.n_chunks = sum(-(-g.numel() // ch) for g in tensors)
+        self.addr = torch.tensor([k[0] for k in self.key], dtype=torch.int64).to(dev)
+        self.numel = torch.tensor([k[1] for k in self.key], dtype=torch.int64).to(dev)
+        codes = [dt(k[2]) for k in self.key]
+        self.dtype0 = codes[0]                                  # one dtype throughout (every table outside data parallelism): no dtype table
+        self.dtype = None if len(set(codes)) == 1 else torch.tensor(codes, dtype=torch.int32).to(dev)
+        self.seg_sumsq = torch.zeros(self.n_seg, dtype=torch.float64, device=dev)
+        self.total = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.ws_bytes = query("egomi_grad_sumsq_workspace_bytes", self.n_seg, self.n_chunks)
+        self.ws = torch.empty(self.ws_bytes // 8, dtype=torch.float64, device=dev)
+
+    @staticmethod
+    def key_of(tensors):
+        return tuple((g.data_ptr(), g.numel(), g.dtype) for g in tensors)
+
+
+def grad_sumsq(table):
+    """table.seg_sumsq f64 [n_seg] and table.total f64 [1] of the table's segments: two launches, float64, no atomics (include/egomi.h)."""
+    call("egomi_grad_sumsq", table.addr, table.numel, table.dtype, table.dtype0, table.n_seg, table.n_chunks, table.seg_sumsq, table.total, table.ws,
+         table.ws_bytes, S())
+    return table.seg_sumsq, table.total
+
+
+def clip_scale(total_sumsq, grad_scale, max_norm, out, stats):
+    """out f32 [3] = (total_norm, coef, effective grad scale); stats f64 [5] accumulated in place (include/egomi.h)."""
+    call("egomi_clip_scale", total_sumsq, grad_scale, max_norm, out, stats, S())
+    return out
 
 
 def transpose(x, ldo=None, out=None):

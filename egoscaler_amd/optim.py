@@ -7,8 +7,14 @@ from . import ops
 
 
 class EgoAdamW:
-    def __init__(self, model, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
+    def __init__(self, model, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=None):
+        """max_grad_norm (None: no clipping, the step as it always was): a float clips the global gradient norm to it
+        (torch.nn.utils.clip_grad_norm_ semantics), float("inf") only measures it.  See _clip."""
         self.model, self.lr, self.betas, self.eps, self.wd = model, lr, betas, eps, weight_decay
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"EgoAdamW: max_grad_norm must be > 0 (or None), got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._clip_table = self._clip_names = self._clip_out = self._clip_stats = self._clip_scale = None
         self.t = 0
         self.state = {}
         for n, p in model.named_parameters():
@@ -23,10 +29,13 @@ class EgoAdamW:
         registers free (attention, norms, RoPE; the 8-phase GEMM does not), instead of queueing all 38 ms of it behind the backward pass.  step()
         then handles what is left (projector / point backbone, embedding, final norm, lm_head).  Values are the same as the plain step's.
         Returns False (and arms nothing) where that is not possible: an exchange is attached (gradients are not final until it has run), no CUDA
-        device, or resident W^T copies of trainable weights that a later product of this backward could still read."""
+        device, or resident W^T copies of trainable weights that a later product of this backward could still read — or max_grad_norm is set:
+        the global norm needs every gradient of the step, so no layer can be updated under the backward pass of the layers below it."""
         eng = self.model.engine
         self._armed = None
         eng.layer_final_hook = None
+        if self.max_grad_norm is not None:
+            return False
         if (eng.grad_sync is not None and not getattr(eng.grad_sync, "local", False)) or eng.device.type != "cuda" or not eng.any_layer_trainable:
             return False
         if any(nm in eng.trainable for nm in getattr(eng, "wT", {})):      # (EGOMI_GEMM_TN=0 route; before the first forward pass the hook looks again)
@@ -62,7 +71,74 @@ class EgoAdamW:
             return
         p = st["p"]
         copy = None if p.dtype == torch.float32 else p.data
+        if self.max_grad_norm is not None:                 # clipping: the scale (grad_scale x coefficient) is on the device, _clip put it there
+            ops.adamw(st["master"], copy, g, st["m"], st["v"], lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t if t is None else t,
+                      grad_scale_dev=self._clip_scale)
+            return
         ops.adamw(st["master"], copy, g, st["m"], st["v"], lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t if t is None else t, grad_scale)
+
+    def _clip_prepare(self, eng):
+        """The segment table over exactly the buffers _update will read (reduced_grad, else main_grad; entries without a gradient left out):
+        device-resident, rebuilt only when an address, size or dtype changed.  False when no entry has a gradient: the step then updates
+        nothing, as without clipping."""
+        names, grads = [], []
+        for n in self.state:
+            g = eng.reduced_grad.get(n)
+            if g is None:
+                g = eng.main_grad.get(n)
+            if g is not None:
+                names.append(n)
+                grads.append(g)
+        if not grads:
+            return False
+        if self._clip_table is None or self._clip_table.key != ops.GradTable.key_of(grads):
+            self._clip_table, self._clip_names = ops.GradTable(grads), names
+        if self._clip_out is None:
+            self._clip_out = torch.zeros(3, dtype=torch.float32, device=eng.device)
+            self._clip_stats = torch.zeros(5, dtype=torch.float64, device=eng.device)
+            self._clip_scale = self._clip_out[2:3]
+        return True
+
+    def _clip(self, grad_scale):
+        """On the stream the updates run on, before the first of them: the float64 sum of squares of every gradient of the step (two
+        launches), then total norm, coefficient and effective scale (one launch).  Nothing here waits for the device.  Under data
+        parallelism this runs after the exchange, on the rank-summed values every rank holds bit-identically: every rank gets the same
+        coefficient and no collective is added."""
+        _, total = ops.grad_sumsq(self._clip_table)
+        ops.clip_scale(total, grad_scale, self.max_grad_norm, self._clip_out, self._clip_stats)
+        self._clip_event = torch.cuda.Event()
+        self._clip_event.record()
+
+    @property
+    def last_grad_norm(self):
+        """Device fp32 scalar: the global norm of the latest step's gradient as the update saw it (grad_scale folded in), before clipping.
+        The current stream is made to wait for the kernel that wrote it (it may have run on the side stream); the host is not."""
+        if self._clip_out is None:
+            raise RuntimeError("EgoAdamW.last_grad_norm: no step with max_grad_norm set has run")
+        torch.cuda.current_stream().wait_event(self._clip_event)
+        return self._clip_out[0]
+
+    def per_tensor_grad_norms(self):
+        """name -> grad_scale * sqrt(sum of squares) of the latest step, for diagnostics.  Waits for the device."""
+        if self._clip_table is None:
+            raise RuntimeError("EgoAdamW.per_tensor_grad_norms: no step with max_grad_norm set has run")
+        self.model.engine.wait_param_updates()
+        seg = self._clip_table.seg_sumsq.cpu().tolist()
+        return {n: self._last_grad_scale * s ** 0.5 for n, s in zip(self._clip_names, seg)}
+
+    def grad_stats(self, reset=True):
+        """{"steps", "clipped_steps", "nonfinite_steps", "grad_norm_mean", "grad_norm_max"} since the last reset.  Waits for the device."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("EgoAdamW.grad_stats: max_grad_norm is not set")
+        if self._clip_stats is None:
+            return {"steps": 0, "clipped_steps": 0, "nonfinite_steps": 0, "grad_norm_mean": float("nan"), "grad_norm_max": 0.0}
+        self.model.engine.wait_param_updates()
+        steps, clipped, bad, total, peak = self._clip_stats.cpu().tolist()
+        if reset:
+            self._clip_stats.zero_()
+        finite = steps - bad
+        return {"steps": int(steps), "clipped_steps": int(clipped), "nonfinite_steps": int(bad),
+                "grad_norm_mean": total / finite if finite else float("nan"), "grad_norm_max": peak}
 
     def step(self, grad_scale=1.0, lr=None, overlap=False):
         """overlap=True (training loops that go straight on to the next forward pass: bench.py, driver.train): the updates run on a side stream in
@@ -79,8 +155,13 @@ class EgoAdamW:
         early = armed["done"] if armed is not None else set()       # decoder layers arm() has already updated under the backward pass
         if early and (armed["lr"] != lr or armed["grad_scale"] != grad_scale):
             raise RuntimeError("EgoAdamW.step: lr / grad_scale differ from the ones given to arm()")
+        clip = self.max_grad_norm is not None and self._clip_prepare(eng)
+        if clip:
+            self._last_grad_scale = float(grad_scale)
         if not (overlap and eng.device.type == "cuda" and not any(nm in eng.trainable for nm in eng.wT)):
             eng.wait_param_updates()
+            if clip:
+                self._clip(grad_scale)
             for n, st in self.state.items():
                 if eng.param_group_of(n) not in early:
                     self._update(n, st, eng, lr, grad_scale)
@@ -96,6 +177,8 @@ class EgoAdamW:
             self._side = torch.cuda.Stream()
         self._side.wait_stream(cur)                        # gradients final (and exchanged); every reader of the old weights has been queued
         with torch.cuda.stream(self._side):
+            if clip:
+                self._clip(grad_scale)
             for key in order:
                 names = groups.get(key)
                 if not names or key in early:

@@ -727,6 +727,52 @@ int egomi_adamw(float* master, void* model_copy, const float* grad, float* m, fl
  * bf16 engine does after its reduce: fp32 master / moments updated from the reduced low-precision gradient, train.py:92-104,184). */
 int egomi_adamw_g16(float* master, void* model_copy, const void* grad_bf16, float* m, float* v, int64_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int step, float grad_scale, int copy_dtype, egomi_stream_t stream);
+/* Both steps with grad_scale read from device memory (grad_scale_dev, one fp32: egomi_clip_scale's out[2]) instead of passed by value.
+ * Same element arithmetic and the same 16-B / scalar split: a device value equal to the host value gives master, m, v and model_copy the
+ * bits of the two entry points above. */
+int egomi_adamw_ds(float* master, void* model_copy, const float* grad, float* m, float* v, int64_t n, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype, egomi_stream_t stream);
+int egomi_adamw_g16_ds(float* master, void* model_copy, const void* grad_bf16, float* m, float* v, int64_t n, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype,
+                       egomi_stream_t stream);
+
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_ semantics; the reference does not clip — HF Trainer max_grad_norm and
+ * DeepSpeed gradient_clipping are what users of the added training modes expect).
+ *
+ * grad_sumsq: the sum of squares of n_seg gradient tensors ("segments") in one call of two launches, whatever n_seg.
+ *   seg_addr  i64 [n_seg]  device address of each segment (contiguous elements)
+ *   seg_numel i64 [n_seg]  element count of each; each must be > 0 (device data: the call cannot check it; a count <= 0 contributes 0)
+ *   seg_dtype i32 [n_seg]  EGOMI_F32 / EGOMI_BF16 per segment, or NULL: every segment has `dtype` (every table outside data parallelism is
+ *                          fp32 throughout).  `dtype` is not read when a table is given, but must be one of the two either way
+ *                          (UNSUPPORTED); the table is device data, which the call cannot check: an entry that is neither makes that
+ *                          segment's sum, and the total, NaN, and nothing is read through its address
+ *   n_chunks               sum over the segments of ceil(numel / C), C = egomi_grad_sumsq_chunk() elements (or more: surplus workgroups do
+ *                          nothing).  The caller knows the counts it wrote into the table.  Fewer than the table needs: the segments
+ *                          past it and the total report NaN; nothing is read or written out of bounds
+ *   seg_sumsq f64 [n_seg], total_sumsq f64 [1] (both written, not accumulated);  workspace: egomi_grad_sumsq_workspace_bytes, 8-B aligned
+ * Stage 1: one workgroup per chunk of C elements of one segment, 16-B loads, every element widened to float64, squared (exact) and
+ * added in float64 in a fixed order — fp32 squares overflow above 1.8e19 and vanish below 1e-19; float64 does neither, and the pass is
+ * HBM-bound whatever the arithmetic — one float64 partial per chunk.  Stage 2: one workgroup adds each segment's partials, then the
+ * segments, in a fixed order (lane-strided in ascending index, then a fixed tree).  No atomics of any kind.
+ * Contract: a segment's seg_sumsq bits depend only on its element count, dtype and values — not on its position in the table, its
+ * neighbours or n_seg, not on the alignment of its address (a segment that is not 16-B aligned takes 4-B / 2-B loads with the same
+ * element-to-lane mapping), not on the grid (n_chunks) and not on which run it is.  total_sumsq's bits depend on the seg_sumsq values in
+ * table order.  All index arithmetic is 64-bit.
+ * Errors: BADARG for a NULL table, output or workspace; SHAPE for n_seg <= 0, n_chunks < n_seg or > 2^31-1, or a workspace that is too
+ * small or not 8-B aligned; UNSUPPORTED for `dtype`.
+ *
+ * clip_scale: one thread, float64.  out f32 [3]:
+ *   out[0] = total_norm = grad_scale * sqrt(total_sumsq)   (the norm of the gradient the update applies, 1/world and 1/accum folded in)
+ *   out[1] = coef = min(1, max_norm / (total_norm + 1e-6)) (clip_grad_norm_ with its 1e-6; a NaN norm gives a NaN coefficient)
+ *   out[2] = grad_scale itself, bit for bit, when coef >= 1; else (float)((double)grad_scale * coef) — what the _ds steps above read
+ * stats f64 [5], accumulated in place (the caller zeroes it for a fresh window): steps seen, steps clipped (finite norm, coef < 1),
+ * steps whose fp32 total_norm is not finite, the sum of the finite norms, their maximum.
+ * max_norm = +inf is legal ("measure only": coef is 1 whenever the norm is finite); max_norm <= 0 or NaN is BADARG. */
+int64_t egomi_grad_sumsq_chunk(void);
+size_t egomi_grad_sumsq_workspace_bytes(int n_seg, int64_t n_chunks);
+int egomi_grad_sumsq(const int64_t* seg_addr, const int64_t* seg_numel, const int32_t* seg_dtype, int dtype, int n_seg, int64_t n_chunks,
+                     double* seg_sumsq, double* total_sumsq, void* workspace, size_t workspace_bytes, egomi_stream_t stream);
+int egomi_clip_scale(const double* total_sumsq, float grad_scale, float max_norm, float* out, double* stats, egomi_stream_t stream);
 
 /* layout helpers: out[c, r] = in[r, c] for r < R, zero for R <= r < ldo; cast; add */
 int egomi_transpose(const void* in, int R, int C, int64_t ldi, void* out, int64_t ldo, int dtype, egomi_stream_t stream);
