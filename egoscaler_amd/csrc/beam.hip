@@ -17,46 +17,14 @@
 //   attn_decode_rows (attn_decode.hip): key t of row r is read from physical cache row kv_row[r, t].  Prompt positions of
 //               every beam point at its item's single prompt row, later positions at the row that computed the token, so a reorder
 //               moves no K/V bytes and no referenced slot is ever overwritten (a step writes slot `pos` of each row's own physical row).
-#include "common.h"
-#include "philox.h"
-#include <math.h>
+#include "choice.h"
 
-#define BR_THREADS 1024
-#define BR_NPT 32                        // values per thread held in registers: V <= 32768
+#define BR_THREADS CH_THREADS
+#define BR_NPT CH_NPT                    // the row lives in registers: V <= 32768
 #define BU_THREADS 256
 #define BU_MAXC 2048                     // nb * K candidates per item
 #define BU_MAXK 64                       // K = max(2, 1 + n_eos) * nb with one eos: nb <= 32
 #define BEAM_NEG 1.0e9f
-
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)(v & 0xFFFFFFFFu), o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        v = other > v ? other : v;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int w = 0; w < nw; ++w) v = red[w] > v ? red[w] : v;
-    return v;
-}
-__device__ __forceinline__ int block_sum_i(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int i = 0; i < nw; ++i) t += red[i];
-    return t;
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-    k ^= (k >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-    return __uint_as_float(k);
-}
 
 // ------------------------------------------------------------------------------------------------
 // beam_rows
@@ -75,15 +43,17 @@ struct BeamRowArgs {
 
 template <typename T>
 __global__ __launch_bounds__(BR_THREADS) void beam_rows_kernel(BeamRowArgs a) {
-    __shared__ float redf[16];
-    __shared__ int redi[16];
-    __shared__ unsigned long long red64[16];
+    __shared__ float redf[CH_WAVES];
+    __shared__ int redi[CH_WAVES];
+    __shared__ unsigned long long red64[CH_WAVES];
     if (a.ctl && a.ctl[0] == 0) return;                            // the loop has closed: HF ran no such iteration
     const int r = blockIdx.x, tid = threadIdx.x, V = a.V;
     const T* lg = (const T*)a.logits + (long long)(r / a.lg_div) * a.ld;
     float* sc = a.scores + (long long)r * a.ld_scores;
     const float NEG_INF = -INFINITY;
-    float x[BR_NPT];
+    ChoiceRow<true> row;
+    row.sc = sc; row.V = V;
+    float (&x)[BR_NPT] = row.x;
 
     // ---- log_softmax in fp32 (x - max - log(sum exp(x - max)), element c = i * 1024 + tid)
     float mx = NEG_INF;
@@ -106,14 +76,7 @@ __global__ __launch_bounds__(BR_THREADS) void beam_rows_kernel(BeamRowArgs a) {
 #pragma unroll
         for (int i = 0; i < BR_NPT; ++i) { const int c = i * BR_THREADS + tid; if (c < V) sc[c] = x[i]; }
         __syncthreads();
-        const int64_t* sq = a.seq + (long long)r * a.ld_seq;
-        for (int j = tid; j < a.pos; j += BR_THREADS) {
-            const long long t = sq[j];
-            if (t >= 0 && t < V) {
-                const float s = (Cvt<T>::ld(lg + t) - m) - lz;
-                sc[t] = s < 0.f ? s * a.rep_penalty : s / a.rep_penalty;
-            }
-        }
+        rep_penalty_scatter(sc, V, a.seq + (long long)r * a.ld_seq, 0, a.pos, a.rep_penalty, [&](long long t) { return (Cvt<T>::ld(lg + t) - m) - lz; });
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < BR_NPT; ++i) { const int c = i * BR_THREADS + tid; if (c < V) x[i] = sc[c]; }
@@ -125,71 +88,15 @@ __global__ __launch_bounds__(BR_THREADS) void beam_rows_kernel(BeamRowArgs a) {
 #pragma unroll
             for (int i = 0; i < BR_NPT; ++i) if (i * BR_THREADS + tid < V) x[i] = x[i] / a.temperature;
         }
-        // ---- top-k (k = max(top_k, min_keep)): k-th largest value by radix select; remove values below it
-        const int kk = a.top_k > a.min_keep ? a.top_k : a.min_keep;
-        if (a.top_k > 0 && kk < V) {
-            unsigned prefix = 0;
-            for (int bit = 31; bit >= 0; --bit) {
-                const unsigned cand = prefix | (1u << bit);
-                int n = 0;
-#pragma unroll
-                for (int i = 0; i < BR_NPT; ++i) n += (i * BR_THREADS + tid < V && f2key(x[i]) >= cand) ? 1 : 0;
-                if (block_sum_i(n, redi) >= kk) prefix = cand;
-            }
-#pragma unroll
-            for (int i = 0; i < BR_NPT; ++i) if (i * BR_THREADS + tid < V && f2key(x[i]) < prefix) x[i] = NEG_INF;
-        }
-        // ---- top-p: sample_rows_kernel's radix walk over (value image << 32 | index); the min_keep largest keys are always kept
+        // ---- TopK with k = max(top_k, min_keep), TopP keeping the min_keep largest keys (choice.h: the sampler's own steps)
+        if (a.top_k > 0) top_k_step(row, a.top_k > a.min_keep ? a.top_k : a.min_keep, redi);
         if (a.top_p < 1.0f) {
-            unsigned long long keep = ~0ull;                       // the min_keep-th largest key
+            unsigned long long top = 0ull, keep = ~0ull;           // the largest and the min_keep-th largest key
             for (int q = 0; q < a.min_keep; ++q) {
-                unsigned long long best = 0ull;
-#pragma unroll
-                for (int i = 0; i < BR_NPT; ++i) {
-                    const int c = i * BR_THREADS + tid;
-                    const unsigned long long k = ((unsigned long long)f2key(x[i]) << 32) | (unsigned)c;
-                    if (c < V && k < keep && k > best) best = k;
-                }
-                keep = block_max_u64(best, red64);
+                keep = row_max_below(row, keep, red64);
+                if (q == 0) top = keep;
             }
-            unsigned long long top = 0ull;
-#pragma unroll
-            for (int i = 0; i < BR_NPT; ++i) {
-                const int c = i * BR_THREADS + tid;
-                const unsigned long long k = ((unsigned long long)f2key(x[i]) << 32) | (unsigned)c;
-                if (c < V && k > top) top = k;
-            }
-            top = block_max_u64(top, red64);
-            const float mm = key2f((unsigned)(top >> 32));
-            float e[BR_NPT], zs = 0.f;
-#pragma unroll
-            for (int i = 0; i < BR_NPT; ++i) {
-                e[i] = (i * BR_THREADS + tid < V && x[i] != NEG_INF) ? expf(x[i] - mm) : 0.f;
-                zs += e[i];
-            }
-            const float Z = block_sum(zs, redf);
-            const float thr = (float)(1.0 - (double)a.top_p) * Z;
-            int idx_bits = 1;
-            while ((1 << idx_bits) < V) ++idx_bits;
-            unsigned long long prefix = 0ull;
-            for (int step = 0; step < 32 + idx_bits; ++step) {
-                const int bit = step < 32 ? 63 - step : idx_bits - 1 - (step - 32);
-                const unsigned long long cand = prefix | (1ull << bit);
-                float s = 0.f;
-#pragma unroll
-                for (int i = 0; i < BR_NPT; ++i) {
-                    const int c = i * BR_THREADS + tid;
-                    const unsigned long long k = ((unsigned long long)f2key(x[i]) << 32) | (unsigned)c;
-                    s += (c < V && k < cand) ? e[i] : 0.f;
-                }
-                if (block_sum(s, redf) <= thr) prefix = cand;
-            }
-#pragma unroll
-            for (int i = 0; i < BR_NPT; ++i) {
-                const int c = i * BR_THREADS + tid;
-                const unsigned long long k = ((unsigned long long)f2key(x[i]) << 32) | (unsigned)c;
-                if (c < V && k < prefix && k < keep) x[i] = NEG_INF;
-            }
+            top_p_step(row, a.top_p, top, keep, redf);
         }
     }
 
@@ -207,11 +114,7 @@ __global__ __launch_bounds__(BR_THREADS) void beam_rows_kernel(BeamRowArgs a) {
         if (c >= V) { taken |= 1u << i; continue; }
         sc[c] = x[i];
         float v = x[i] + rs;
-        if (a.do_sample && v != NEG_INF) {
-            unsigned rb[4];
-            philox4x32((unsigned)(c >> 2), (unsigned)r, (unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)seed, (unsigned)(seed >> 32), rb);
-            v += gumbel_from_bits(rb[c & 3]);
-        }
+        if (a.do_sample && v != NEG_INF) v += gumbel_noise((unsigned)r, (unsigned)c, seed, ctr);
         kimg[i] = f2key(v);
     }
     // ---- the row's K best: K rounds of a block arg-max; the owner of the winner emits it and drops it

@@ -4,8 +4,8 @@
 // of seq_rank.
 //
 // egomi_traj_modes: one 256-thread workgroup per clip, K <= 64.
-//   Phase 1, all 256 threads: the K (K - 1) / 2 unordered pairs are dealt round-robin; a thread computes d(j, i) as traj_medoid_kernel does
-//     (float64, each sample padded with its own last step, t and then d in index order) and stores it to both halves of a [64][64] float64
+//   Phase 1, all 256 threads: the K (K - 1) / 2 unordered pairs are dealt round-robin; a thread computes d(j, i) with traj_medoid_kernel's own
+//     function (traj_disp.h: traj_pair_dist, so that kernel's cost is the index-order mean of a row of `dist`, bit for bit) and stores it to both halves of a [64][64] float64
 //     LDS tile, so the matrix is bit-symmetric; diagonal 0, NaN wherever j or i is invalid.  The tile goes out to `dist` row by row.
 //   Phase 2, wavefront 0 alone, lane j = sample j, no barrier and no LDS write: lanes read column j of a tile row (tile[c][j] = d(j, c),
 //     consecutive addresses), talk through ballots and shuffles, and keep everything else in registers.
@@ -17,32 +17,11 @@
 //       assign  slot of the nearest mode (ties -> lower slot, a mode to itself), conf = members / n_valid
 //   The order of every sum depends on (K, Tmax, D, n_gen) only; nothing is accumulated across threads: a replay is bit-equal.
 #include "common.h"
+#include "traj_disp.h"
 #include <math.h>
 
 #define MODES_THREADS 256
 #define MODES_MAXK 64
-
-// traj_medoid_kernel's d(j, i) (nj, ni > 0): the same source expression, compiled here a second time with the same contraction setting.
-// What the header promises from it is the medoid's PICK at M = 1, not the bits of its cost.
-__device__ __forceinline__ double modes_pair_dist(const float* gj, int nj, const float* gi, int ni, int D) {
-    const int n = nj > ni ? nj : ni;
-    double acc = 0.0;
-    for (int t = 0; t < n; ++t) {
-        const int tj = t < nj ? t : nj - 1, ti = t < ni ? t : ni - 1;
-        double s = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double df = (double)gj[(long long)tj * D + d] - (double)gi[(long long)ti * D + d];
-            s += df * df;
-        }
-        acc += sqrt(s);
-    }
-    return acc / n;
-}
-
-__device__ __forceinline__ int modes_len(const int32_t* n_gen, long long at, int Tmax) {
-    const int n = n_gen ? n_gen[at] : Tmax;
-    return n > Tmax ? Tmax : n;
-}
 
 __global__ __launch_bounds__(MODES_THREADS) void traj_modes_kernel(const float* gen, const int32_t* n_gen, const float* score, int K, int Tmax, int D,
                                                                    int M, double radius, double* dist, int32_t* modes, double* conf,
@@ -52,15 +31,15 @@ __global__ __launch_bounds__(MODES_THREADS) void traj_modes_kernel(const float* 
     const float* gb = gen + (long long)b * K * Tmax * D;
 
     // ---- phase 1: the distance matrix
-    if (tid < K) tile[tid][tid] = modes_len(n_gen, (long long)b * K + tid, Tmax) > 0 ? 0.0 : NAN;
+    if (tid < K) tile[tid][tid] = traj_len(n_gen, (long long)b * K + tid, Tmax) > 0 ? 0.0 : NAN;
     const int npair = K * (K - 1) / 2;
     for (int p = tid; p < npair; p += MODES_THREADS) {
         int j = 0, rem = p;                                                 // pair p = (j, i), j < i, row by row
         while (rem >= K - 1 - j) { rem -= K - 1 - j; ++j; }
         const int i = j + 1 + rem;
-        const int nj = modes_len(n_gen, (long long)b * K + j, Tmax), ni = modes_len(n_gen, (long long)b * K + i, Tmax);
+        const int nj = traj_len(n_gen, (long long)b * K + j, Tmax), ni = traj_len(n_gen, (long long)b * K + i, Tmax);
         double d = NAN;
-        if (nj > 0 && ni > 0) d = modes_pair_dist(gb + (long long)j * Tmax * D, nj, gb + (long long)i * Tmax * D, ni, D);
+        if (nj > 0 && ni > 0) d = traj_pair_dist(gb + (long long)j * Tmax * D, nj, gb + (long long)i * Tmax * D, ni, D);
         tile[j][i] = d;
         tile[i][j] = d;
     }
@@ -73,7 +52,7 @@ __global__ __launch_bounds__(MODES_THREADS) void traj_modes_kernel(const float* 
 
     // ---- phase 2: one wavefront, lane j owns sample j; the tile is read-only from here on
     const int j = tid;
-    const bool valid = j < K && modes_len(n_gen, (long long)b * K + (j < K ? j : 0), Tmax) > 0;
+    const bool valid = j < K && traj_len(n_gen, (long long)b * K + (j < K ? j : 0), Tmax) > 0;
     const unsigned long long vmask = __ballot(valid);
     const int nvalid = __popcll(vmask);
 

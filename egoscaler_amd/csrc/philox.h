@@ -1,12 +1,7 @@
-// Device helpers shared by the token-choice kernels (sample.hip, beam.hip): the order-preserving integer image of a float and the
-// Philox4x32-10 + Gumbel draw that egomi_sample_rows / egomi_beam_rows add to scores (oracle/sampling.py restates it on the host).
+// The random draw of the token-choice kernels (choice.h; sample.hip, beam.hip): Philox4x32-10 and the Gumbel noise that egomi_sample_rows /
+// egomi_beam_rows add to the scores of one element.  oracle/sampling.py (gumbel_noise) restates gumbel_noise() on the host.
 #pragma once
 #include <math.h>
-
-__device__ __forceinline__ unsigned f2key(float v) {
-    unsigned u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);           // order-preserving: a < b  <=>  key(a) < key(b)
-}
 
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
 __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
@@ -22,4 +17,10 @@ __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2
 __device__ __forceinline__ float gumbel_from_bits(unsigned r) {
     const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);          // (0, 1) strictly
     return -logf(-logf(u));
+}
+// g = -log(-log u) of element (row, c) at draw counter `ctr`: counter (c / 4, row, ctr lo, ctr hi), key (seed lo, seed hi), word c % 4
+__device__ __forceinline__ float gumbel_noise(unsigned row, unsigned c, unsigned long long seed, unsigned long long ctr) {
+    unsigned r[4];
+    philox4x32(c >> 2, row, (unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)seed, (unsigned)(seed >> 32), r);
+    return gumbel_from_bits(r[c & 3]);
 }

@@ -47,100 +47,78 @@ __global__ __launch_bounds__(256) void traj_tokenize_kernel(const float* traj, c
     }
 }
 
-// one thread per sample: scan ids, emit values[b, step, 6] (bin centres linspace[idx]) and n_steps[b]
+// The scan of one row of ids, a bit-exact restatement of str_to_float (rt2, 6-DoF): cut at the first eos (train.py:241-242), split on
+// <tsep>, per segment the first run of six consecutive <p*> ids (the regex of utils.py:52-57); a segment without one repeats the previous
+// step once there is one (utils.py:88-90).  parse(hit): a step was parsed at ids hit .. hit+5; emit(n): step n goes out, as parsed last.
+// Returns the number of steps (<= Tmax).  Both detokenize kernels are this scan: their n_steps cannot differ.
+template <typename Parse, typename Emit>
+__device__ __forceinline__ int traj_scan(const int64_t* r, int L, int nb, int64_t p0, int64_t tsep, int64_t eos, int Tmax, Parse parse, Emit emit) {
+    int n = 0, end = L;
+    for (int j = 0; j < L; ++j) if (r[j] == eos) { end = j; break; }
+    int seg0 = 0;
+    bool have_last = false;
+    while (seg0 <= end && n < Tmax) {
+        int seg1 = seg0;
+        while (seg1 < end && r[seg1] != tsep) ++seg1;                       // segment [seg0, seg1)
+        int run = 0, hit = -1;
+        for (int j = seg0; j < seg1; ++j) {
+            if (r[j] >= p0 && r[j] < p0 + nb) { if (++run == 6) { hit = j - 5; break; } } else run = 0;
+        }
+        if (hit >= 0) { parse(hit); have_last = true; }
+        if (have_last) { emit(n); ++n; }
+        if (seg1 >= end) break;
+        seg0 = seg1 + 1;
+    }
+    return n;
+}
+
+// one thread per sample: values[b, step, 6] (bin centres linspace[idx]) and n_steps[b]
 __global__ __launch_bounds__(64) void traj_detokenize_kernel(const int64_t* ids, int B, int L, const double* bins, int nb, int64_t p0, int64_t tsep,
                                                              int64_t eos, int Tmax, float* out, int32_t* n_steps) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     const int64_t* r = ids + (long long)b * L;
-    int n = 0, end = L;
-    for (int j = 0; j < L; ++j) if (r[j] == eos) { end = j; break; }       // train.py:241-242: cut at the first eos
-    int seg0 = 0;
-    bool have_last = false;
     float last[6];
-    while (seg0 <= end && n < Tmax) {
-        int seg1 = seg0;
-        while (seg1 < end && r[seg1] != tsep) ++seg1;                       // segment [seg0, seg1)
-        // first run of six consecutive <p*> ids inside the segment (the regex of utils.py:52-57)
-        int run = 0, hit = -1;
-        for (int j = seg0; j < seg1; ++j) {
-            if (r[j] >= p0 && r[j] < p0 + nb) { if (++run == 6) { hit = j - 5; break; } } else run = 0;
-        }
-        if (hit >= 0) {
-            for (int c = 0; c < 6; ++c) last[c] = (float)bins[(int)(r[hit + c] - p0)];
-            have_last = true;
-        }
-        if (hit >= 0 || have_last) {                                        // utils.py:88-90 copy-forward
-            for (int c = 0; c < 6; ++c) out[((long long)b * Tmax + n) * 6 + c] = last[c];
-            ++n;
-        }
-        if (seg1 >= end) break;
-        seg0 = seg1 + 1;
-    }
-    n_steps[b] = n;
+    n_steps[b] = traj_scan(r, L, nb, p0, tsep, eos, Tmax,
+        [&](int hit) { for (int c = 0; c < 6; ++c) last[c] = (float)bins[(int)(r[hit + c] - p0)]; },
+        [&](int n) { for (int c = 0; c < 6; ++c) out[((long long)b * Tmax + n) * 6 + c] = last[c]; });
 }
 
-// traj_detokenize_kernel's scan (cut at the first eos, split on <tsep>, first run of six bin ids per segment, copy-forward), gathering
-// the per-token statistics of egomi_bin_stats instead of bin centres: a step parsed from ids hit .. hit+5 takes mean / std of columns
-// hit .. hit+5 and, with bin_mass, the smallest of their six masses; a copied step repeats all three.  n_steps is that kernel's.
+// the same scan, gathering the per-token statistics of egomi_bin_stats instead of bin centres: a step parsed from ids hit .. hit+5 takes
+// mean / std of columns hit .. hit+5 and, with bin_mass, the smallest of their six masses; a copied step repeats all three.
 __global__ __launch_bounds__(64) void traj_detokenize_soft_kernel(const int64_t* ids, int B, int L, int nb, int64_t p0, int64_t tsep, int64_t eos,
                                                                   const float* bin_mean, const float* bin_std, const float* bin_mass,
                                                                   long long ld_stat, int Tmax, float* mean, float* std, float* mass,
                                                                   int32_t* n_steps) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const int64_t* r = ids + (long long)b * L;
     const long long sr = (long long)b * ld_stat;
-    int n = 0, end = L;
-    for (int j = 0; j < L; ++j) if (r[j] == eos) { end = j; break; }
-    int seg0 = 0;
-    bool have_last = false;
     float lm[6], ls[6], lmass = 0.f;
-    while (seg0 <= end && n < Tmax) {
-        int seg1 = seg0;
-        while (seg1 < end && r[seg1] != tsep) ++seg1;
-        int run = 0, hit = -1;
-        for (int j = seg0; j < seg1; ++j) {
-            if (r[j] >= p0 && r[j] < p0 + nb) { if (++run == 6) { hit = j - 5; break; } } else run = 0;
-        }
-        if (hit >= 0) {
+    n_steps[b] = traj_scan(ids + (long long)b * L, L, nb, p0, tsep, eos, Tmax,
+        [&](int hit) {
             for (int c = 0; c < 6; ++c) { lm[c] = bin_mean[sr + hit + c]; ls[c] = bin_std[sr + hit + c]; }
             if (bin_mass) {
                 lmass = bin_mass[sr + hit];
                 for (int c = 1; c < 6; ++c) { const float x = bin_mass[sr + hit + c]; lmass = (x < lmass || x != x) ? x : lmass; }   // a NaN mass wins
             }
-            have_last = true;
-        }
-        if (hit >= 0 || have_last) {
+        },
+        [&](int n) {
             for (int c = 0; c < 6; ++c) {
                 mean[((long long)b * Tmax + n) * 6 + c] = lm[c];
                 std[((long long)b * Tmax + n) * 6 + c] = ls[c];
             }
             if (mass) mass[(long long)b * Tmax + n] = lmass;
-            ++n;
-        }
-        if (seg1 >= end) break;
-        seg0 = seg1 + 1;
-    }
-    n_steps[b] = n;
+        });
 }
 
-// per sample: gen padded with its last step / cut to len_gt (metrics.py:40-52), then
-// ade = mean_t ||gt_t - gen_t||_2, fde = ||gt_last - gen_last||_2 over all D dims (float64 like numpy)
+// per sample: ADE / FDE of gen against gt (traj_disp.h: traj_ade_fde, float64 like numpy); NaN when either holds no step
 __global__ __launch_bounds__(64) void traj_metrics_kernel(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int Tmax,
                                                           int D, double* ade, double* fde) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const int ng = n_gen ? n_gen[b] : Tmax, nt = n_gt ? n_gt[b] : Tmax;
+    const int ng = traj_len(n_gen, b, Tmax), nt = traj_len(n_gt, b, Tmax);
     if (ng <= 0 || nt <= 0) { ade[b] = NAN; fde[b] = NAN; return; }
-    double acc = 0.0, lastd = 0.0;
-    for (int t = 0; t < nt; ++t) {
-        const int tg = t < ng ? t : ng - 1;
-        lastd = traj_step_dist(gt + ((long long)b * Tmax + t) * D, gen + ((long long)b * Tmax + tg) * D, D);
-        acc += lastd;
-    }
-    ade[b] = acc / nt;
-    fde[b] = lastd;
+    traj_ade_fde(gt + (long long)b * Tmax * D, nt, gen + (long long)b * Tmax * D, ng, D, ade[b], fde[b]);
 }
 
 // best of K: gen [B, K, Tmax, D], n_gen [B, K]; per clip the minimum ADE and the minimum FDE over the samples with n_gen > 0 (each
@@ -149,22 +127,16 @@ __global__ __launch_bounds__(64) void traj_metrics_min_kernel(const float* gen, 
                                                               int Tmax, int D, double* min_ade, double* min_fde, int32_t* best) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const int nt = n_gt ? n_gt[b] : Tmax;
+    const int nt = traj_len(n_gt, b, Tmax);
     double ba = NAN, bf = NAN;
     int bi = -1;
     for (int j = 0; j < K && nt > 0; ++j) {
-        const int ng = n_gen ? n_gen[(long long)b * K + j] : Tmax;
+        const int ng = traj_len(n_gen, (long long)b * K + j, Tmax);
         if (ng <= 0) continue;
-        const float* g = gen + ((long long)b * K + j) * Tmax * D;
-        double acc = 0.0, lastd = 0.0;
-        for (int t = 0; t < nt; ++t) {
-            const int tg = t < ng ? t : ng - 1;
-            lastd = traj_step_dist(gt + ((long long)b * Tmax + t) * D, g + (long long)tg * D, D);
-            acc += lastd;
-        }
-        const double ade = acc / nt;
+        double ade, fde;
+        traj_ade_fde(gt + (long long)b * Tmax * D, nt, gen + ((long long)b * K + j) * Tmax * D, ng, D, ade, fde);
         if (bi < 0 || ade < ba) { ba = ade; bi = j; }
-        if (!(bf <= lastd)) bf = lastd;                                    // first sample (bf NaN) or a smaller FDE
+        if (!(bf <= fde)) bf = fde;                                        // first sample (bf NaN) or a smaller FDE
     }
     min_ade[b] = ba;
     min_fde[b] = bf;
@@ -172,9 +144,8 @@ __global__ __launch_bounds__(64) void traj_metrics_min_kernel(const float* gen, 
 }
 
 // medoid of K: gen [B, K, Tmax, D], n_gen [B, K] or NULL (= Tmax); sample j is valid when n_gen > 0 (traj_metrics_min_kernel's rule).
-// d(j, i) = mean over t < max(n_j, n_i) of ||g_j[min(t, n_j - 1)] - g_i[min(t, n_i - 1)]||_2 over all D dims: each sample padded with its
-// own last step, as traj_metrics_kernel pads (bit-symmetric in j, i).  cost[b, j] = mean of d(j, i) over the valid i != j, float64, summed in
-// index order; one valid sample: 0; invalid j: NaN.  pick[b] = arg-min of cost over the valid samples (lowest index on ties), none: -1.
+// cost[b, j] = mean of d(j, i) (traj_disp.h: traj_pair_dist, traj_modes_kernel's matrix) over the valid i != j, float64, summed in index
+// order; one valid sample: 0; invalid j: NaN.  pick[b] = arg-min of cost over the valid samples (lowest index on ties), none: -1.
 // One workgroup per clip, one thread per sample j.
 #define MED_THREADS 256
 #define MED_MAXK 1024
@@ -184,30 +155,15 @@ __global__ __launch_bounds__(MED_THREADS) void traj_medoid_kernel(const float* g
     const int b = blockIdx.x;
     const float* gb = gen + (long long)b * K * Tmax * D;
     for (int j = threadIdx.x; j < K; j += MED_THREADS) {
-        int nj = n_gen ? n_gen[(long long)b * K + j] : Tmax;
-        nj = nj > Tmax ? Tmax : nj;
+        const int nj = traj_len(n_gen, (long long)b * K + j, Tmax);
         double c = NAN;
         if (nj > 0) {
-            const float* gj = gb + (long long)j * Tmax * D;
             double tot = 0.0;
             int others = 0;
             for (int i = 0; i < K; ++i) {
-                int ni = n_gen ? n_gen[(long long)b * K + i] : Tmax;
-                ni = ni > Tmax ? Tmax : ni;
+                const int ni = traj_len(n_gen, (long long)b * K + i, Tmax);
                 if (i == j || ni <= 0) continue;
-                const float* gi = gb + (long long)i * Tmax * D;
-                const int n = nj > ni ? nj : ni;
-                double acc = 0.0;
-                for (int t = 0; t < n; ++t) {
-                    const int tj = t < nj ? t : nj - 1, ti = t < ni ? t : ni - 1;
-                    double s = 0.0;
-                    for (int d = 0; d < D; ++d) {
-                        const double df = (double)gj[(long long)tj * D + d] - (double)gi[(long long)ti * D + d];
-                        s += df * df;
-                    }
-                    acc += sqrt(s);
-                }
-                tot += acc / n;
+                tot += traj_pair_dist(gb + (long long)j * Tmax * D, nj, gb + (long long)i * Tmax * D, ni, D);
                 ++others;
             }
             c = others ? tot / others : 0.0;

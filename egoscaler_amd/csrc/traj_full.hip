@@ -56,8 +56,7 @@ __global__ __launch_bounds__(FULL_THREADS) void traj_metrics_full_kernel(const f
                                                                          const int32_t* n_gt, int K, int Tmax, int D, int rot0, double* out,
                                                                          double* mins, int32_t* args) {
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int nt = n_gt ? n_gt[b] : Tmax;
-    nt = nt > Tmax ? Tmax : nt;
+    const int nt = traj_len(n_gt, b, Tmax);
     const float* gtb = gt + (long long)b * Tmax * D;
     for (int i = threadIdx.x; i < nt * D; i += FULL_THREADS) full_gt[i] = gtb[i];      // nothing of gt beyond its nt rows is read
     __syncthreads();
@@ -65,8 +64,7 @@ __global__ __launch_bounds__(FULL_THREADS) void traj_metrics_full_kernel(const f
     const double inf = HUGE_VAL;
 
     for (int j = wave; j < K; j += FULL_WAVES) {                                         // wave-uniform: every lane of a wave runs one sample
-        int ng = n_gen ? n_gen[(long long)b * K + j] : Tmax;
-        ng = ng > Tmax ? Tmax : ng;
+        const int ng = traj_len(n_gen, (long long)b * K + j, Tmax);
         double* o = out + ((long long)b * K + j) * FULL_COLS;
         if (ng <= 0 || nt <= 0) {
             if (lane < FULL_COLS) o[lane] = NAN;

@@ -82,6 +82,16 @@ def detokenize_soft(ids: torch.Tensor, tok, max_steps: int, bin_mean, bin_std, b
     return mean, std, mass, n
 
 
+def _lens(n, dev, shape=None):
+    """A step-count argument as the kernels read it: None (every sample is full length), or int32, contiguous, on `dev`; of `shape`
+    [B,K] where one is given.  A count beyond the buffer's T steps counts as T (csrc/traj_disp.h: traj_len)."""
+    if n is None:
+        return None
+    if shape is not None and tuple(n.shape) != shape:
+        raise ValueError("n_gen must be [B,K]")
+    return n.to(device=dev, dtype=torch.int32).contiguous()
+
+
 def metrics_batch(gen, n_gen, gt, n_gt=None):
     """ADE / FDE per sample (float64), generated trajectories padded with their last step or cut to
     the ground-truth length (models/utils/metrics.py:40-52)."""
@@ -92,9 +102,7 @@ def metrics_batch(gen, n_gen, gt, n_gt=None):
     dev = gt.device
     ade = torch.empty(B, dtype=torch.float64, device=dev)
     fde = torch.empty(B, dtype=torch.float64, device=dev)
-    ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
-    nt = None if n_gt is None else n_gt.to(torch.int32).contiguous()
-    call("egomi_traj_metrics", gen, ng, gt, nt, B, T, D, ade, fde, S())
+    call("egomi_traj_metrics", gen, _lens(n_gen, dev), gt, _lens(n_gt, dev), B, T, D, ade, fde, S())
     return ade, fde
 
 
@@ -110,14 +118,11 @@ def metrics_best_of(gen, n_gen, gt, n_gt=None):
     K = gen.shape[1]
     if K < 1:
         raise ValueError("gen holds no sample")
-    if n_gen is not None and tuple(n_gen.shape) != (B, K):
-        raise ValueError("n_gen must be [B,K]")
     dev = gt.device
+    ng, nt = _lens(n_gen, dev, (B, K)), _lens(n_gt, dev)
     min_ade = torch.empty(B, dtype=torch.float64, device=dev)
     min_fde = torch.empty(B, dtype=torch.float64, device=dev)
     best = torch.empty(B, dtype=torch.int32, device=dev)
-    ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
-    nt = None if n_gt is None else n_gt.to(torch.int32).contiguous()
     call("egomi_traj_metrics_min", gen, ng, gt, nt, B, K, T, D, min_ade, min_fde, best, S())
     return min_ade, min_fde, best
 
@@ -148,16 +153,13 @@ def metrics_full(gen, n_gen, gt, n_gt=None, rot0=3):
     K = gen.shape[1]
     if K < 1:
         raise ValueError("gen holds no sample")
-    if n_gen is not None and tuple(n_gen.shape) != (B, K):
-        raise ValueError("n_gen must be [B,K]")
+    dev = gt.device
+    ng, nt = _lens(n_gen, dev, (B, K)), _lens(n_gt, dev)
     if T > FULL_MAX_STEPS:
         raise ValueError(f"metrics_full serves T <= {FULL_MAX_STEPS} steps, not {T}")
-    dev = gt.device
     out = torch.empty(B, K, len(FULL_METRICS), dtype=torch.float64, device=dev)
     mins = torch.empty(B, len(FULL_METRICS), dtype=torch.float64, device=dev)
     args = torch.empty(B, len(FULL_METRICS), dtype=torch.int32, device=dev)
-    ng = None if n_gen is None else n_gen.to(device=dev, dtype=torch.int32).contiguous()
-    nt = None if n_gt is None else n_gt.to(device=dev, dtype=torch.int32).contiguous()
     call("egomi_traj_metrics_full", gen, ng, gt, nt, B, K, T, D, int(rot0), out, mins, args, S())
     cols = out[:, 0] if single else out
     return FullMetrics(*(cols[..., m] for m in range(len(FULL_METRICS))), mins, args)
@@ -173,12 +175,10 @@ def select_medoid(gen, n_gen=None):
     if gen.dim() != 4 or gen.shape[1] < 1:
         raise ValueError("gen must be [B,K,T,D] with K >= 1")
     B, K, Tn, D = gen.shape
-    if n_gen is not None and tuple(n_gen.shape) != (B, K):
-        raise ValueError("n_gen must be [B,K]")
     dev = gen.device
+    ng = _lens(n_gen, dev, (B, K))
     cost = torch.empty(B, K, dtype=torch.float64, device=dev)
     pick = torch.empty(B, dtype=torch.int32, device=dev)
-    ng = None if n_gen is None else n_gen.to(torch.int32).contiguous()
     call("egomi_traj_medoid", gen, ng, B, K, Tn, D, cost, pick, S())
     return pick, cost
 
@@ -216,8 +216,7 @@ def select_modes(gen, n_gen=None, scores=None, num_modes=6, radius=0.0, return_d
         raise ValueError(f"select_modes serves K <= 64 samples per clip, not {K}")
     if not 1 <= M <= 64:
         raise ValueError(f"num_modes must be in 1 .. 64, not {num_modes}")
-    if n_gen is not None and tuple(n_gen.shape) != (B, K):
-        raise ValueError("n_gen must be [B,K]")
+    ng = _lens(n_gen, gen.device, (B, K))
     if scores is not None and tuple(scores.shape) != (B, K):
         raise ValueError("scores must be [B,K]")
     radius = float(radius)
@@ -230,7 +229,6 @@ def select_modes(gen, n_gen=None, scores=None, num_modes=6, radius=0.0, return_d
     n_modes = torch.empty(B, dtype=torch.int32, device=dev)
     n_nms = torch.empty(B, dtype=torch.int32, device=dev)
     dist = torch.empty(B, K, K, dtype=torch.float64, device=dev) if return_dist else None
-    ng = None if n_gen is None else n_gen.to(device=dev, dtype=torch.int32).contiguous()
     sc = None if scores is None else scores.to(device=dev, dtype=torch.float32).contiguous()
     call("egomi_traj_modes", gen, ng, sc, B, K, Tn, D, M, radius, dist, modes, conf, assign, n_modes, n_nms, S())
     out = (modes, conf, assign, n_modes, n_nms)

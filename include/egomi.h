@@ -509,7 +509,8 @@ int egomi_lora_wgrad(const void* l, int64_t ldl, const void* r, int64_t ldr, flo
  *               <ts> (p*6 <tsep>) x steps <te> <eos> pad..., mask u8 [B,L]; err[b]=1 if L is too short
  *               (sequence truncated to whole steps).  bin = clamp(digitize(v)-1, 0, num_bins-1).
  *   detokenize: ids i64 [B,L] (cut at the first eos) -> out f32 [B,Tmax,6] bin values, n_steps i32 [B]
- *   metrics   : gen/gt f32 [B,Tmax,D] with lengths (NULL = Tmax) -> ade, fde float64 [B]
+ *   metrics   : gen/gt f32 [B,Tmax,D] with lengths (NULL = Tmax; a length above Tmax counts as Tmax, as in every trajectory entry
+ *               point: nothing past a buffer is read) -> ade, fde float64 [B]; NaN, NaN when either length is <= 0
  */
 int egomi_traj_tokenize(const float* traj, const int32_t* steps, int B, int Tmax, const double* bins, int num_bins, int64_t p0,
                         int64_t ts, int64_t tsep, int64_t te, int64_t eos, int64_t pad, int L, int64_t* ids, uint8_t* mask,
@@ -529,8 +530,8 @@ int egomi_traj_detokenize_soft(const int64_t* ids, int B, int L, int num_bins, i
 int egomi_traj_metrics(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int Tmax, int D, double* ade,
                        double* fde, egomi_stream_t stream);
 /* metrics_min: best-of-K (minADE_K / minFDE_K; the reference's run_validation, train.py:207-264, scores one draw per clip with
- *              models/utils/metrics.py:7-55).  gen f32 [B,K,Tmax,D], n_gen i32 [B,K] (NULL = Tmax), gt f32 [B,Tmax,D], n_gt i32 [B] (NULL = Tmax)
- *              -> min_ade, min_fde float64 [B], best i32 [B].  Every sample is scored as `metrics` scores it; samples with n_gen <= 0 take no
+ *              models/utils/metrics.py:7-55).  gen f32 [B,K,Tmax,D], n_gen i32 [B,K] (NULL = Tmax), gt f32 [B,Tmax,D], n_gt i32 [B] (NULL = Tmax);
+ *              lengths above Tmax count as Tmax -> min_ade, min_fde float64 [B], best i32 [B].  Every sample is scored as `metrics` scores it; samples with n_gen <= 0 take no
  *              part; best = arg-min ADE (lowest index on ties); min_fde is the minimum over the samples, not the FDE of `best`; no sample
  *              left (or n_gt <= 0): NaN, NaN, -1. */
 int egomi_traj_metrics_min(const float* gen, const int32_t* n_gen, const float* gt, const int32_t* n_gt, int B, int K, int Tmax, int D,

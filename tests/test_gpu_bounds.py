@@ -5,7 +5,7 @@ past such an operand leaves its mapped segment (a fault), and results are compar
 (a stray read that lands in mapped memory but feeds a result shows there).  Families: fused attention forward / backward (q|k|v, out, dout,
 dq|dk|dv, LSE, delta, key mask), the K-contiguous GEMMs (256x256 8-phase, 128x128, the M <= 256 ring kernel, the M <= 16 weight-streaming kernel: A, B, C), the k-major 8-phase
 GEMM (weight- and data-gradient forms, a column-sliced operand whose width is not a multiple of 256: ADVICE r3), the decode attention's K/V
-cache.  One parametrised test per family; run once."""
+cache.  One parametrised test per family; run once.  Last, the trajectory metrics with step counts beyond their buffers (clamped)."""
 import math
 
 import pytest
@@ -159,3 +159,23 @@ def test_decode_attention_cache_at_the_end_of_its_allocation(ops, T_len, Smax):
     sc = sc.masked_fill(~km0[:, None, None, :T_len].bool(), float("-inf"))
     ref = (torch.softmax(sc, -1) @ vc0.float()[:, :, :T_len]).reshape(B, d)
     assert float((res[1].float() - ref).abs().max()) <= 2e-2 * float(ref.abs().max())
+
+
+@pytest.mark.parametrize("call", ["metrics_batch", "metrics_best_of"])
+def test_trajectory_metrics_clamp_step_counts_to_the_buffer(call):
+    """n_gen / n_gt beyond Tmax count as Tmax (csrc/traj_disp.h: traj_len): with gen and gt each ending an allocation, entries of Tmax + 3
+    give the bits of entries of Tmax, and nothing past either buffer is read."""
+    from egoscaler_amd import traj as T
+    B, K, Tm, D = 3, 2, 5, 6
+    gs = (B, Tm, D) if call == "metrics_batch" else (B, K, Tm, D)
+    keep = []
+    gen, gt = at_end(rnd(*gs, seed=1, dtype=torch.float32).cuda(), keep), at_end(rnd(B, Tm, D, seed=2, dtype=torch.float32).cuda(), keep)
+    n_gen = torch.tensor([[Tm, 2], [1, Tm], [Tm, Tm]], dtype=torch.int32, device="cuda")
+    n_gen = n_gen[:, 0].contiguous() if call == "metrics_batch" else n_gen
+    n_gt = torch.tensor([Tm, 3, Tm], dtype=torch.int32, device="cuda")
+    over = lambda n: torch.where(n == Tm, n + 3, n)
+    fn = getattr(T, call)
+    ref, got = fn(gen, n_gen, gt, n_gt), fn(gen, over(n_gen), gt, over(n_gt))
+    torch.cuda.synchronize()
+    for a, b in zip(ref, got):
+        assert torch.equal(a, b) and bool(torch.isfinite(a.double()).all())

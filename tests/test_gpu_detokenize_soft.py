@@ -87,6 +87,33 @@ def test_one_hot_statistics_give_the_hard_trajectory_and_the_rest_gathers(dims, 
     assert none is None and torch.equal(m2, mean) and torch.equal(s2, std) and torch.equal(n2, n)
 
 
+def test_hard_and_soft_scan_agree_on_the_edge_rows():
+    """Both kernels are one scan (csrc/traj.hip: traj_scan): a row with no eos, a row whose first id is the eos, and a row whose first
+    segment has no run of six bin ids (copy-forward with nothing to copy yet).  L = 20, Tmax = 4."""
+    tok, L, tmax, text = dims_tiny().tok, 20, 4, 3
+    g = np.random.default_rng(20)
+    step = lambda: list(tok.p0 + g.integers(0, tok.num_bins, 6))
+    noise = lambda k: list(g.integers(0, tok.p0 + tok.num_bins, k))
+    rows = [step() + [tok.tsep] + step() + [tok.tsep] + step()[:5] + [text],                      # no eos: the row's end closes a broken segment
+            [tok.eos] + noise(L - 1),                                                               # eos first: nothing is read
+            step()[:3] + [text] + step()[:2] + [tok.tsep] + step() + [tok.tsep, tok.te, tok.eos] + noise(4)]
+    rows[0] = [t if t != tok.eos else text for t in rows[0]]
+    assert all(len(r) == L for r in rows)
+    ids = torch.tensor(np.array(rows, dtype=np.int64)).cuda()
+    hard, n_hard = T.detokenize_batch(ids, tok, tmax)
+    values = T.bin_edges(tok.num_bins, "cuda")
+    isbin = (ids >= tok.p0) & (ids < tok.p0 + tok.num_bins)
+    tg = torch.Generator().manual_seed(20)
+    bin_mean, bin_std, bin_mass = (torch.rand(3, L, generator=tg).cuda() for _ in range(3))
+    bin_mean = torch.where(isbin, values[(ids - tok.p0).clamp(0, tok.num_bins - 1)].float(), bin_mean)
+    mean, std, mass, n = T.detokenize_soft(ids, tok, tmax, bin_mean, bin_std, bin_mass)
+    assert torch.equal(n, n_hard) and torch.equal(mean, hard)
+    assert n.tolist() == [3, 0, 2]
+    rm, rs, rmass, rn = _scan(ids.cpu().numpy(), tok, bin_mean.cpu().numpy(), bin_std.cpu().numpy(), bin_mass.cpu().numpy(), tmax)
+    assert np.array_equal(n.cpu().numpy(), rn)
+    assert np.array_equal(mean.cpu().numpy(), rm) and np.array_equal(std.cpu().numpy(), rs) and np.array_equal(mass.cpu().numpy(), rmass)
+
+
 def test_rejected_inputs():
     tok = dims_tiny().tok
     ids = _rows(tok, 2, 20).cuda()

@@ -161,6 +161,43 @@ def test_lengths_ragged_per_sample(K, Tm, D):
             assert np.array_equal(_run(gen, n, None, 1, 0.0)[0][:, 0], pick.cpu().numpy())
 
 
+@pytest.mark.parametrize("D", [1, 6])
+@pytest.mark.parametrize("Tm", [1, 7])
+@pytest.mark.parametrize("K", [1, 2, 3, 64])
+def test_medoid_cost_is_the_index_order_mean_of_a_row_of_dist(K, Tm, D):
+    """select_medoid's cost from select_modes' dist, bit for bit: both kernels call one pairwise distance (csrc/traj_disp.h), so
+    cost[b, j] is the float64 sum of dist[b, j, i] over the valid i != j in index order, divided once; 0 with no other valid sample, NaN
+    for an invalid j.  Clip 0 ragged lengths (0 included), clip 1 one valid sample, clip 2 none, clip 3 two identical samples."""
+    g = np.random.default_rng(100 * K + 10 * Tm + D)
+    gen = g.normal(0, 1, (4, K, Tm, D)).astype(np.float32)
+    n = g.integers(0, Tm + 1, (4, K)).astype(np.int32)
+    n[0, 0] = 0
+    n[1, :], n[1, K - 1] = 0, Tm
+    n[2, :] = 0
+    n[3, :] = np.maximum(n[3, :], 1)
+    if K >= 2:
+        gen[3, K - 1], n[3, K - 1] = gen[3, 0], n[3, 0]
+    dist = _run(gen, n, None, 1, 0.0)[5]
+    pick, cost = T.select_medoid(torch.tensor(gen).cuda(), torch.tensor(n).cuda())
+    cost = cost.cpu().numpy()
+    ref = np.full((4, K), np.nan)
+    for b in range(4):
+        valid = [j for j in range(K) if n[b, j] > 0]
+        assert valid == [j for j in range(K) if not np.isnan(dist[b, j, j])]
+        for j in valid:
+            tot, others = 0.0, 0
+            for i in valid:
+                if i != j:
+                    tot, others = tot + float(dist[b, j, i]), others + 1
+            ref[b, j] = tot / others if others else 0.0
+    assert np.array_equal(np.isnan(cost), np.isnan(ref))
+    ok = ~np.isnan(ref)
+    assert np.array_equal(_bits(cost[ok]), _bits(ref[ok]))
+    assert cost[1, K - 1] == 0.0 and np.isnan(cost[2]).all() and pick.cpu().tolist()[1:3] == [K - 1, -1]
+    if K >= 2:
+        assert dist[3, 0, K - 1] == 0.0 and _bits(cost[3, :1]) == _bits(cost[3, K - 1:])
+
+
 @pytest.mark.parametrize("K", [3, 16, 33])
 def test_edge_radii(K):
     Tm, D = 7, 6
