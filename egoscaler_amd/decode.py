@@ -157,6 +157,46 @@ def bin_window(bin_token_ids, V):
     return p0, nb
 
 
+GRAMMAR_FIELDS = ("p0", "nb", "ts", "tsep", "te", "eos", "min_steps", "max_steps")
+
+
+def grammar_check(spec, V):
+    """The eight integers (GRAMMAR_FIELDS) of a trajectory grammar spec (traj.grammar_spec), checked against a vocabulary of V ids
+    (the limits of egomi_traj_grammar_step, raised before any launch)."""
+    try:
+        g = tuple(int(getattr(spec, f)) for f in GRAMMAR_FIELDS) if hasattr(spec, "p0") else tuple(int(v) for v in spec)
+        p0, nb, ts, tsep, te, eos, mn, mx = g
+    except (TypeError, ValueError, AttributeError):
+        raise ValueError(f"a trajectory grammar is traj.grammar_spec(tok, min_steps, max_steps), not {spec!r}") from None
+    if not 1 <= nb <= 1024 or p0 < 0 or p0 + nb > V:
+        raise ValueError(f"grammar: the bin window ({p0}, {nb}) is not 1 .. 1024 ids inside the vocabulary of {V}")
+    sp = (ts, tsep, te, eos)
+    if any(not 0 <= s < V or p0 <= s < p0 + nb for s in sp) or len(set(sp)) != 4:
+        raise ValueError(f"grammar: <ts>, <tsep>, <te>, eos = {sp} must be four different ids of the vocabulary of {V} outside the bin window")
+    if not 0 <= mn <= mx:
+        raise ValueError(f"grammar: 0 <= min_steps <= max_steps does not hold for ({mn}, {mx})")
+    return g
+
+
+def traj_grammar_init(ids, mask, spec, state, need):
+    """The grammar state every prompt row leaves and the tokens it needs to close (include/egomi.h egomi_traj_grammar_init): ids int64
+    [R, S0] and mask uint8 [R, S0] or None (views with a row stride are fine) -> state int32 [R, 2], need int32 [R]."""
+    R, S0 = ids.shape
+    p0, nb, ts, tsep, te, eos, mn, mx = spec
+    call("egomi_traj_grammar_init", ids, ids.stride(0), mask, mask.stride(0) if mask is not None else 0, R, S0, p0, nb, ts, tsep, te, eos, mn, mx,
+         state, need, S())
+
+
+def traj_grammar_step(logits, tok_prev, state, spec, rem, mass, col):
+    """One step of the trajectory grammar, in place on `logits` [R, V] (include/egomi.h egomi_traj_grammar_step): the state advances by
+    tok_prev (None at step 0), mass[:, col] = the raw probability of the allowed set, and every other id becomes -inf.  rem = the tokens
+    the loop still emits, this one included."""
+    R, V = logits.shape
+    p0, nb, ts, tsep, te, eos, mn, mx = spec
+    call("egomi_traj_grammar_step", logits, logits.stride(0), R, V, tok_prev, state, p0, nb, ts, tsep, te, eos, mn, mx, rem, mass, mass.stride(0),
+         col, dt(logits.dtype), S())
+
+
 def seq_rank(sum_lp, n_tok, B, K, length_penalty=1.0):
     """Per clip, the K rows b * K + j by descending sum_lp / n_tok ** length_penalty (include/egomi.h egomi_seq_rank):
     -> (score fp32 [B, K], order int32 [B, K])."""
@@ -412,6 +452,7 @@ class Decoder:
         self.lp_tok = self.lp_sum = self.lp_n = self.lp_live = None      # sample() / greedy() with logprobs=True: made on first use (_lp_buffers)
         self.bs_mass = self.bs_mean = self.bs_std = self.bs_ent = None   # sample() / greedy() / score() with bin_stats=(p0, nb) (_bs_buffers)
         self._bs_values = {}
+        self.gr_state = self.gr_need = self.gr_mass = None               # sample() / greedy() with grammar=spec (_grammar)
         self._score_act = None                              # score(): the activations of a suffix pass, made on first use (_score_buffers)
         self.kv_row = None                                  # beam mode: [B, Smax] int32, physical cache row of every key of every logical row
         if self.nb > 1:
@@ -482,6 +523,33 @@ class Decoder:
             from .traj import bin_edges
             self._bs_values[nb] = bin_edges(nb, dev)
         return p0, nb, self._bs_values[nb], (self.bs_mass, self.bs_mean, self.bs_std, self.bs_ent)
+
+    def _grammar(self, grammar, T_new):
+        """The trajectory grammar of sample() / greedy() with grammar=spec: its static buffers, made on first use -- gr_state int32 [B, 2]
+        (phase, steps per row), gr_need int32 [B] (the tokens the prompt row needs to close: a row with gr_need <= T_new ends `<te> eos`
+        inside the loop, any other may not; the caller checks), gr_mass fp32 [B, max_len] (column t = the raw probability of step t's allowed
+        set) -- and -> (head, mask, key).  head() queues egomi_traj_grammar_init on the prompt in self.seq / self.mask: the token loop
+        starts with it, inside the captured graph, so every replay starts from the state of the prompt that is in the static buffers then,
+        not from where the last replay ended.  mask(t) queues step t's egomi_traj_grammar_step on self.lg, directly before the token
+        kernel.  key: what the grammar adds to a graph key (the spec with its step limits).  None: no launch, no buffer, () as key."""
+        if grammar is None:
+            return (lambda: None), (lambda t: None), ()
+        if self.nb > 1:
+            raise ValueError("a trajectory grammar is for num_beams == 1: the beams of an item share one prefill logits row at step 0")
+        spec = grammar_check(grammar, self.lg.shape[1])
+        if self.gr_state is None:
+            dev = self.eng.device
+            self.gr_state = torch.zeros(self.B, 2, dtype=torch.int32, device=dev)
+            self.gr_need = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.gr_mass = torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev)
+        S0 = self.pos
+
+        def head():
+            traj_grammar_init(self.seq_buf[:, :S0], self.mask_buf[:, :S0], spec, self.gr_state, self.gr_need)
+
+        def mask(t):
+            traj_grammar_step(self.lg, None if t == 0 else self.tok.view(-1), self.gr_state, spec, T_new - t, self.gr_mass, t)
+        return head, mask, ("grammar",) + spec
 
     def _readouts(self, logprobs, bin_stats, eos):
         """The per-step readouts of sample() / greedy() / score(): prepares their buffers (_lp_buffers, _bs_buffers) and -> (emit, key).
@@ -686,7 +754,7 @@ class Decoder:
         return self._scores[T_new]
 
     def sample(self, T_new, do_sample=True, temperature=1.0, top_k=50, top_p=0.95, repetition_penalty=1.0, eos=None, pad=None, seed=None,
-               use_graph=True, logprobs=False, bin_stats=None):
+               use_graph=True, logprobs=False, bin_stats=None, grammar=None):
         """After prefill(): T_new steps of HF generate's token loop (model_arch.py:82-108 -> GenerationMixin: logits processors, warpers,
         multinomial / arg-max, eos bookkeeping), every step one egomi_sample_rows launch + one cached decode step, all of them captured
         into ONE hipGraph (the draw counter and `pos` are launch constants, seed and done flags live in device memory).
@@ -696,8 +764,17 @@ class Decoder:
         the pads not).  A graph of its own (the flag is part of the key); with False the loop has the launches it had.
         bin_stats=(p0, nb): every step also runs one egomi_bin_stats launch on the raw logits, after those: self.bs_mass / bs_mean / bs_std /
         bs_ent[:, t] describe the distribution token t was chosen from, over the bin ids p0 .. p0 + nb - 1 (values linspace(-1, 1, nb)); rows
-        that have finished are computed like any other (the caller cuts at the eos).  Again a graph of its own; None: no launch, no buffer."""
+        that have finished are computed like any other (the caller cuts at the eos).  Again a graph of its own; None: no launch, no buffer.
+        grammar=spec (traj.grammar_spec; num_beams == 1): constrained decoding.  The loop starts with one egomi_traj_grammar_init launch on
+        the prompt, and every step runs one egomi_traj_grammar_step launch directly before the token kernel (csrc/grammar.hip; _grammar):
+        in place on self.lg, every id the row's grammar state does not allow becomes -inf, and self.gr_mass[:, t] keeps the raw probability
+        the model gave the allowed set.  Everything downstream then sees the CONSTRAINED row: the returned scores are the processed scores
+        of the constrained distribution, and logprobs / bin_stats describe that same renormalised distribution -- the one the token was
+        drawn from, a proper distribution over valid trajectories; the raw signal survives in gr_mass alone.  A row with
+        self.gr_need <= T_new ends `<te> eos` with min_steps <= n <= max_steps.  A graph of its own (the spec and its limits are part of the
+        key); None: the loop has the launches it had."""
         emit, readout_key = self._readouts(logprobs, bin_stats, eos)
+        gr_head, gr_mask, gr_key = self._grammar(grammar, T_new)
         S0, sc_buf = self.pos, self._score_buf(T_new)
         self._seed(seed)
         self.done_buf.zero_()
@@ -706,28 +783,35 @@ class Decoder:
                   top_p=float(1.0 if top_p is None else top_p), do_sample=bool(do_sample), rng=self.rng, eos=eos, pad=pad)
 
         def steps():
+            gr_head()
             for t in range(T_new):
+                gr_mask(t)
                 sample_rows(self.lg, sc_buf[t], self.seq, S0 + t, 0, self.tok.view(-1), self.done, draw=t, **kw)
                 emit(self.lg, self.tok.view(-1), t)
                 if t + 1 < T_new:
                     self.step(S0 + t)
         key = (S0, T_new, kw["repetition_penalty"], kw["temperature"], kw["top_k"], kw["top_p"], kw["do_sample"], eos, pad)
-        self._run(steps, use_graph, key + readout_key)
+        self._run(steps, use_graph, key + readout_key + gr_key)
         self.pos = S0 + T_new
         return self.seq, sc_buf
 
-    def greedy(self, T_new, use_graph=True, keep_scores=True, logprobs=False, bin_stats=None):
+    def greedy(self, T_new, use_graph=True, keep_scores=True, logprobs=False, bin_stats=None, grammar=None):
         """After prefill(): T_new greedy tokens.  Returns (sequences [B,S0+T], scores list or None).  logprobs=True: one egomi_token_logprob
         launch per step after the arg-max, into self.lp_tok / lp_sum / lp_n as in sample() (no eos here: every row counts every step).
-        bin_stats=(p0, nb): one egomi_bin_stats launch per step after those, into self.bs_mass / bs_mean / bs_std / bs_ent as in sample()."""
+        bin_stats=(p0, nb): one egomi_bin_stats launch per step after those, into self.bs_mass / bs_mean / bs_std / bs_ent as in sample().
+        grammar=spec: as in sample(): the init launch before the loop and one egomi_traj_grammar_step launch per step before the scores
+        are kept and the arg-max runs, so scores, logprobs and bin_stats are those of the constrained row; self.gr_mass / gr_need as there."""
         emit, _ = self._readouts(logprobs, bin_stats, None)
+        gr_head, gr_mask, _ = self._grammar(grammar, T_new)
         S0 = self.pos
         scores = None                                       # eager: fp32 clones; captured: views of one buffer the graph writes
         if keep_scores:
             scores = list(torch.zeros(T_new, self.B, self.lg.shape[1], dtype=torch.float32, device=self.eng.device)) if use_graph else []
 
         def steps():
+            gr_head()
             for t in range(T_new):
+                gr_mask(t)
                 if keep_scores and use_graph:
                     ops.cast(self.lg, torch.float32, out=scores[t])
                 elif keep_scores:
@@ -847,11 +931,13 @@ class Decoder:
         self._cands = {}
 
     def beam(self, T_new, num_return_sequences=1, length_penalty=1.0, early_stopping=False, do_sample=False, temperature=1.0, top_k=50,
-             top_p=1.0, repetition_penalty=1.0, eos=None, pad=None, seed=None, use_graph=True):
+             top_p=1.0, repetition_penalty=1.0, eos=None, pad=None, seed=None, use_graph=True, grammar=None):
         """After prefill(nb=self.nb): HF _beam_search (generation/utils.py:3208-3560) for T_new steps, every step one egomi_beam_rows + one
         egomi_beam_update launch + one cached decode step over the B * nb logical beams, all captured into ONE hipGraph (no host sync per
         step: the loop-open flag lives in device memory and closes the remaining steps when HF would have left its loop).
         Returns (sequences [B*nrs, S0 + Lgen], sequences_scores [B*nrs], scores [iterations, B*nb, V] fp32, beam_indices [B*nrs, Lgen])."""
+        if grammar is not None:
+            raise ValueError("beam() takes no trajectory grammar: the beams of an item share one prefill logits row at step 0")
         nb, R, S0, dev = self.nb, self.B, self.pos, self.eng.device
         Bi, V = R // nb, self.lg.shape[1]
         n_eos = 0 if eos is None else 1

@@ -140,11 +140,13 @@ def micro_batch_per_rank(bs, grad_accum_steps, world):
     return max(1, -(-int(bs) // (max(1, int(grad_accum_steps)) * max(1, int(world)))))
 
 
-def check_val_options(K, num_beams, sample, select, rescore, M, radius, soft, decoding_rules=True, full=False):
+def check_val_options(K, num_beams, sample, select, rescore, M, radius, soft, decoding_rules=True, full=False, constrain=False):
     """The rules of --num_samples / --select / --rescore / --num_modes / --mode_radius / --soft_decode on their resolved values, one text
     per rule; raises ValueError.  run_validation applies all of them; parse_args applies the first four (decoding_rules=False) and exits
     on them: the last four stay errors of the run itself (main() raises ValueError there, and tests pin that).  --full_metrics goes with
     every decoding mode: `full` has no rule."""
+    if constrain and num_beams != 1:
+        raise ValueError("--constrain_traj masks the logits row of every sample: it needs num_beams == 1 (beams share one prefill row)")
     if soft and num_beams != 1:
         raise ValueError("--soft_decode reads the per-step distribution of sampled or greedy decoding: it needs num_beams == 1")
     if M < 0 or (M > 0 and not (K > 1 and M <= K <= 64)):
@@ -165,13 +167,15 @@ def check_val_options(K, num_beams, sample, select, rescore, M, radius, soft, de
         raise ValueError("--select chooses among samples: it needs --num_samples K > 1")
 
 
-def val_options(args, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None, soft_decode=None, full_metrics=None):
+def val_options(args, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None, soft_decode=None, full_metrics=None,
+                constrain_traj=None):
     """run_validation's options, each resolved as: the explicit keyword, else `args`, else its default; checked (check_val_options)."""
     pick = lambda explicit, name, default: explicit if explicit is not None else (getattr(args, name, default) or default)
     o = types.SimpleNamespace(K=int(pick(num_samples, "num_samples", 1)), num_beams=num_beams, sample=bool(getattr(args, "val_sample", True)),
                               select=str(pick(select, "select", "none")), rescore=bool(getattr(args, "rescore", False)),
                               M=int(pick(num_modes, "num_modes", 0)), radius=float(pick(mode_radius, "mode_radius", 0.0)),
-                              soft=bool(pick(soft_decode, "soft_decode", False)), full=bool(pick(full_metrics, "full_metrics", False)))
+                              soft=bool(pick(soft_decode, "soft_decode", False)), full=bool(pick(full_metrics, "full_metrics", False)),
+                              constrain=bool(pick(constrain_traj, "constrain_traj", False)))
     check_val_options(**vars(o))
     return o
 
@@ -181,6 +185,7 @@ BASE_SUMS = ("ADE", "FDE", "ADE_as_called", "GD", "n")
 BEST_SUMS = ("minADE", "minFDE", "n_min")
 SEL_SUMS = ("ADE_sel", "FDE_sel", "n_sel")
 MODE_SUMS = ("minADE_M", "minFDE_M", "brierADE_M", "n_M", "modes", "clips_M")      # n_M: clips with a mode; modes over clips_M clips
+GRAMMAR_SUMS = ("gmass_mean", "gmass_min", "n_gmass")                             # per clip: mean and smallest per-step mass of the allowed set
 SOFT_SUMS = ("ADE_soft", "FDE_soft", "n_soft", "std", "n_std", "mass_min")        # std over n_std coordinates; the smallest masses
 FULL_SUMS = ("IDE", "DTW", "GD_dev", "n_full", "minIDE", "minGD", "minDTW", "n_fmin", "GD_sel", "DTW_sel", "n_fsel", "minGD_M", "minDTW_M", "n_fM")
 
@@ -223,6 +228,8 @@ def parse_trajectories(ids, tok, num_steps, Tn, norm, max_abs, device):
 def generate_kwargs(o, args, tok):
     """generate()'s keyword arguments for the decoding mode: K samples on a shared prompt, beams, or neither; the bin statistics."""
     kw = {"output_bin_stats": True, "bin_token_ids": (tok.p0, tok.num_bins)} if o.soft else {}
+    if o.constrain:                                          # the prompt holds the first step: it counts among the num_steps
+        kw["traj_grammar"] = T.grammar_spec(tok, args.num_steps, args.num_steps)
     if o.K > 1:
         kw.update(num_return_sequences=o.K, share_prompt=True, **({"output_logprobs": True} if o.select == "logprob" else {}))
     elif o.num_beams != 1:
@@ -324,6 +331,21 @@ def modes_record(o, sums):
             "brierADE_M": _mean(sums, "brierADE_M", "n_M"), "n_modes": _mean(sums, "modes", "clips_M"), "M": o.M, "mode_radius": o.radius}
 
 
+def grammar_batch(o, b, tok, sums):
+    """Sample 0 of every clip: the mean and the smallest raw probability its steps gave the ids the grammar allowed, up to its eos."""
+    from .decode import candidate_lengths
+    mass = b.out.grammar_mass[::o.K].double()
+    lens = candidate_lengths(b.all_ids[::o.K], tok.eos).clamp(min=1)
+    live = torch.arange(mass.shape[1], device=mass.device)[None, :] < lens[:, None]
+    mean = (mass * live).sum(1) / lens
+    low = mass.masked_fill(~live, float("inf")).min(1).values
+    _add(sums, gmass_mean=mean.sum(), gmass_min=low.sum(), n_gmass=len(mean))
+
+
+def grammar_record(o, sums):
+    return {"grammar_mass_mean": _mean(sums, "gmass_mean", "n_gmass"), "grammar_mass_min": _mean(sums, "gmass_min", "n_gmass")}
+
+
 def soft_batch(o, b, tok, num_steps, norm, sums, soft_dump):
     """Sample 0 of every clip again, from the distributions its tokens were drawn from: the soft trajectory and its std."""
     device, Tn = b.head.device, b.gt.shape[1]
@@ -402,7 +424,7 @@ def rank_batches(n, per, rank, world, max_batches=None):
 
 @torch.no_grad()
 def run_validation(model, data, args, device, max_batches=None, num_beams=1, num_samples=None, select=None, num_modes=None, mode_radius=None,
-                   soft_decode=None, full_metrics=None):
+                   soft_decode=None, full_metrics=None, constrain_traj=None):
     """Generation + metrics on the rank's shard (train.py:207-264, evaluate.py:104-154): prompts up to the first <tsep>,
     `generate` of the remaining positions (sampling with the reference's defaults top_k 50 / top_p 0.95 / T 1.0 unless
     args.val_sample is False -> greedy), cut at eos, de-tokenise, de-normalise (dataset.denorm), pad with the last step,
@@ -449,16 +471,24 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     which stays), with K > 1 'minIDE' / 'minGD' / 'minDTW' (means over the clips with a parsed sample), with select 'GD_sel' / 'DTW_sel'
     (the pick's values) and with num_modes 'minGD_M' / 'minDTW_M' (minima over the chosen samples); the dump gains one key,
     "full": {image id: {"ADE": [K values], "FDE": ..., "IDE": ..., "GD": ..., "DTW": ...}} with None for an unparsed sample.  Off, the
-    record and the dump are what they are without it."""
-    o = val_options(args, num_beams, num_samples, select, num_modes, mode_radius, soft_decode, full_metrics)
+    record and the dump are what they are without it.
+
+    constrain_traj (default: args.constrain_traj, else False; num_beams == 1): generate(traj_grammar=T.grammar_spec(tok, num_steps, num_steps)):
+    every generated row is a well-formed trajectory of exactly args.num_steps steps, the prompt's first step included (the state is read
+    from the prompt).  The record gains 'grammar_mass_mean' and 'grammar_mass_min': the mean over the clips (sample 0) of the mean, and of
+    the smallest, raw probability that a step gave the ids the grammar allowed -- how much of the model's own mass the constraint kept.
+    Off, every record, dump and bit is what it is without it."""
+    o = val_options(args, num_beams, num_samples, select, num_modes, mode_radius, soft_decode, full_metrics, constrain_traj)
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
-    sums = dict.fromkeys(BASE_SUMS + BEST_SUMS + SEL_SUMS + MODE_SUMS + SOFT_SUMS + FULL_SUMS, 0.0)
+    sums = dict.fromkeys(BASE_SUMS + BEST_SUMS + SEL_SUMS + MODE_SUMS + SOFT_SUMS + FULL_SUMS + GRAMMAR_SUMS, 0.0)
     dump, picked, mode_dump, soft_dump, full_dump = {}, {}, {}, {}, {}
     model.eval()
     for idx in rank_batches(len(data), micro_batch_per_rank(args.bs, 1, world), rank, world, max_batches):
         b = generate_batch(model, data, args, device, o, idx, norm)
         base_batch(o, b, sums, dump)
+        if o.constrain:
+            grammar_batch(o, b, model.dims.tok, sums)
         if o.soft:
             soft_batch(o, b, model.dims.tok, args.num_steps, norm, sums, soft_dump)
         if o.K > 1:
@@ -488,6 +518,8 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     if o.full:
         rec.update(full_record(o, sums))
         dump["full"] = full_dump
+    if o.constrain:
+        rec.update(grammar_record(o, sums))
     return rec, dump
 
 
@@ -733,12 +765,16 @@ def parse_args(argv=None):
                          "for every sample on the device, one launch per batch; adds IDE / DTW / GD_dev / n_full (with --num_samples K > 1 "
                          "minIDE / minGD / minDTW, with --select GD_sel / DTW_sel, with --num_modes minGD_M / minDTW_M) to the record and the "
                          "per-sample values per image id to the dump")
+    ap.add_argument("--constrain_traj", action="store_true",
+                    help="validation / eval with --num_beams 1: constrained decoding, every generated row is a well-formed trajectory of exactly "
+                         "--num_steps steps (the prompt's first step included), by one grammar launch per step on the device; adds "
+                         "grammar_mass_mean / grammar_mass_min (the raw probability the model gave the allowed ids) to the record")
     a = ap.parse_args(argv)
     if not a.max_grad_norm >= 0:
         ap.error("--max_grad_norm must be >= 0 (0: off)")
     try:
         check_val_options(int(a.num_samples or 1), a.num_beams, a.val_sample, a.select, a.rescore, a.num_modes, a.mode_radius, a.soft_decode,
-                          decoding_rules=False)
+                          decoding_rules=False, constrain=a.constrain_traj)
     except ValueError as e:
         ap.error(str(e))
     return a

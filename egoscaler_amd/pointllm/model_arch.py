@@ -153,6 +153,8 @@ class GenerateOutput:
     bin_mean: Optional[torch.Tensor] = None             # E[value | bin token]
     bin_std: Optional[torch.Tensor] = None              # the standard deviation of that conditional distribution
     bin_entropy: Optional[torch.Tensor] = None          # its entropy in nats
+    # generate(traj_grammar=spec) only: fp32 [rows, T'], column t = the raw probability of the ids the grammar allowed at step t; 0 after a row's eos
+    grammar_mass: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -595,7 +597,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
                  eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
                  decode_weight_dtype=None, share_prompt=False, kv_cache_layout=None, output_logprobs=False, rank_length_penalty=1.0, output_bin_stats=False,
-                 bin_token_ids=None, **kwargs):
+                 bin_token_ids=None, traj_grammar=None, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -661,7 +663,21 @@ class TrajPointLLMForCausalLM(nn.Module):
         bin_mean (E[value | bin token]: a continuous estimate without the quantisation step 2 / (nb - 1)), bin_std and bin_entropy (nats) of
         that conditional distribution; 0 after a row's eos.  It reports and changes nothing: the fed-back token, every other field and the
         graphs of the calls without it are what they were; it combines with output_logprobs (two launches per step).  traj.detokenize_soft
-        turns bin_mean / bin_std / bin_mass into trajectories.  num_beams > 1 raises ValueError."""
+        turns bin_mean / bin_std / bin_mass into trajectories.  num_beams > 1 raises ValueError.
+
+        traj_grammar=traj.grammar_spec(tok, min_steps, max_steps) (num_beams == 1; HF: prefix_allowed_tokens_fn): constrained decoding.  Every
+        returned row reads <ts> (bin x 6 <tsep>) x n <te> eos with min_steps <= n <= max_steps from the prompt's last <ts> on, whatever the
+        weights: a ten-state machine per row on the device, one egomi_traj_grammar_step launch per step directly before the token kernel
+        inside the token loop (csrc/grammar.hip), writes -inf over every id the row's state does not allow.  The state is read from the
+        prompt (egomi_traj_grammar_init, before the prefill is queued), and a row that needs more than max_length tokens to close raises
+        ValueError naming it.  The mask is in place on the logits, so with the option on `scores` are the processed scores of the
+        CONSTRAINED distribution, and output_logprobs / output_bin_stats report on that same renormalised distribution -- the one the token
+        was drawn from, a proper distribution over valid trajectories.  What the model itself thought of the grammar survives in
+        grammar_mass fp32 [rows, T']: column t = the raw probability of the ids allowed at step t (0 after a row's eos).  eos_token_id must
+        be the spec's eos.  Works with every cache and weight dtype, share_prompt and LoRA; num_beams > 1 raises ValueError.  None: every
+        graph, launch and output is what it is without the option."""
+        if traj_grammar is not None and int(num_beams) > 1:
+            raise ValueError("traj_grammar is for num_beams == 1: the beams of an item share one prefill logits row at step 0")
         if output_logprobs and int(num_beams) > 1:
             raise ValueError("output_logprobs=True is for num_beams == 1; beam search returns `sequences_scores` (length-penalised sums of "
                              "the beams' log-probs)")
@@ -727,6 +743,7 @@ class TrajPointLLMForCausalLM(nn.Module):
         if share and T < 1:
             raise ValueError("share_prompt=True needs max_length >= 1")
         eos_token_id, pad_token_id = self._sampling_args(eos_token_id, pad_token_id, temperature, repetition_penalty, top_p)
+        grammar = self._grammar_ready(traj_grammar, ids, attention_mask, eos_token_id, T) if traj_grammar is not None else None
         # one Decoder (static KV cache + captured token loops) per geometry, kept while the decoder layers it holds stacked copies of cannot
         # change: frozen-LLM mode, same prepared weights.  run_validation / evaluate (train.py:207-264, evaluate.py:104-154) call generate()
         # once per batch: without this every batch re-allocated the cache and re-captured a graph of (new tokens x ~300) kernels
@@ -741,7 +758,7 @@ class TrajPointLLMForCausalLM(nn.Module):
             temperature, top_k, top_p = 1.0, 0, 1.0
         seq, sc = dec.sample(T, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                              eos=eos_token_id, pad=pad_token_id, seed=seed, use_graph=kwargs.get("use_graph", True),
-                             logprobs=bool(output_logprobs), bin_stats=bins)
+                             logprobs=bool(output_logprobs), bin_stats=bins, grammar=grammar)
         stop = T
         if eos_token_id is not None and T > 0:             # HF leaves the loop after the step at which the last unfinished row emitted eos
             hit = seq[:, S0:] == eos_token_id
@@ -751,11 +768,34 @@ class TrajPointLLMForCausalLM(nn.Module):
         out = GenerateOutput(sequences=seq[:, :S0 + stop].clone(), scores=tuple(sc[t] for t in range(stop)))     # hand out copies
         if output_logprobs:
             _fill_logprobs(out, dec, stop, (B // n_ret, n_ret) if n_ret > 1 else None, rank_length_penalty)
-        if bins is not None:
+        if bins is not None or grammar is not None:
             from ..decode import candidate_lengths
             past = torch.arange(stop, device=dev)[None, :] >= candidate_lengths(out.sequences[:, S0:], eos_token_id)[:, None]
+        if bins is not None:
             _fill_bin_stats(out, dec, stop, past=past)
+        if grammar is not None:
+            out.grammar_mass = dec.gr_mass[:, :stop].masked_fill(past, 0.0)
         return out
+
+    def _grammar_ready(self, traj_grammar, ids, attention_mask, eos_token_id, T):
+        """generate(traj_grammar=...) before its prefill: the checked spec, after one egomi_traj_grammar_init launch on the prompts whose
+        `need` is read back: a prompt row that cannot close inside T new tokens raises ValueError."""
+        from ..decode import grammar_check, traj_grammar_init
+        spec = grammar_check(traj_grammar, self.dims.lm.vocab_size)
+        if eos_token_id != spec[5]:
+            raise ValueError(f"traj_grammar closes every row with eos = {spec[5]}: `eos_token_id` must be that id, not {eos_token_id}")
+        dev, B = ids.device, ids.shape[0]
+        mask = None if attention_mask is None else attention_mask.to(dev).to(torch.uint8).contiguous()
+        state = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        need = torch.empty(B, dtype=torch.int32, device=dev)
+        traj_grammar_init(ids.to(torch.int64).contiguous(), mask, spec, state, need)
+        need = need.cpu()
+        short = (need > T).nonzero()
+        if short.numel():
+            r = int(short[0, 0])
+            raise ValueError(f"traj_grammar: prompt row {r} needs {int(need[r])} new tokens to close its trajectory, max_length is {T}"
+                             + (" (the prompt already holds more steps than max_steps)" if int(need[r]) >= (1 << 30) else ""))
+        return spec
 
     def _decode_inputs(self, input_ids, point_clouds, fps_start):
         """The start of generate() and score(): pending parameter updates are waited for (the decoder reads the weights outside the engine's

@@ -58,6 +58,20 @@ def detokenize_batch(ids: torch.Tensor, tok, max_steps: int):
     return out, n
 
 
+GrammarSpec = collections.namedtuple("GrammarSpec", "p0 nb ts tsep te eos min_steps max_steps")
+
+
+def grammar_spec(tok, min_steps: int, max_steps: int) -> GrammarSpec:
+    """The trajectory grammar of generate(traj_grammar=...) for the tokenizer ids `tok` (the object tokenize_batch takes):
+    <ts> (bin x 6 <tsep>) x n <te> eos with min_steps <= n <= max_steps, bins = the ids tok.p0 .. tok.p0 + tok.num_bins - 1.  n counts the
+    steps from the sequence's last <ts>, the prompt's included: a prompt that already holds the first step needs min_steps >= 1 to mean
+    anything.  The table itself is csrc/grammar.hip's."""
+    mn, mx = int(min_steps), int(max_steps)
+    if not 0 <= mn <= mx:
+        raise ValueError(f"grammar_spec: 0 <= min_steps <= max_steps does not hold for ({min_steps}, {max_steps})")
+    return GrammarSpec(int(tok.p0), int(tok.num_bins), int(tok.ts), int(tok.tsep), int(tok.te), int(tok.eos), mn, mx)
+
+
 def detokenize_soft(ids: torch.Tensor, tok, max_steps: int, bin_mean, bin_std, bin_mass=None):
     """detokenize_batch with the per-token statistics of generate(output_bin_stats=True) / egomi_bin_stats in place of the bin centres
     (egomi_traj_detokenize_soft): the same scan of the same ids, and a step parsed from ids hit .. hit+5 takes

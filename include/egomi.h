@@ -342,6 +342,35 @@ int egomi_seq_rank(const float* sum_lp, const int32_t* n_tok, int B, int K, floa
  * [0, ld_out)), UNSUPPORTED (logits not aligned to their element size). */
 int egomi_bin_stats(const void* logits, int64_t ld, int R, int V, int p0, int nb, const double* values, float* mass, float* mean,
                     float* std, float* ent, int64_t ld_out, int col, int dtype, egomi_stream_t stream);
+/* Constrained decoding of trajectories (csrc/grammar.hip; HF: generate(prefix_allowed_tokens_fn=...), logits_process.py
+ * PrefixConstrainedLogitsProcessor, without its per-row host callback).  The grammar <ts> (bin x 6 <tsep>) x n <te> eos with
+ * min_steps <= n <= max_steps over the bin ids p0 .. p0 + nb - 1 and the four special ids is a ten-state machine; a decoder row's state
+ * is int32 (phase, steps), state[2 r] and state[2 r + 1].  The transition table, the allowed set of every state and need(state) are
+ * stated once, in the header comment of csrc/grammar.hip.
+ *   grammar_init: ids int64 [R, S0] (row stride ld_ids), mask uint8 [R, S0] (row stride ld_mask) or NULL; positions with mask == 0 are
+ *                skipped.  state[r] = the state the prompt leaves (from its last <ts>: steps = the <tsep> after it, phase = the trailing
+ *                run of bins, capped at 6; no <ts>: (9, 0)) and need[r] = the tokens to the earliest legal close, EGOMI_GRAMMAR_NEVER
+ *                where the prompt already holds more steps than max_steps.  A row with need <= T_new ends `<te> eos` inside T_new steps.
+ *   grammar_step: one launch per decode step directly before the token kernel, in place on the logits (bf16 or fp32 [R, V], row stride
+ *                ld).  Per row: tok_prev != NULL advances state[r] by tok_prev[r] (a token the state does not allow leaves it as it
+ *                is); mass[r*ld_mass + col] = sum exp(x_a - m) over the allowed ids / sum exp(x - m) over all V, on the RAW row
+ *                (token_logprob's pass; the allowed sum in float64 in a fixed order; a NaN logit gives NaN); then -inf over every id of
+ *                [0, V) that is not allowed.  rem = the tokens the loop still emits, this one included: at a step boundary a new step
+ *                may open only when rem >= 9.  Allowed elements are not written, nor is any byte outside [row, row + V): padding
+ *                columns and neighbouring rows stay.  Every allowed logit -inf: mass = 0 and the row ends all -inf.  rem and col are
+ *                launch constants; no atomics; a row's bits depend on its values, its state and (V, spec, dtype) only; a replay is
+ *                bit-equal.
+ * Both return BADARG (a NULL pointer other than mask / tok_prev, unknown dtype), SHAPE (a size <= 0, a row stride below its row, rem < 1,
+ * col outside [0, ld_mass), nb outside 1 .. 1024, p0 < 0, min_steps < 0 or > max_steps, a special id negative, inside the bin window or
+ * equal to another; grammar_step also: the window or a special id outside [0, V)), grammar_step UNSUPPORTED (logits not aligned to
+ * their element size). */
+#define EGOMI_GRAMMAR_NEVER 1073741824
+int egomi_traj_grammar_init(const int64_t* ids, int64_t ld_ids, const uint8_t* mask, int64_t ld_mask, int R, int S0, int64_t p0, int nb,
+                            int64_t ts, int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int32_t* state, int32_t* need,
+                            egomi_stream_t stream);
+int egomi_traj_grammar_step(void* logits, int64_t ld, int R, int V, const int64_t* tok_prev, int32_t* state, int64_t p0, int nb, int64_t ts,
+                            int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int rem, float* mass, int64_t ld_mass, int col,
+                            int dtype, egomi_stream_t stream);
 /* Beam search / beam sampling (num_beams > 1): HF GenerationMixin._beam_search, transformers 5.15 generation/utils.py:3208-3560.
  * Logical rows r = b * nb + j (item b, beam j), R = B * nb.  Every step is one beam_rows + one beam_update launch; ctl (int32 [6], device)
  * holds the loop-open flag [0] and the iteration count [1]: once a step closes the loop, both return at once, so T captured steps
