@@ -140,3 +140,11 @@ static inline int egomi_launch_status() {
         else if ((dtype) == EGOMI_BF16) { typedef bf16_t T; __VA_ARGS__; } \
         else return EGOMI_E_BADARG;                              \
     } while (0)
+
+// the row kernels that keep a row in registers: MAXV = chunks of 8 columns per thread of a 256-thread block (cols <= 8192)
+#define EGOMI_DISPATCH_MAXV(cols, ...)                           \
+    do {                                                         \
+        if ((cols) <= 2048) { constexpr int MAXV = 1; __VA_ARGS__; }      \
+        else if ((cols) <= 4096) { constexpr int MAXV = 2; __VA_ARGS__; } \
+        else { constexpr int MAXV = 4; __VA_ARGS__; }            \
+    } while (0)

@@ -1,4 +1,5 @@
-// Single-token decode against a static KV cache (A13): kv_append, the consumers of the split-K slabs, argmax; the attention over the
+// Single-token decode against a static KV cache (A13): kv_append, qkv_finish (the q|k|v consumer of the split-K slabs; its arithmetic is
+// qkv_finish.h on row_pieces.h, and the slabs + residual + RMSNorm consumer is in elementwise.hip), argmax; the attention over the
 // cache is attn_decode.hip.  Replaces the cache update of HF LlamaAttention.forward (modeling_llama.py:243-281 with
 // past_key_values.update) and the greedy step of GenerationMixin.generate reached from model_arch.py:94-108.  Cache layout
 // [B, H, Smax, hd] keeps every (batch, head) stream contiguous.  All launches take their lengths as arguments, so 32 steps can be
@@ -41,77 +42,10 @@ extern "C" int egomi_kv_append(const void* k, const void* v, int64_t ld, void* k
 
 // ------------------------------------------------------------------------------------------------
 // Consumers of EGOMI_EPI_SLABS products (include/egomi.h): the single-token step's split-K projections leave fp32 K-slice
-// slabs; these kernels sum them (slice order, like splitk_reduce_kernel) while doing the next operation of the layer, with
-// the rounding sequence of the separate kernels they replace (bit-identical results).
+// slabs; the consumers sum them (slice order, like splitk_reduce_kernel) while doing the next operation of the layer, with
+// the rounding sequence of the separate kernels they replace (bit-identical results: the same device functions, row_pieces.h).
+// The o_proj / down_proj consumer, egomi_slabs_rmsnorm, is elementwise.hip's rmsnorm_slabs_kernel, the training step's tail-row kernel.
 //
-// slabs_rmsnorm: x = bf16(sum_s slab[s] + residual)   (the o_proj / down_proj output with its residual, HF modeling_llama.py:
-//                 243-281), h = rmsnorm(x) * w         (rmsnorm_fwd_kernel's arithmetic).  One 256-thread block per row.
-// ------------------------------------------------------------------------------------------------
-template <typename T, int MAXV>
-__global__ __launch_bounds__(256) void slabs_rmsnorm_kernel(const float* slabs, int sk, long long slab_stride, int cols, const T* residual, long long ldr,
-                                                            const T* w, float eps, T* x_out, long long ldx, T* h_out, long long ldh) {
-    __shared__ float red[16];
-    const long long row = blockIdx.x;
-    float xv[MAXV][8];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (threadIdx.x + i * 256) * 8;
-        if (c < cols) {
-            float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            for (int s2 = 0; s2 < sk; ++s2) {
-                float t[8];
-                load8<float>(slabs + (long long)s2 * slab_stride + row * cols + c, t);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] += t[j];
-            }
-            if (residual) {
-                float r[8];
-                load8<T>(residual + row * ldr + c, r);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] += r[j];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) xv[i][j] = sizeof(T) == 2 ? bf2f(f2bf(v[j])) : v[j];      // what the combine pass would have stored
-            store8<T>(x_out + row * ldx + c, xv[i]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss += xv[i][j] * xv[i][j];
-        }
-    }
-    const float rstd = rsqrtf(block_sum(ss, red) / cols + eps);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (threadIdx.x + i * 256) * 8;
-        if (c < cols) {
-            float ww[8], o[8];
-            load8<T>(w + c, ww);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float h = xv[i][j] * rstd;
-                if (sizeof(T) == 2) h = bf2f(f2bf(h));
-                o[j] = ww[j] * h;
-            }
-            store8<T>(h_out + row * ldh + c, o);
-        }
-    }
-}
-
-extern "C" int egomi_slabs_rmsnorm(const float* slabs, int slices, int rows, int cols, const void* residual, int64_t ldr, const void* w, float eps,
-                                   void* x_out, int64_t ldx, void* h_out, int64_t ldh, int dtype, egomi_stream_t stream) {
-    if (!slabs || !w || !x_out || !h_out) return EGOMI_E_BADARG;
-    if (slices < 1 || rows <= 0 || cols <= 0 || cols % 8 || ldx < cols || ldh < cols || ldx % 8 || ldh % 8 || (residual && (ldr < cols || ldr % 8))) return EGOMI_E_SHAPE;
-    if (cols > 8192) return EGOMI_E_UNSUPPORTED;
-    if (((uintptr_t)slabs | (uintptr_t)x_out | (uintptr_t)h_out | (uintptr_t)w | (uintptr_t)residual) & 15) return EGOMI_E_SHAPE;
-    hipStream_t s = (hipStream_t)stream;
-    const long long stride = (long long)rows * cols;
-#define SRN(V) EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((slabs_rmsnorm_kernel<T, V>), dim3(rows), dim3(256), 0, s, slabs, slices, stride, cols, (const T*)residual, \
-                                                        (long long)ldr, (const T*)w, eps, (T*)x_out, (long long)ldx, (T*)h_out, (long long)ldh))
-    if (cols <= 2048) SRN(1); else if (cols <= 4096) SRN(2); else SRN(4);
-#undef SRN
-    return egomi_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
 // qkv_finish (single-token step): q|k|v = bf16(sum_s slab[s]) [B, 3*H*hd]; RoPE at position `pos` on q and k (rope_vec8_kernel's
 // arithmetic, HF apply_rotary_pos_emb; qkv_finish.h), q written to qkv (attn_decode reads it there), k and v written straight into the
 // [B,H,Smax,hd] caches at `pos`.  Replaces splitk_reduce + rope + kv_append.  One thread per 8 rotation pairs / 16 v columns.

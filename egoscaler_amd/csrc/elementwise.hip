@@ -3,7 +3,10 @@
 // fwd+bwd, AdamW, transpose, cast, add, mini-PointNet group max, small-K linear.
 // All compute in fp32; I/O in T (float or bf16).  16-byte vector accesses where the shape allows.
 #include "common.h"
+#include "row_pieces.h"
 #include <math.h>
+
+static inline int ew_grid(long long total) { long long g = (total + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm forward (+ fused pre-add).  reference: point_encoder.py:60,63,74-75,95-98,142
@@ -69,26 +72,20 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const T* x, const T* w
     const float rstd = rsqrtf(block_sum(s, red) / cols + eps);
     if (rstd_out && threadIdx.x == 0) rstd_out[row] = rstd;
     for (int c = threadIdx.x * 8; c < cols; c += 256 * 8) {
-        float v[8], ww[8], o[8];
+        float v[8];
         load8<T>(xr + c, v);
-        load8<T>(w + c, ww);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float h = v[j] * rstd;
-            if (sizeof(T) == 2) h = bf2f(f2bf(h));      // .to(input_dtype) before the weight multiply
-            o[j] = ww[j] * h;
-        }
-        store8<T>(y + row * cols + c, o);
+        rmsnorm_apply_store8<T>(v, rstd, w + c, y + row * cols + c);
     }
 }
 
-// rmsnorm_fwd_kernel for an input whose last rows are still K-slice slabs of the producing GEMM (EGOMI_EPI_SLABS on a large
-// product, include/egomi.h): rows >= row0 are first formed as x = round(sum_s slab[s] (+ residual)) — what the combine pass would
-// have stored — written to x, and normalised from registers; rows < row0 take rmsnorm_fwd_kernel's path.  Same arithmetic and
-// summation order as the two separate kernels.
+// rmsnorm_fwd_kernel for an input whose rows >= row0 are still K-slice slabs of the producing GEMM (EGOMI_EPI_SLABS, include/egomi.h):
+// those rows are first formed as x = round(sum_s slab[s] (+ residual)) — what the combine pass would have stored — written to x, and
+// normalised from registers (cols <= MAXV * 2048); rows < row0 are read from x.  Row strides ldx / ldy; the residual and rstd_out are
+// optional.  The training step's tail rows (egomi_rmsnorm_fwd_tail) and the single-token step, where every row is slabs
+// (egomi_slabs_rmsnorm, row0 = 0), both launch it.
 template <typename T, int MAXV>
-__global__ __launch_bounds__(256) void rmsnorm_fwd_tail_kernel(T* x, const T* w, T* y, float* rstd_out, int cols, float eps, int row0, const float* slabs,
-                                                               int sk, long long slab_stride, const T* residual, long long ldr) {
+__global__ __launch_bounds__(256) void rmsnorm_slabs_kernel(T* x, long long ldx, const T* w, T* y, long long ldy, float* rstd_out, int cols, float eps, int row0,
+                                                            const float* slabs, int sk, long long slab_stride, const T* residual, long long ldr) {
     __shared__ float red[16];
     const long long row = blockIdx.x;
     float xv[MAXV][8];
@@ -98,24 +95,17 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_tail_kernel(T* x, const T* w,
         const int c = (threadIdx.x + i * 256) * 8;
         if (c < cols) {
             if (row >= row0) {                                           // block-uniform
-                float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                for (int s2 = 0; s2 < sk; ++s2) {
-                    float t[8];
-                    load8<float>(slabs + (long long)s2 * slab_stride + (row - row0) * cols + c, t);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] += t[j];
-                }
+                slab_sum8(slabs + (row - row0) * cols + c, sk, slab_stride, xv[i]);
                 if (residual) {
                     float r[8];
                     load8<T>(residual + row * ldr + c, r);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] += r[j];
+                    for (int j = 0; j < 8; ++j) xv[i][j] += r[j];
                 }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xv[i][j] = sizeof(T) == 2 ? bf2f(f2bf(v[j])) : v[j];
-                store8<T>(x + row * cols + c, xv[i]);
+                round_as_stored8<T>(xv[i]);
+                store8<T>(x + row * ldx + c, xv[i]);
             } else {
-                load8<T>(x + row * cols + c, xv[i]);
+                load8<T>(x + row * ldx + c, xv[i]);
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) ss += xv[i][j] * xv[i][j];
@@ -126,17 +116,7 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_tail_kernel(T* x, const T* w,
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int c = (threadIdx.x + i * 256) * 8;
-        if (c < cols) {
-            float ww[8], o[8];
-            load8<T>(w + c, ww);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float h = xv[i][j] * rstd;
-                if (sizeof(T) == 2) h = bf2f(f2bf(h));      // .to(input_dtype) before the weight multiply
-                o[j] = ww[j] * h;
-            }
-            store8<T>(y + row * cols + c, o);
-        }
+        if (c < cols) rmsnorm_apply_store8<T>(xv[i], rstd, w + c, y + row * ldy + c);
     }
 }
 
@@ -159,18 +139,8 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(T* dy, const T* x, con
             if (c < cols) {
                 float g[8], xv[8], ww[8];
                 if (row >= row0) {                                       // block-uniform
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) g[j] = 0.f;
-                    for (int s2 = 0; s2 < sk; ++s2) {
-                        float t[8];
-                        load8<float>(slabs + (long long)s2 * slab_stride + (row - row0) * cols + c, t);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) g[j] += t[j];
-                    }
-                    if (sizeof(T) == 2) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) g[j] = bf2f(f2bf(g[j]));
-                    }
+                    slab_sum8(slabs + (row - row0) * cols + c, sk, slab_stride, g);
+                    round_as_stored8<T>(g);
                     store8<T>(dy + row * cols + c, g);
                 } else {
                     load8<T>(dy + row * cols + c, g);
@@ -283,10 +253,8 @@ static int rmsnorm_bwd_impl(void* dy, const void* x, const void* w, const float*
     };
     if (dw && !tail) dw_pass();
     const int grid = rows;
-#define RNB(V) EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((rmsnorm_bwd_kernel<T, V>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)dy, (const T*)x, \
-                                                        (const T*)w, rstd, (T*)dx, (const T*)dx_add, rows, cols, row0, slabs, sk, stride))
-    if (cols <= 2048) RNB(1); else if (cols <= 4096) RNB(2); else RNB(4);
-#undef RNB
+    EGOMI_DISPATCH_MAXV(cols, EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((rmsnorm_bwd_kernel<T, MAXV>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)dy,
+                                                                (const T*)x, (const T*)w, rstd, (T*)dx, (const T*)dx_add, rows, cols, row0, slabs, sk, stride)));
     if (dw && tail) dw_pass();
     return egomi_launch_status();
 }
@@ -311,18 +279,32 @@ extern "C" int egomi_rmsnorm_bwd_tail(void* dy, const void* x, const void* w, co
     return rmsnorm_bwd_impl(dy, x, w, rstd, dx, dx_add, dw, rows, cols, row0, slabs, slices, dtype, stream);
 }
 
+static int rmsnorm_slabs_launch(void* x, long long ldx, const void* w, void* y, long long ldy, float* rstd, int rows, int cols, float eps, int row0,
+                                const float* slabs, int slices, const void* residual, long long ldr, int dtype, egomi_stream_t stream) {
+    const long long stride = (long long)(rows - row0) * cols;
+    EGOMI_DISPATCH_MAXV(cols, EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((rmsnorm_slabs_kernel<T, MAXV>), dim3(rows), dim3(256), 0, (hipStream_t)stream, (T*)x, ldx,
+                                                                (const T*)w, (T*)y, ldy, rstd, cols, eps, row0, slabs, slices, stride, (const T*)residual, ldr)));
+    return egomi_launch_status();
+}
+
 extern "C" int egomi_rmsnorm_fwd_tail(void* x, const void* w, void* y, float* rstd, int rows, int cols, float eps, int row0, const float* slabs, int slices,
                                       const void* residual, int64_t ldr, int dtype, egomi_stream_t stream) {
     if (!x || !w || !y) return EGOMI_E_BADARG;
     if (rows <= 0 || cols <= 0 || cols % 8 || row0 < 0 || row0 > rows) return EGOMI_E_SHAPE;
     if (row0 < rows && (!slabs || slices < 1 || ((uintptr_t)slabs & 15) || (residual && (ldr < cols || ldr % 8)))) return EGOMI_E_SHAPE;
     if (cols > 8192) return EGOMI_E_UNSUPPORTED;
-    const long long stride = (long long)(rows - row0) * cols;
-#define RNF(V) EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((rmsnorm_fwd_tail_kernel<T, V>), dim3(rows), dim3(256), 0, (hipStream_t)stream, (T*)x, (const T*)w, (T*)y, \
-                                                        rstd, cols, eps, row0, slabs, slices, stride, (const T*)residual, (long long)ldr))
-    if (cols <= 2048) RNF(1); else if (cols <= 4096) RNF(2); else RNF(4);
-#undef RNF
-    return egomi_launch_status();
+    return rmsnorm_slabs_launch(x, cols, w, y, cols, rstd, rows, cols, eps, row0, slabs, slices, residual, ldr, dtype, stream);
+}
+
+// the single-token step (decode.hip's other slab consumers): every row is slabs of the o_proj / down_proj product;
+// x_out = round(sum_s slab[s] + residual), h_out = rmsnorm(x_out) * w
+extern "C" int egomi_slabs_rmsnorm(const float* slabs, int slices, int rows, int cols, const void* residual, int64_t ldr, const void* w, float eps,
+                                   void* x_out, int64_t ldx, void* h_out, int64_t ldh, int dtype, egomi_stream_t stream) {
+    if (!slabs || !w || !x_out || !h_out) return EGOMI_E_BADARG;
+    if (slices < 1 || rows <= 0 || cols <= 0 || cols % 8 || ldx < cols || ldh < cols || ldx % 8 || ldh % 8 || (residual && (ldr < cols || ldr % 8))) return EGOMI_E_SHAPE;
+    if (cols > 8192) return EGOMI_E_UNSUPPORTED;
+    if (((uintptr_t)slabs | (uintptr_t)x_out | (uintptr_t)h_out | (uintptr_t)w | (uintptr_t)residual) & 15) return EGOMI_E_SHAPE;
+    return rmsnorm_slabs_launch(x_out, ldx, w, h_out, ldh, nullptr, rows, cols, eps, 0, slabs, slices, residual, ldr, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -345,14 +327,7 @@ __global__ __launch_bounds__(256) void rope_kernel(T* x, const float* cos_tab, c
         T* p = x + r * ld + (long long)h * hd + i;
         const float a = Cvt<T>::ld(p), b = Cvt<T>::ld(p + half);
         float oa, ob;
-        if (sizeof(T) == 2) {
-            c = bf2f(f2bf(c)); s = bf2f(f2bf(s));
-            oa = bf2f(f2bf(a * c)) + bf2f(f2bf(-b * s));
-            ob = bf2f(f2bf(b * c)) + bf2f(f2bf(a * s));
-        } else {
-            oa = a * c + (-b) * s;
-            ob = b * c + a * s;
-        }
+        rope_pair<T>(a, b, c, s, ROPE_FUSE_MIX, oa, ob);           // fp32: this kernel's own rounding (row_pieces.h)
         Cvt<T>::st(p, oa);
         Cvt<T>::st(p + half, ob);
     }
@@ -375,18 +350,7 @@ __global__ __launch_bounds__(256) void rope_vec8_kernel(T* x, const float* cos_t
         T* p = x + r * ld + (long long)h * hd + i;
         load8<T>(p, a);
         load8<T>(p + half, b);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float cj = c[j], sj = inverse ? -s[j] : s[j];
-            if (sizeof(T) == 2) {
-                cj = bf2f(f2bf(cj)); sj = bf2f(f2bf(sj));
-                oa[j] = bf2f(f2bf(a[j] * cj)) + bf2f(f2bf(-b[j] * sj));
-                ob[j] = bf2f(f2bf(b[j] * cj)) + bf2f(f2bf(a[j] * sj));
-            } else {
-                oa[j] = a[j] * cj + (-b[j]) * sj;
-                ob[j] = b[j] * cj + a[j] * sj;
-            }
-        }
+        rope_rotate8<T>(a, b, c, s, inverse, 0xcc, oa, ob);        // fp32: pairs 2, 3, 6, 7 fused, unlike the kernels that start from slabs
         store8<T>(p, oa);
         store8<T>(p + half, ob);
     }
@@ -413,21 +377,11 @@ __global__ __launch_bounds__(256) void rope_qkv_tail_kernel(T* x, const float* c
         T* p = x + r * ld + col;
         float a[8], b[8], oa[8], ob[8];
         if (tail) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { a[j] = 0.f; b[j] = 0.f; }
-            for (int s2 = 0; s2 < sk; ++s2) {
-                float t[8];
-                load8<float>(slabs + (long long)s2 * slab_stride + (r - row0) * ncols + col, t);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) a[j] += t[j];
-                load8<float>(slabs + (long long)s2 * slab_stride + (r - row0) * ncols + col + half, t);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) b[j] += t[j];
-            }
-            if (sizeof(T) == 2) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { a[j] = bf2f(f2bf(a[j])); b[j] = bf2f(f2bf(b[j])); }
-            }
+            const float* sp = slabs + (r - row0) * ncols + col;
+            slab_sum8(sp, sk, slab_stride, a);
+            slab_sum8(sp + half, sk, slab_stride, b);
+            round_as_stored8<T>(a);
+            round_as_stored8<T>(b);
         } else {
             load8<T>(p, a);
             load8<T>(p + half, b);
@@ -437,18 +391,7 @@ __global__ __launch_bounds__(256) void rope_qkv_tail_kernel(T* x, const float* c
             float c[8], sn[8];
             load8<float>(cos_tab + (long long)pos * half + i, c);
             load8<float>(sin_tab + (long long)pos * half + i, sn);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float cj = c[j], sj = sn[j];
-                if (sizeof(T) == 2) {
-                    cj = bf2f(f2bf(cj)); sj = bf2f(f2bf(sj));
-                    oa[j] = bf2f(f2bf(a[j] * cj)) + bf2f(f2bf(-b[j] * sj));
-                    ob[j] = bf2f(f2bf(b[j] * cj)) + bf2f(f2bf(a[j] * sj));
-                } else {
-                    oa[j] = a[j] * cj + (-b[j]) * sj;
-                    ob[j] = b[j] * cj + a[j] * sj;
-                }
-            }
+            rope_rotate8<T>(a, b, c, sn, false, 0x3f, oa, ob);     // fp32: pairs 0..5 fused, as in qkv_finish.h
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) { oa[j] = a[j]; ob[j] = b[j]; }
@@ -458,15 +401,16 @@ __global__ __launch_bounds__(256) void rope_qkv_tail_kernel(T* x, const float* c
     }
 }
 
+// one thread per 8 rotation pairs of `rows` rows of H heads
+static inline int rope_vec8_grid(long long rows, int H, int hd) { return ew_grid(rows * H * (hd / 16)); }
+
 extern "C" int egomi_rope_qkv_tail(void* qkv, const float* cos_tab, const float* sin_tab, int64_t rows, int S, int pos_offset, int H, int hd, int64_t ld,
                                    int row0, const float* slabs, int slices, int dtype, egomi_stream_t stream) {
     if (!qkv || !cos_tab || !sin_tab) return EGOMI_E_BADARG;
     if (rows <= 0 || S <= 0 || H <= 0 || hd <= 0 || (hd / 2) % 8 || ld % 8 || ld < 3ll * H * hd || pos_offset < 0 || row0 < 0 || row0 > rows) return EGOMI_E_SHAPE;
     if (row0 < rows && (!slabs || slices < 1 || ((uintptr_t)slabs & 15))) return EGOMI_E_SHAPE;
     if ((uintptr_t)qkv & 15) return EGOMI_E_SHAPE;
-    const long long tv = rows * 3 * H * (hd / 16);
-    const int gv = (int)((tv + 255) / 256 < 16384 ? (tv + 255) / 256 : 16384);
-    EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH(rope_qkv_tail_kernel<T>, dim3(gv), dim3(256), 0, (hipStream_t)stream, (T*)qkv, cos_tab, sin_tab, (long long)rows, S,
+    EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH(rope_qkv_tail_kernel<T>, dim3(rope_vec8_grid(3 * rows, H, hd)), dim3(256), 0, (hipStream_t)stream, (T*)qkv, cos_tab, sin_tab, (long long)rows, S,
                                              pos_offset, H, hd, (long long)ld, row0, slabs, slices, (long long)(rows - row0) * 3 * H * hd));
     return egomi_launch_status();
 }
@@ -477,9 +421,7 @@ extern "C" int egomi_rope(void* x, const float* cos_tab, const float* sin_tab, i
     if (rows <= 0 || S <= 0 || H <= 0 || hd <= 0 || (hd & 1) || ld < (int64_t)H * hd || pos_offset < 0) return EGOMI_E_SHAPE;
     const int esz = dtype == EGOMI_F32 ? 4 : 2;
     if ((hd / 2) % 8 == 0 && ld % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((hd / 2) * esz) % 16 == 0) {
-        const long long tv = rows * H * (hd / 16);
-        const int gv = (int)((tv + 255) / 256 < 16384 ? (tv + 255) / 256 : 16384);
-        EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH(rope_vec8_kernel<T>, dim3(gv), dim3(256), 0, (hipStream_t)stream,
+        EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH(rope_vec8_kernel<T>, dim3(rope_vec8_grid(rows, H, hd)), dim3(256), 0, (hipStream_t)stream,
                                                  (T*)x, cos_tab, sin_tab, rows, S, pos_offset, H, hd, ld, inverse));
         return egomi_launch_status();
     }
@@ -538,8 +480,6 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* dact, const T*
         store8<T>(dup + r * ld_out + ci, ou);
     }
 }
-
-static inline int ew_grid(long long total) { long long g = (total + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
 
 extern "C" int egomi_swiglu_fwd(const void* gate, const void* up, void* out, int64_t rows, int cols, int64_t ld_in, int64_t ld_out,
                                 int dtype, egomi_stream_t stream) {
@@ -933,9 +873,14 @@ extern "C" int egomi_ce_fwd_bwd(const void* logits, int64_t ld, const int64_t* t
 // ------------------------------------------------------------------------------------------------
 // AdamW (torch.optim.AdamW semantics, reference optimizer: train.py:107-111).  fp32 master/moments;
 // optional low-precision model copy written in the same pass.
-// adamw_kernel, adamw_vec4_kernel and adamw_launch have copies below that read the gradient scale from device
-// memory (adamw_ds_kernel, adamw_vec4_ds_kernel, adamw_ds_launch): a change to either must be made in both.
+// Scale: the gradient scale, a float by value (egomi_adamw, _g16) or a const float* read once before the loop (the _ds entries:
+// egomi_clip_scale's out[2], the step's scale times the clipping coefficient, known only on the device).  One loop, one element-to-lane
+// mapping and one adamw_elem for both, so a device value equal to the host value gives the same bits.
 // ------------------------------------------------------------------------------------------------
+__device__ __host__ __forceinline__ float adamw_scale(float s) { return s; }
+__device__ __host__ __forceinline__ float adamw_scale(const float* s) { return *s; }
+static inline bool adamw_scale_given(float) { return true; }
+static inline bool adamw_scale_given(const float* s) { return s != nullptr; }
 template <typename G> __device__ __forceinline__ float adamw_g(const G* g, long long i);
 template <> __device__ __forceinline__ float adamw_g<float>(const float* g, long long i) { return g[i]; }
 template <> __device__ __forceinline__ float adamw_g<bf16_t>(const bf16_t* g, long long i) { return bf2f(g[i]); }
@@ -954,9 +899,10 @@ __device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g
     p = pi; m = mi; v = vi;
 }
 
-template <typename T, typename G>
+template <typename T, typename G, typename Scale>
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, T* p_model, const G* g, float* m, float* v, long long n, float lr, float b1,
-                                                    float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
+                                                    float b2, float eps, float wd, float bc1, float bc2_sqrt, Scale gs) {
+    const float gscale = adamw_scale(gs);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float pi = p[i], mi = m[i], vi = v[i];
         adamw_elem(pi, mi, vi, adamw_g<G>(g, i), lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
@@ -968,10 +914,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, T* p_model, const 
 // 16-B form: four elements per lane and access (master, m, v read and written, the gradient read, the model copy written: 30 B per
 // element at bf16 — the pass is HBM-bound).  Same arithmetic per element.  G = bf16: the gradient is read straight from the rank-summed
 // bf16 wire buffer of dp.GradSync (28 B per element, and no widening pass before it).
-template <typename T, typename G>
+template <typename T, typename G, typename Scale>
 __global__ __launch_bounds__(256) void adamw_vec4_kernel(float* p, T* p_model, const G* g, float* m, float* v, long long n4, float lr, float b1,
-                                                         float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
+                                                         float b2, float eps, float wd, float bc1, float bc2_sqrt, Scale gs) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const float gscale = adamw_scale(gs);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         f32x4 g4;
         if constexpr (sizeof(G) == 4) g4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
@@ -998,10 +945,10 @@ __global__ __launch_bounds__(256) void adamw_vec4_kernel(float* p, T* p_model, c
     }
 }
 
-template <typename G>
+template <typename G, typename Scale>
 static int adamw_launch(float* master, void* model_copy, const G* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                        float weight_decay, int step, float grad_scale, int copy_dtype, hipStream_t stream) {
-    if (!master || !grad || !m || !v) return EGOMI_E_BADARG;
+                        float weight_decay, int step, Scale grad_scale, int copy_dtype, hipStream_t stream) {
+    if (!master || !grad || !m || !v || !adamw_scale_given(grad_scale)) return EGOMI_E_BADARG;
     if (n <= 0 || step <= 0) return EGOMI_E_SHAPE;
     if (model_copy && copy_dtype != EGOMI_F32 && copy_dtype != EGOMI_BF16) return EGOMI_E_BADARG;
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2s = sqrtf(1.0f - powf(beta2, (float)step));
@@ -1009,17 +956,17 @@ static int adamw_launch(float* master, void* model_copy, const G* grad, float* m
     const bool vec = n4 > 0 && (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && ((uintptr_t)grad & (4 * sizeof(G) - 1)) == 0 &&
                      (!model_copy || (copy_dtype == EGOMI_BF16 && ((uintptr_t)model_copy & 7) == 0));
     if (vec) {
-        EGOMI_LAUNCH((adamw_vec4_kernel<bf16_t, G>), dim3(ew_grid(n4)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
+        EGOMI_LAUNCH((adamw_vec4_kernel<bf16_t, G, Scale>), dim3(ew_grid(n4)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
                            n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
         if (rest == 0) return egomi_launch_status();
         master += 4 * n4; grad += 4 * n4; m += 4 * n4; v += 4 * n4; n = rest;
         if (model_copy) model_copy = (bf16_t*)model_copy + 4 * n4;
     }
     if (!model_copy || copy_dtype == EGOMI_F32)
-        EGOMI_LAUNCH((adamw_kernel<float, G>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (float*)model_copy, grad, m, v,
+        EGOMI_LAUNCH((adamw_kernel<float, G, Scale>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (float*)model_copy, grad, m, v,
                            (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
     else
-        EGOMI_LAUNCH((adamw_kernel<bf16_t, G>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
+        EGOMI_LAUNCH((adamw_kernel<bf16_t, G, Scale>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
                            (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
     return egomi_launch_status();
 }
@@ -1034,89 +981,16 @@ extern "C" int egomi_adamw_g16(float* master, void* model_copy, const void* grad
                                 (hipStream_t)stream);
 }
 
-// The same two kernels with the gradient scale read from device memory (egomi_clip_scale's out[2]: the step's scale times the clipping
-// coefficient, known only on the device).  They are separate kernels, not a template parameter of the two above, so that those keep their
-// code; the loops, the element-to-lane mapping and adamw_elem are the same, so a device value equal to the host value gives the same bits.
-template <typename T, typename G>
-__global__ __launch_bounds__(256) void adamw_ds_kernel(float* p, T* p_model, const G* g, float* m, float* v, long long n, float lr, float b1,
-                                                       float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* gscale_dev) {
-    const float gscale = *gscale_dev;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float pi = p[i], mi = m[i], vi = v[i];
-        adamw_elem(pi, mi, vi, adamw_g<G>(g, i), lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (p_model) Cvt<T>::st(p_model + i, pi);
-    }
-}
-
-template <typename T, typename G>
-__global__ __launch_bounds__(256) void adamw_vec4_ds_kernel(float* p, T* p_model, const G* g, float* m, float* v, long long n4, float lr, float b1,
-                                                            float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* gscale_dev) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    const float gscale = *gscale_dev;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        f32x4 g4;
-        if constexpr (sizeof(G) == 4) g4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
-        else {
-            const u32x2 r = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(g) + i);
-            g4[0] = __uint_as_float(r[0] << 16); g4[1] = __uint_as_float(r[0] & 0xFFFF0000u);
-            g4[2] = __uint_as_float(r[1] << 16); g4[3] = __uint_as_float(r[1] & 0xFFFF0000u);
-        }
-        f32x4 p4 = reinterpret_cast<f32x4*>(p)[i], m4 = reinterpret_cast<f32x4*>(m)[i], v4 = reinterpret_cast<f32x4*>(v)[i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float pi = p4[j], mi = m4[j], vi = v4[j];
-            adamw_elem(pi, mi, vi, g4[j], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
-            p4[j] = pi; m4[j] = mi; v4[j] = vi;
-        }
-        reinterpret_cast<f32x4*>(p)[i] = p4; reinterpret_cast<f32x4*>(m)[i] = m4; reinterpret_cast<f32x4*>(v)[i] = v4;
-        if (p_model) {
-            T o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) Cvt<T>::st(o + j, p4[j]);
-            typedef T tx4 __attribute__((ext_vector_type(4)));
-            reinterpret_cast<tx4*>(p_model)[i] = tx4{o[0], o[1], o[2], o[3]};
-        }
-    }
-}
-
-template <typename G>
-static int adamw_ds_launch(float* master, void* model_copy, const G* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                           float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype, hipStream_t stream) {
-    if (!master || !grad || !m || !v || !grad_scale_dev) return EGOMI_E_BADARG;
-    if (n <= 0 || step <= 0) return EGOMI_E_SHAPE;
-    if (model_copy && copy_dtype != EGOMI_F32 && copy_dtype != EGOMI_BF16) return EGOMI_E_BADARG;
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2s = sqrtf(1.0f - powf(beta2, (float)step));
-    const long long n4 = n / 4, rest = n - 4 * n4;
-    const bool vec = n4 > 0 && (((uintptr_t)master | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && ((uintptr_t)grad & (4 * sizeof(G) - 1)) == 0 &&
-                     (!model_copy || (copy_dtype == EGOMI_BF16 && ((uintptr_t)model_copy & 7) == 0));
-    if (vec) {
-        EGOMI_LAUNCH((adamw_vec4_ds_kernel<bf16_t, G>), dim3(ew_grid(n4)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
-                           n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev);
-        if (rest == 0) return egomi_launch_status();
-        master += 4 * n4; grad += 4 * n4; m += 4 * n4; v += 4 * n4; n = rest;
-        if (model_copy) model_copy = (bf16_t*)model_copy + 4 * n4;
-    }
-    if (!model_copy || copy_dtype == EGOMI_F32)
-        EGOMI_LAUNCH((adamw_ds_kernel<float, G>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (float*)model_copy, grad, m, v,
-                           (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev);
-    else
-        EGOMI_LAUNCH((adamw_ds_kernel<bf16_t, G>), dim3(ew_grid(n)), dim3(256), 0, stream, master, (bf16_t*)model_copy, grad, m, v,
-                           (long long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev);
-    return egomi_launch_status();
-}
-
 extern "C" int egomi_adamw_ds(float* master, void* model_copy, const float* grad, float* m, float* v, int64_t n, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype,
                               egomi_stream_t stream) {
-    return adamw_ds_launch<float>(master, model_copy, grad, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, copy_dtype,
-                                  (hipStream_t)stream);
+    return adamw_launch<float>(master, model_copy, grad, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, copy_dtype, (hipStream_t)stream);
 }
 extern "C" int egomi_adamw_g16_ds(float* master, void* model_copy, const void* grad_bf16, float* m, float* v, int64_t n, float lr, float beta1,
                                   float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev, int copy_dtype,
                                   egomi_stream_t stream) {
-    return adamw_ds_launch<bf16_t>(master, model_copy, (const bf16_t*)grad_bf16, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev,
-                                   copy_dtype, (hipStream_t)stream);
+    return adamw_launch<bf16_t>(master, model_copy, (const bf16_t*)grad_bf16, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, copy_dtype,
+                                (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------

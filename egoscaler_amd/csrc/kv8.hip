@@ -87,7 +87,7 @@ extern "C" int egomi_kv_append_fp8(const void* k, const void* v, int64_t ld, uin
 
 // ------------------------------------------------------------------------------------------------
 // qkv_finish_fp8: qkv_finish_kernel (decode.hip) with k and v quantised into the fp8 caches at `pos`.  q|k|v = round(sum of the slabs),
-// RoPE(pos) on q and k with the bf16 kernel's rounding sequence (the same code, qkv_finish.h), q -> qkv (bit-equal to qkv_finish).  One thread per 8 rotation pairs
+// RoPE(pos) on q and k with the bf16 kernel's rounding sequence (the same code: qkv_finish.h, on the pieces of row_pieces.h), q -> qkv (bit-equal to qkv_finish).  One thread per 8 rotation pairs
 // (columns i..i+7 and half+i..half+i+7 of a head): the CPV = hd / 16 threads of a head are consecutive lanes, amax is a CPV-lane
 // shuffle reduction.
 // ------------------------------------------------------------------------------------------------
@@ -113,10 +113,8 @@ __global__ __launch_bounds__(256) void qkv_finish_fp8_kernel(const float* slabs,
         }
         // parts are uniform over a head's CPV lanes, but the q group's lanes take part in no shuffle of another group: every lane
         // computes amax, the q lanes just do not store
-        if (sizeof(T) == 2) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { oa[j] = bf2f(f2bf(oa[j])); ob[j] = bf2f(f2bf(ob[j])); }    // what the bf16 cache would hold
-        }
+        round_as_stored8<T>(oa);                                     // what the bf16 cache would hold
+        round_as_stored8<T>(ob);
         float am = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) am = fmaxf(am, fmaxf(fabsf(oa[j]), fabsf(ob[j])));
