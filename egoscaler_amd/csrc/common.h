@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/egomi.h"
 
 typedef uint16_t bf16_t;   // raw bf16 storage
@@ -134,7 +135,13 @@ static inline int egomi_launch_status() {
     return e ? EGOMI_E_LAUNCH : EGOMI_OK;
 }
 
-#define EGOMI_DISPATCH_DTYPE(dtype, ...)                         \
+// an integer switch of the environment (A/B runs, tests).  Read once per process: `static const int on = egomi_env_int("EGOMI_X", 1);`
+static inline int egomi_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+#define EGOMI_DISPATCH_DTYPE(dtype, ...)                        \
     do {                                                         \
         if ((dtype) == EGOMI_F32) { typedef float T; __VA_ARGS__; }        \
         else if ((dtype) == EGOMI_BF16) { typedef bf16_t T; __VA_ARGS__; } \

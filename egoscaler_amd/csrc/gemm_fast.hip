@@ -17,10 +17,13 @@
 //     consecutive output columns
 //   * rows beyond M / N are clamped on load and masked on store; K % 64 == 0
 //   * XCD-aware block order: each XCD walks a contiguous strip of tiles, grouped 8 M-tiles deep (T1)
+//   Host code (end of the file): the per-form rules and launches, then gemm_route() — the one decision which form runs a product, with
+//   its K slices, tail rows and split column — which egomi_gemm_fast_try launches and the three queries (kernel id, slab count, tail plan) report.
 #include "common.h"
+#include <map>
 #include <mutex>
 #include <queue>
-#include <unordered_map>
+#include <tuple>
 #include <vector>
 
 #define FT_BK 64
@@ -1561,10 +1564,30 @@ static bool fast_applicable(const egomi_gemm_desc* d) {
     return true;
 }
 
+// the 256-row forms address both operands with 31-bit element offsets
+static bool spans_fit_31(const egomi_gemm_desc* d) { return (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31); }
+
+// The caller's scratch as the launches use it: slabs behind the 4 KB of ticket words when ws_tickets_zeroed says they are there (*tickets, else
+// null).  false: no scratch, or nothing behind the ticket words (*slabs = null); what follows from that is the call site's business.  Also used by gemm_tn.hip.
+bool egomi_scratch_slabs(const egomi_gemm_desc* d, int** tickets, char** slabs, long long* bytes) {
+    *tickets = nullptr; *slabs = (char*)d->workspace; *bytes = d->workspace_bytes;
+    if (d->ws_tickets_zeroed && d->workspace) {
+        if (d->workspace_bytes > 4096) { *tickets = (int*)d->workspace; *slabs += 4096; *bytes -= 4096; }
+        else { *slabs = nullptr; *bytes = 0; }
+    }
+    return *slabs != nullptr;
+}
+
+// EGOMI_EPI_SLABS (include/egomi.h): plain bf16 product only — everything an epilogue could do is the consumer kernel's job.  `tail_rows`: the
+// 256-row forms, which leave only K-sliced tail rows as slabs (bf16 out; whole tiles keep the residual); else every row is left, M <= 512
+static bool plain_slabs(const egomi_gemm_desc* d, bool tail_rows) {
+    if (d->bias || d->accumulate || d->act != 0 || d->alpha != 1.0f) return false;
+    return tail_rows ? d->c_dtype == EGOMI_BF16 && (d->N & 7) == 0 : !d->residual && d->workspace && d->M <= 512 && (d->N & 3) == 0;
+}
+
 // tile choice: 8 = 256x256 8-phase kernel, 2 = 256x128, 1 = 128x128.  EGOMI_GEMM_TILE=1|2|8 overrides (A/B runs).
 static int tile_choice(const egomi_gemm_desc* d) {
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("EGOMI_GEMM_TILE"); forced = e ? atoi(e) : 0; }
+    static const int forced = egomi_env_int("EGOMI_GEMM_TILE", 0);
     if (forced == 1 || forced == 2 || forced == 8) return forced;
     // measured (tools/gemm_bench.py, M=5536): 256x128 wins only where N is wide enough to keep every CU at
     // 2 resident blocks to the end (N=11008: 1168 vs 1084 TFLOP/s); at N=4096 its 704 tiles quantise worse
@@ -1572,41 +1595,26 @@ static int tile_choice(const egomi_gemm_desc* d) {
     // 256x256 8-phase kernel (tools/gemm_bench.py: 1.06-1.32 PFLOP/s at M=5536, 1.3-1.49 at M=8192 vs ~1.0-1.1): needs
     // enough tiles to occupy the chip at one block per CU and a K long enough to amortise its prologue/epilogue
     const long long t256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256);
-    if (t256 >= 128 && d->K >= 2048 && (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) return 8;
+    if (t256 >= 128 && d->K >= 2048 && spans_fit_31(d)) return 8;
     // many tiles make up for a shorter K (lm_head wgrad of the step: 32262 x 4096 x 1280 = 2032 tiles, fp32 out: 365 vs 474 us,
     // tools/debug/lmhead_wgrad_probe.py)
-    if (t256 >= 512 && d->K >= 1024 && (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) return 8;
+    if (t256 >= 512 && d->K >= 1024 && spans_fit_31(d)) return 8;
     // few tiles but a very long K (the lm_head dgrad of the training step: 1280 x 4096 x 32320 = 80 tiles): every tile row K-sliced
     // (plan_tail with rows = all) fills the chip — tools/debug/lmhead_dgrad_probe.py: 313 us (S = 6) vs 482 us on the 128x128 kernel
     if (t256 >= 32 && t256 < 128 && d->K >= 8192 && d->M > 512 && d->epilogue == EGOMI_EPI_NONE && d->workspace &&
-        d->workspace_bytes >= (long long)((d->M + 255) / 256) * 256 * d->N * 4 * 2 + 4096 &&
-        (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) return 8;
+        d->workspace_bytes >= (long long)((d->M + 255) / 256) * 256 * d->N * 4 * 2 + 4096 && spans_fit_31(d)) return 8;
     // whole tiles asked for (split_k = 1: no K-sliced rows) at few tiles: the 8-phase kernel, in which every element accumulates its K-tiles in the
     // order of the 352x256 form (tests/test_gpu_gemm_tall.py).  The windowed top decoder layer (M = 8 x 153 = 1224, 80 tiles at N = 4096) asks for it
     // so that its rows keep the bits they have in the M = 5536 products of the layers below; it is not the fastest route at this height
     // (profiles/top_rows_gemm_shapes.txt, cold weights, N = 4096: K = 4096 + residual 88.2 vs 68.6 us on the 128x128 kernel, K = 4096 plain 71.4 vs 62.6,
     // K = 11008 + residual 199.7 vs 136.0 and K = 22016 365.1 vs 233.7 with all rows K-sliced), which is why it is taken on request only
-    if (d->split_k == 1 && t256 >= 32 && t256 < 128 && d->K >= 2048 && d->M > 512 &&
-        (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) return 8;
+    if (d->split_k == 1 && t256 >= 32 && t256 < 128 && d->K >= 2048 && d->M > 512 && spans_fit_31(d)) return 8;
     return (d->M >= 2048 && d->N >= 8192) ? 2 : 1;
 }
 
-extern "C" int egomi_gemm_tn_kernel_id(const egomi_gemm_desc* d);      // gemm_tn.hip: 3 when the k-major 8-phase kernel takes the product
-extern "C" int egomi_gemm_kernel_id(const egomi_gemm_desc* d) {
-    if (!d) return EGOMI_E_BADARG;
-    if (!d->force_generic && !fast_applicable(d)) return egomi_gemm_tn_kernel_id(d);
-    if (d->force_generic || !fast_applicable(d)) return 0;
-    return tile_choice(d) == 8 ? 2 : 1;
-}
-
-static bool slabs_form_ok(const egomi_gemm_desc* d);
-static int skinny_splitk(const egomi_gemm_desc* d, int nwg);
-static bool gemv_form(const egomi_gemm_desc* d);
-static int gemv_splitk(const egomi_gemm_desc* d);
 // 128 < M <= 256 with a long K and enough columns: the all-rows ring kernel (gemm_nt_bf16_m256_kernel).  EGOMI_GEMM_M256=0: the 128x128 kernel (A/B runs)
 static bool m256_form(const egomi_gemm_desc* d) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("EGOMI_GEMM_M256"); on = e ? atoi(e) : 1; }
+    static const int on = egomi_env_int("EGOMI_GEMM_M256", 1);
     // N >= 8192 (q|k|v, gate|up, lm_head): measured per shape (tools/gemm_bench_decode.py, M = 256): 41 vs 44 us, 57 vs 61, 77 vs 90; the N = 4096 products
     // (o_proj, down_proj: 32 column tiles x 8 K-slices of 8-22 steps) are dominated by per-block fixed cost and stay on the 128x128 kernel (24.7 vs 21.9 us)
     return on && d->M > 128 && d->M <= 256 && d->N >= 8192 && d->K >= 1024;
@@ -1620,12 +1628,6 @@ static int m256_splitk(const egomi_gemm_desc* d) {
     if ((long long)sk * per_slab > d->workspace_bytes) sk = (int)(d->workspace_bytes / per_slab);
     if (sk > 1) { const int per = (nt + sk - 1) / sk; sk = (nt + per - 1) / per; }     // no empty slices
     return sk > 1 ? sk : 1;
-}
-extern "C" int egomi_gemm_slab_count(const egomi_gemm_desc* d) {
-    if (!d) return EGOMI_E_BADARG;
-    if (d->force_generic || !fast_applicable(d) || !slabs_form_ok(d) || tile_choice(d) != 1) return 0;
-    const int sk = gemv_form(d) ? gemv_splitk(d) : (m256_form(d) ? m256_splitk(d) : skinny_splitk(d, ((d->M + 127) / 128) * ((d->N + 127) / 128)));
-    return sk >= 2 ? sk : 0;
 }
 
 // skinny products (decode, M <= 512): too few tiles to fill 256 CUs and each block is DMA-latency bound, so the K range is
@@ -1648,8 +1650,7 @@ static int skinny_splitk(const egomi_gemm_desc* d, int nwg) {
 
 // M <= 16 (gemv_m16_kernel).  EGOMI_GEMM_GEMV=0: the 128x128 kernel (A/B runs)
 static bool gemv_form(const egomi_gemm_desc* d) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("EGOMI_GEMM_GEMV"); on = e ? atoi(e) : 1; }
+    static const int on = egomi_env_int("EGOMI_GEMM_GEMV", 1);
     return on && d->M <= 16 && d->K >= 1024 && d->K % 128 == 0 && d->N >= 64 && (d->epilogue == EGOMI_EPI_NONE || d->epilogue == EGOMI_EPI_SLABS);
 }
 static int gemv_splitk(const egomi_gemm_desc* d) {
@@ -1665,81 +1666,47 @@ static int gemv_splitk(const egomi_gemm_desc* d) {
     if ((long long)sk * per_slab > d->workspace_bytes) sk = (int)(d->workspace_bytes / per_slab);
     return sk > 1 ? sk : 1;
 }
-static int launch_gemv(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s) {
-    g.tiles_m = 1; g.tiles_n = (d->N + GV_BN - 1) / GV_BN;
-    g.ws = (float*)d->workspace;
-    g.splitk = gemv_splitk(d);
-    if (d->epilogue == EGOMI_EPI_SLABS && g.splitk < 2) return EGOMI_E_UNSUPPORTED;     // egomi_gemm_slab_count said so
-    if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(gemv_m16_kernel<bf16_t>, dim3(g.tiles_n, g.splitk), dim3(256), 0, s, g);
-    else if (d->c_dtype == EGOMI_F32) EGOMI_LAUNCH(gemv_m16_kernel<float>, dim3(g.tiles_n, g.splitk), dim3(256), 0, s, g);
-    else return EGOMI_E_UNSUPPORTED;
-    if (g.splitk > 1 && d->epilogue != EGOMI_EPI_SLABS) {
-        const long long total = (long long)d->M * ((d->N + 3) / 4);
-        const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, g);
-        else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, g);
-    }
-    egomi_route_set(4, g.splitk, d->M, 0, 0);
-    return egomi_launch_status();
-}
 
-static int launch_m256(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s) {
-    g.tiles_m = 1; g.tiles_n = (d->N + 127) / 128;
-    g.ws = (float*)d->workspace;
-    g.splitk = m256_splitk(d);
-    if (d->epilogue == EGOMI_EPI_SLABS && g.splitk < 2) return EGOMI_E_UNSUPPORTED;     // egomi_gemm_slab_count said so
-    if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(gemm_nt_bf16_m256_kernel<bf16_t>, dim3(g.tiles_n, g.splitk), dim3(512), 0, s, g);
-    else if (d->c_dtype == EGOMI_F32) EGOMI_LAUNCH(gemm_nt_bf16_m256_kernel<float>, dim3(g.tiles_n, g.splitk), dim3(512), 0, s, g);
-    else return EGOMI_E_UNSUPPORTED;
-    if (g.splitk > 1 && d->epilogue != EGOMI_EPI_SLABS) {                // EGOMI_EPI_SLABS: the caller's next kernel sums the slabs
-        const long long total = (long long)d->M * ((d->N + 3) / 4);
-        const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, g);
-        else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, g);
-    }
-    egomi_route_set(5, g.splitk, d->M, 0, 0);
-    return egomi_launch_status();
-}
+// ---- launches.  The forms a product can take (gemm_route below), numbered as egomi_gemm_last_route reports them
+enum { FORM_UNSUPPORTED = -1, FORM_NA = 0, FORM_128 = 2, FORM_256x128 = 3, FORM_GEMV = 4, FORM_M256 = 5, FORM_8PHASE = 6, FORM_P8 = 7, FORM_TALL = 8, FORM_SPLIT = 9 };
 
-template <int BM, int BN>
-static int launch_fast(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s) {
-    if (BM == 128 && BN == 128 && gemv_form(d)) return launch_gemv(d, g, s);
-    if (BM == 128 && BN == 128 && m256_form(d)) return launch_m256(d, g, s);
-    g.tiles_m = (d->M + BM - 1) / BM; g.tiles_n = (d->N + BN - 1) / BN;
-    const int nwg = g.tiles_m * g.tiles_n;
-    constexpr int threads = (BM / 64) * (BN / 64) * 64;
-    g.ws = (float*)d->workspace;
-    g.splitk = skinny_splitk(d, nwg);
-    if (d->epilogue == EGOMI_EPI_SLABS && g.splitk < 2) return EGOMI_E_UNSUPPORTED;     // egomi_gemm_slab_count said so
-    static int pf_env = -1;                                            // EGOMI_GEMM_PF=0: one LDS stage (A/B switch)
-    if (pf_env < 0) { const char* e = getenv("EGOMI_GEMM_PF"); pf_env = e ? atoi(e) : 1; }
-    if (d->c_dtype != EGOMI_BF16 && d->c_dtype != EGOMI_F32) return EGOMI_E_UNSUPPORTED;
-    if (BM == 128 && BN == 128 && pf_env) {
-        if constexpr (BM == 128 && BN == 128) {
-            if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH((gemm_nt_bf16_kernel<bf16_t, 128, 128, 2>), dim3(nwg, g.splitk), dim3(threads), 0, s, g);
-            else EGOMI_LAUNCH((gemm_nt_bf16_kernel<float, 128, 128, 2>), dim3(nwg, g.splitk), dim3(threads), 0, s, g);
-        }
-    } else if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH((gemm_nt_bf16_kernel<bf16_t, BM, BN, 1>), dim3(nwg, g.splitk), dim3(threads), 0, s, g);
-    else EGOMI_LAUNCH((gemm_nt_bf16_kernel<float, BM, BN, 1>), dim3(nwg, g.splitk), dim3(threads), 0, s, g);
-    if (g.splitk > 1 && d->epilogue != EGOMI_EPI_SLABS) {                // EGOMI_EPI_SLABS: the caller's next kernel sums the slabs
-        const long long total = (long long)d->M * ((d->N + 3) / 4);
-        const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, g);
-        else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, g);
-    }
-    egomi_route_set(BM == 256 ? 3 : 2, g.splitk, d->M, 0, 0);
-    return egomi_launch_status();
+// the kernels of the forms that cut K over blockIdx.y, on (column tiles, g.splitk) blocks; launch_sliced (below) is the frame around them
+static void run_gemv(FastArgs& g, bool bf16, hipStream_t s) {
+    g.tiles_m = 1; g.tiles_n = (g.N + GV_BN - 1) / GV_BN;
+    if (bf16) EGOMI_LAUNCH(gemv_m16_kernel<bf16_t>, dim3(g.tiles_n, g.splitk), dim3(256), 0, s, g);
+    else EGOMI_LAUNCH(gemv_m16_kernel<float>, dim3(g.tiles_n, g.splitk), dim3(256), 0, s, g);
+}
+// the combine pass over the r.splitk slabs of r.M rows (splitk_reduce_kernel); `c_dtype` is EGOMI_BF16 or EGOMI_F32
+static int combine_grid(long long items) { return (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096); }
+static void launch_combine(const FastArgs& r, int c_dtype, hipStream_t s) {
+    const int grid = combine_grid((long long)r.M * ((r.N + 3) / 4));
+    if (c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, r);
+    else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, r);
+}
+// rows >= row0 of a product as a product of their own, for the combine pass over their `slices` slabs: C and the residual start at row0
+static FastArgs tail_rows_view(const FastArgs& g, long long row0, int slices, int c_dtype) {
+    const int esz = c_dtype == EGOMI_BF16 ? 2 : 4;
+    FastArgs r = g;
+    r.M = g.M - (int)row0; r.splitk = slices;
+    r.C = (char*)g.C + row0 * g.ldc * esz;
+    if (g.residual) r.residual = (const char*)g.residual + row0 * g.ldr * esz;
+    return r;
+}
+static void run_m256(FastArgs& g, bool bf16, hipStream_t s) {
+    g.tiles_m = 1; g.tiles_n = (g.N + 127) / 128;
+    if (bf16) EGOMI_LAUNCH(gemm_nt_bf16_m256_kernel<bf16_t>, dim3(g.tiles_n, g.splitk), dim3(512), 0, s, g);
+    else EGOMI_LAUNCH(gemm_nt_bf16_m256_kernel<float>, dim3(g.tiles_n, g.splitk), dim3(512), 0, s, g);
 }
 
 // ---- ragged last round.  One 256x256 block per CU means ceil(tiles / 256) rounds; at M = 5536, N = 4096 that is 2
 // rounds for 1.375 rounds of work.  The last `rows` tile rows are therefore cut into S K-slices (fp32 slabs of those rows
 // only, combined by splitk_reduce_kernel): short blocks that the dispatcher packs into the last round.  (rows, S) come from
-// a list-scheduling model in K-tile units, cached per shape.
+// a list-scheduling model in K-tile units, cached per shape and scratch size (the slabs of a candidate must fit it).
 struct TailPlan { int rows, s; };
 static TailPlan plan_tail(int M, int N, int K, long long ws_bytes) {
     static std::mutex mu;
-    static std::unordered_map<unsigned long long, TailPlan> cache;
-    const unsigned long long key = ((unsigned long long)M << 42) ^ ((unsigned long long)N << 21) ^ (unsigned long long)K ^ (ws_bytes ? 1ull << 63 : 0);
+    static std::map<std::tuple<int, int, int, long long>, TailPlan> cache;
+    const auto key = std::make_tuple(M, N, K, ws_bytes);
     {
         std::lock_guard<std::mutex> lk(mu);
         auto it = cache.find(key);
@@ -1781,14 +1748,11 @@ void egomi_plan_tail_rows(int M, int N, int K, long long ws_bytes, int* rows, in
     const TailPlan tp = plan_tail(M, N, (K + FT_BK - 1) / FT_BK * FT_BK, ws_bytes);
     *rows = tp.rows; *slices = tp.s;
 }
-int egomi_splitk_reduce_rows(void* C, int c_dtype, long long ldc, int rows, int N, const float* ws, int slices, int accumulate, hipStream_t s) {
-    FastArgs r = {};
-    r.C = C; r.ldc = ldc; r.M = rows; r.N = N; r.ws = const_cast<float*>(ws); r.splitk = slices; r.accumulate = accumulate; r.alpha = 1.0f;
-    const long long total = (long long)rows * ((N + 3) / 4);
-    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    if (c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, r);
-    else if (c_dtype == EGOMI_F32) EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, r);
-    else return EGOMI_E_UNSUPPORTED;
+int egomi_splitk_reduce_rows(void* C, int c_dtype, long long ldc, int M, int row0, int N, const float* ws, int slices, int accumulate, hipStream_t s) {
+    if (c_dtype != EGOMI_BF16 && c_dtype != EGOMI_F32) return EGOMI_E_UNSUPPORTED;
+    FastArgs g = {};
+    g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.ws = const_cast<float*>(ws); g.accumulate = accumulate; g.alpha = 1.0f;
+    launch_combine(tail_rows_view(g, row0, slices, c_dtype), c_dtype, s);
     return egomi_launch_status();
 }
 
@@ -1803,16 +1767,17 @@ static int p8_cus() {
     }
     return n;
 }
-static bool p8_applicable(const egomi_gemm_desc* d, P8Sched& sc) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("EGOMI_GEMM_PERSIST"); off = (e && atoi(e) == 0) ? 1 : 0; }
-    if (off || !d->workspace || !d->ws_tickets_zeroed || d->split_k > 0) return false;
+// EGOMI_GEMM_PERSIST: 0 never, 2 wherever it can run, anything else (default): where the caller asks for it (ws_tickets_zeroed = 2)
+static int persist_mode() { static const int mode = egomi_env_int("EGOMI_GEMM_PERSIST", 1); return mode; }
+// `d`: workspace = the slab area behind the ticket words `tickets` (egomi_scratch_slabs)
+static bool p8_applicable(const egomi_gemm_desc* d, int* tickets, P8Sched& sc) {
+    if (persist_mode() == 0 || !tickets || d->split_k > 0) return false;
     const int nt = d->K / FT_BK;
     if (nt < 4 || (nt & 1)) return false;
     const int tm = (d->M + 255) / 256, tn = (d->N + 255) / 256;
     const long long T = (long long)tm * tn;
     sc.G = p8_cus();
-    if ((long long)4096 + (long long)sc.G * 2 * 262144 > d->workspace_bytes) return false;
+    if ((long long)sc.G * 2 * 262144 > d->workspace_bytes) return false;
     sc.full_rounds = (int)(T / sc.G); sc.R = (int)(T % sc.G); sc.nt = nt; sc.pp = nt / 2;
     if (sc.full_rounds + 2 > P8S_MAX_ITEMS || sc.R > 1000) return false;
     // Selection.  Measured at M = 5536 on one box, A/B in one process:
@@ -1823,15 +1788,13 @@ static bool p8_applicable(const egomi_gemm_desc* d, P8Sched& sc) {
     //     its launches averaging 441.6 us vs 417.4 — the static assignment cannot re-balance around slow HBM fetches the way
     //     the dispatcher does when it hands out one tile at a time, and the stream-K remainder walks K out of step (L2 misses).
     // So the library's own rule never picks it; ws_tickets_zeroed = 2 (ops.mm(persistent=True)) or EGOMI_GEMM_PERSIST=2 do.
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("EGOMI_GEMM_PERSIST"); force = (e && atoi(e) == 2) ? 1 : 0; }
-    if (!force && d->ws_tickets_zeroed != 2) return false;
+    if (persist_mode() != 2 && d->ws_tickets_zeroed != 2) return false;
     sc.P = sc.R * sc.pp;
     sc.Gr = sc.R == 0 ? 8 : (sc.G < 4 * sc.R ? sc.G : 4 * sc.R);          // <= ~4 sharers per remainder tile
     if (sc.P > 0 && sc.Gr > sc.P) sc.Gr = sc.P;
     if (sc.Gr >= 8) sc.Gr &= ~7;                                             // multiple of 8: remainder ranges follow the XCD order too
-    sc.tickets = (int*)d->workspace;
-    sc.slabs = (float*)((char*)d->workspace + 4096);
+    sc.tickets = tickets;
+    sc.slabs = (float*)d->workspace;
     return true;
 }
 static int launch_p8(const egomi_gemm_desc* d, FastArgs& g, const P8Sched& sc, hipStream_t s) {
@@ -1842,7 +1805,7 @@ static int launch_p8(const egomi_gemm_desc* d, FastArgs& g, const P8Sched& sc, h
     if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(gemm_nt_bf16_p8_kernel<bf16_t>, dim3(grid), dim3(512), 0, s, g, sc);
     else if (d->c_dtype == EGOMI_F32) EGOMI_LAUNCH(gemm_nt_bf16_p8_kernel<float>, dim3(grid), dim3(512), 0, s, g, sc);
     else return EGOMI_E_UNSUPPORTED;
-    egomi_route_set(7, 1, d->M, 0, 0);
+    egomi_route_set(FORM_P8, 1, d->M, 0, 0);
     return egomi_launch_status();
 }
 
@@ -1852,48 +1815,78 @@ static int launch_p8(const egomi_gemm_desc* d, FastArgs& g, const P8Sched& sc, h
 //   352x256 plan: 1.31 per round of its own tiles (1.375 x the flops; 0.34 instead of 0.375 ds_read per MFMA and 12 instead of 16 barriers per 128 MFMAs)
 //   N = 4096: K = 4096 183.5 -> 158.8 us, K = 11008 404.9 -> 355.9, K = 12288 452.7 -> 382.1, K = 22016 758.0 -> 712.7; N = 12288 425.9 -> 399.9;
 //   N = 11008 / 22016 (0.70 / 0.39 of a round left over, 688 / 1376 tall tiles = 2.69 / 5.375 rounds): 373.8 vs 376.2, 746.9 vs 753.1 — stay on the 256x256 form
-static int g_tall_mode = -1;
+static int g_tall_mode = -1;                                             // -1: EGOMI_GEMM_TALL is (re)read at the next use
 extern "C" int egomi_gemm_set_tall(int mode) { g_tall_mode = mode < 0 ? -1 : (mode > 2 ? 2 : mode); return EGOMI_OK; }
+static int tall_mode() {
+    if (g_tall_mode < 0) { g_tall_mode = egomi_env_int("EGOMI_GEMM_TALL", 1); if (g_tall_mode < 0 || g_tall_mode > 2) g_tall_mode = 1; }
+    return g_tall_mode;
+}
+// the 256x256 plan of `tiles` tiles, in rounds; `ws`: scratch for K-sliced rows in a ragged last round
+static double c256_model(long long tiles, bool ws) {
+    const int ncu = p8_cus();                                            // CUs of this device (256 on MI355X in SPX mode)
+    const int rem = (int)(tiles % ncu);
+    return (double)(tiles / ncu) + (rem ? (rem * 2 <= ncu && ws ? 0.28 + 0.85 * rem / ncu : 1.0) : 0.0);
+}
 static bool tall_form(const egomi_gemm_desc* d) {
-    if (g_tall_mode < 0) { const char* e = getenv("EGOMI_GEMM_TALL"); g_tall_mode = e ? atoi(e) : 1; if (g_tall_mode < 0 || g_tall_mode > 2) g_tall_mode = 1; }
-    const int mode = g_tall_mode;
+    const int mode = tall_mode();
     if (!mode) return false;
     if (d->epilogue != EGOMI_EPI_NONE && d->epilogue != EGOMI_EPI_SLABS && d->epilogue != EGOMI_EPI_SWIGLU && d->epilogue != EGOMI_EPI_SWIGLU_BWD) return false;
     if ((d->M & 7) || (d->N & 7) || d->M < TL_BM || d->N < 256 || d->K < 2048 || d->split_k > 1) return false;      // (split_k = 1: "no K-sliced rows", the tests' way to compare whole tiles of both forms)
-    if ((long long)d->M * d->lda >= (1ll << 31) || (long long)d->N * d->ldb >= (1ll << 31)) return false;
+    if (!spans_fit_31(d)) return false;
     if (d->c_dtype != EGOMI_BF16 && d->c_dtype != EGOMI_F32) return false;
     if (mode == 2) return true;
-    const int ncu = p8_cus();                                            // CUs of this device (256 on MI355X in SPX mode)
     const long long tn = (d->N + 255) / 256;
     const long long t256 = (long long)((d->M + 255) / 256) * tn, t352 = (long long)((d->M + TL_BM - 1) / TL_BM) * tn;
-    const int rem = (int)(t256 % ncu);
-    const double c256 = (double)(t256 / ncu) + (rem ? (rem * 2 <= ncu && d->workspace ? 0.28 + 0.85 * rem / ncu : 1.0) : 0.0);
+    const int ncu = p8_cus();
     const double c352 = 1.31 * (double)((t352 + ncu - 1) / ncu);
-    return c352 < 0.98 * c256;
+    return c352 < 0.98 * c256_model(t256, d->workspace != nullptr);
 }
+
 static int launch_tall(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
     g.tiles_m = (d->M + TL_BM - 1) / TL_BM; g.tiles_n = (d->N + 255) / 256;
     g.splitk = 1; g.ws = nullptr; g.tickets = nullptr;
-    if (g.epi == EGOMI_EPI_SLABS) g.epi = 0;                          // (a product in this form has no K-sliced rows to leave as slabs)
-    static int gdepth = -1;
-    if (gdepth < 0) { const char* e = getenv("EGOMI_TALL_GROUP"); gdepth = e ? atoi(e) : 8; if (gdepth < 1) gdepth = 8; }
-    g.full_tm = gdepth;
+    static const int group = egomi_env_int("EGOMI_TALL_GROUP", 8);
+    g.full_tm = group < 1 ? 8 : group;
     const int nwg = g.tiles_m * g.tiles_n;
     if (t0) (void)hipEventRecord(t0, s);
     if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH((gemm_nt_bf16_tall_kernel<bf16_t, false>), dim3(nwg), dim3(512), 0, s, g);
     else EGOMI_LAUNCH((gemm_nt_bf16_tall_kernel<float, false>), dim3(nwg), dim3(512), 0, s, g);
     if (t1) (void)hipEventRecord(t1, s);
-    egomi_route_set(8, 1, d->M, 0, 0);
+    egomi_route_set(FORM_TALL, 1, d->M, 0, 0);
     return egomi_launch_status();
 }
 
+// ---- column split: the 352x256 form on the first Na columns (whole rounds), the 256x256 form on the rest.  Products whose tiles fit neither
+// form in whole rounds: gate|up at M = 5536 (N = 22016: 1892 tiles of 256x256 = 7.39 rounds; 16 x 86 tall tiles = 5.375) runs as 16 x 64 tall tiles
+// (4 rounds) + 22 x 22 tiles of 256x256 (1.89 rounds), the down_proj data gradient (N = 11008: 3.70 / 2.69 rounds) as 16 x 32 tall (2 rounds) +
+// 22 x 11 (0.95 rounds).  Same round model as tall_form(); both parts carry the product's epilogue (plain, SwiGLU, SwiGLU backward); the second
+// part plans its own K-sliced tail.  Na is a multiple of 256 columns, so interleaved-32 gate|up groups and 64-column wave strips stay whole.
+// -> Na, 0: no split.  EGOMI_GEMM_SPLIT=0: never (A/B runs)
+static int split_cols(const egomi_gemm_desc* d) {
+    static const int on = egomi_env_int("EGOMI_GEMM_SPLIT", 1);
+    if (tall_mode() != 1 || !on) return 0;                             // (mode 2 = "the tall form wherever it applies" is the whole-product A/B arm)
+    if (d->epilogue != EGOMI_EPI_NONE && d->epilogue != EGOMI_EPI_SWIGLU && d->epilogue != EGOMI_EPI_SWIGLU_BWD) return 0;
+    if ((d->M & 7) || (d->N & 255) || d->M < TL_BM || d->K < 2048 || d->split_k > 0 || d->bias) return 0;
+    if (!spans_fit_31(d)) return 0;
+    if (d->c_dtype != EGOMI_BF16 && d->c_dtype != EGOMI_F32) return 0;
+    const int ncu = p8_cus();                                            // CUs of this device (256 on MI355X in SPX mode)
+    const long long tn = d->N / 256, tm256 = (d->M + 255) / 256, tm352 = (d->M + TL_BM - 1) / TL_BM;
+    const double c0 = c256_model(tm256 * tn, d->workspace != nullptr);
+    double best = 0.97 * c0;
+    int ja_best = 0;
+    for (long long ja = 1; ja < tn; ++ja) {
+        if ((tm352 * ja) % ncu) continue;                                // the tall part: whole rounds only
+        const double c = 1.31 * (double)(tm352 * ja / ncu) + c256_model(tm256 * (tn - ja), d->workspace != nullptr) + 0.03;
+        if (c < best) { best = c; ja_best = (int)ja; }
+    }
+    return ja_best * 256;
+}
+
 int egomi_gemm_tn_rest(const egomi_gemm_desc* d, hipStream_t s);        // gemm_tn.hip: its 256x256 kernel, without trying this form again
-static int split_cols(const egomi_gemm_desc* d);
 // data gradient against a k-major weight (a_layout 0, b_layout 1; called by gemm_tn.hip before its own 256x256 kernel): the 352x256 form where the round
 // model prefers it.  -> 0 launched, 1 not applicable, < 0 error.  `query`: decide only.
 int egomi_tall_kmajor_try(const egomi_gemm_desc* d, hipStream_t s, bool query) {
-    static int on = -1;                                                  // EGOMI_GEMM_TALL_KMAJOR=0: gemm_tn.hip's 256x256 kernel for every k-major product (A/B runs)
-    if (on < 0) { const char* e = getenv("EGOMI_GEMM_TALL_KMAJOR"); on = e ? atoi(e) : 1; }
+    static const int on = egomi_env_int("EGOMI_GEMM_TALL_KMAJOR", 1);    // 0: gemm_tn.hip's 256x256 kernel for every k-major product (A/B runs)
     if (!on) return 1;
     if (d->a_layout != 0 || d->b_layout != 1 || d->ab_dtype != EGOMI_BF16 || d->c_dtype != EGOMI_BF16 || d->batch > 1) return 1;
     if (d->bias || d->residual || d->accumulate || d->act != 0 || d->alpha != 1.0f || d->epilogue != EGOMI_EPI_NONE) return 1;
@@ -1923,13 +1916,13 @@ int egomi_tall_kmajor_try(const egomi_gemm_desc* d, hipStream_t s, bool query) {
     return rc;
 }
 
-// the tail plan launch_8phase will run for this descriptor (d->workspace already points at the slab area)
+// EGOMI_GEMM_NO_TAIL=1: no K-sliced tail rows in either 256x256 kernel (A/B runs).  Also read by gemm_tn.hip
+int egomi_gemm_no_tail() { static const int on = egomi_env_int("EGOMI_GEMM_NO_TAIL", 0); return on; }
+// the tail plan of the 256x256 per-tile kernel for this descriptor (d->workspace already points at the slab area)
 static TailPlan tail_plan_for(const egomi_gemm_desc* d) {
     const int tiles_m = (d->M + 255) / 256;
-    static int no_tail = -1;
-    if (no_tail < 0) { const char* e = getenv("EGOMI_GEMM_NO_TAIL"); no_tail = e ? atoi(e) : 0; }
     TailPlan tp = {0, 1};
-    if (d->workspace && !no_tail) tp = plan_tail(d->M, d->N, d->K, d->workspace_bytes);
+    if (d->workspace && !egomi_gemm_no_tail()) tp = plan_tail(d->M, d->N, d->K, d->workspace_bytes);
     if (d->split_k > 0 && d->workspace) {                             // explicit override (experiments): split_k = rows * 16 + S
         tp.rows = d->split_k / 16; tp.s = d->split_k % 16;
         if (tp.rows > tiles_m) tp.rows = tiles_m;
@@ -1945,33 +1938,9 @@ static TailPlan tail_plan_for(const egomi_gemm_desc* d) {
     return tp;
 }
 
-// EGOMI_EPI_SLABS on a product that takes the 256x256 kernel: rows >= *row0 are left as *slices fp32 slabs [slices][M - row0][N]
-// at the start of the slab area (workspace + 4096 when ws_tickets_zeroed); *slices = 0: every row gets the normal epilogue
-extern "C" int egomi_gemm_tail_plan(const egomi_gemm_desc* d0, int* row0, int* slices) {
-    if (!d0 || !row0 || !slices) return EGOMI_E_BADARG;
-    *row0 = d0->M; *slices = 0;
-    // the plan is asked BEFORE the caller sets epilogue = EGOMI_EPI_SLABS; the launch that follows carries it, and tile_choice looks at
-    // the epilogue (its few-tiles / long-K rule wants a plain one): evaluate the descriptor the launch will see, so that plan and launch
-    // agree for every M (M in [1024, 1792] at K >= 8192 used to plan the 256x256 kernel and launch the 128x128 one)
-    egomi_gemm_desc dl = *d0;
-    dl.epilogue = EGOMI_EPI_SLABS;
-    if (dl.force_generic || !fast_applicable(&dl) || tile_choice(&dl) != 8) return EGOMI_E_UNSUPPORTED;
-    if (dl.bias || dl.accumulate || dl.act != 0 || dl.alpha != 1.0f || dl.c_dtype != EGOMI_BF16 || (dl.N & 7)) return EGOMI_E_UNSUPPORTED;
-    if (dl.ws_tickets_zeroed && dl.workspace) {
-        if (dl.workspace_bytes > 4096) { dl.workspace = (char*)dl.workspace + 4096; dl.workspace_bytes -= 4096; }
-        else { dl.workspace = nullptr; dl.workspace_bytes = 0; }
-    }
-    if (tall_form(&dl)) return EGOMI_OK;                               // one round of 352x256 tiles: no K-sliced rows
-    const TailPlan tp = tail_plan_for(&dl);
-    if (tp.rows) { *row0 = ((dl.M + 255) / 256 - tp.rows) * 256; *slices = tp.s; }
-    return EGOMI_OK;
-}
-
-static int launch_8phase(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s, int* tickets = nullptr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
-                         bool leave_slabs = false) {
+static int launch_8phase(const egomi_gemm_desc* d, FastArgs& g, const TailPlan tp, hipStream_t s, int* tickets, hipEvent_t t0, hipEvent_t t1, bool leave_slabs = false) {
     g.tiles_m = (d->M + 255) / 256; g.tiles_n = (d->N + 255) / 256;
     g.splitk = 1; g.ws = (float*)d->workspace;
-    const TailPlan tp = tail_plan_for(d);
     g.full_tm = g.tiles_m - tp.rows; g.tail_s = tp.s; g.full_tiles = g.full_tm * g.tiles_n;
     // in-launch combine: needs the caller's ticket words (4 KB ahead of the slabs, include/egomi.h `ws_tickets_zeroed`) and room for
     // whole 256x256 slabs of every tail tile and slice
@@ -1983,31 +1952,16 @@ static int launch_8phase(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s, i
     if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(gemm_nt_bf16_8phase_kernel<bf16_t>, dim3(nwg, 1), dim3(512), 0, s, g);
     else EGOMI_LAUNCH(gemm_nt_bf16_8phase_kernel<float>, dim3(nwg, 1), dim3(512), 0, s, g);
     if (t1) (void)hipEventRecord(t1, s);
-    egomi_route_set(6, 1, tp.rows ? g.full_tm * 256 : d->M, tp.rows ? tp.s : 0, 0);
+    egomi_route_set(FORM_8PHASE, 1, tp.rows ? g.full_tm * 256 : d->M, tp.rows ? tp.s : 0, 0);
     if (tp.rows && g.epi == 1 && g.tickets) g.tickets = nullptr;         // the fused SwiGLU epilogue wants the separate combine + tail pass below
-    if (leave_slabs) return egomi_launch_status();                       // EGOMI_EPI_SLABS: the caller's next kernel sums the tail rows' slabs
-    if (tp.rows && g.epi == 3) {                                         // K-sliced tail rows of d(act): summed and turned into d(gate|up) in one pass
-        FastArgs r = g;
-        const long long row0 = (long long)g.full_tm * 256;
-        r.M = d->M - (int)row0; r.splitk = tp.s;
-        r.C = (char*)g.C + row0 * g.ldc * 2;
+    if (leave_slabs || !tp.rows) return egomi_launch_status();           // EGOMI_EPI_SLABS: the caller's next kernel sums the tail rows' slabs
+    const long long row0 = (long long)g.full_tm * 256;
+    FastArgs r = tail_rows_view(g, row0, tp.s, d->c_dtype);
+    if (g.epi == 3) {                                                    // K-sliced tail rows of d(act): summed and turned into d(gate|up) in one pass
         r.C2 = (char*)g.C2 + row0 * g.ldc2 * 2;
-        const long long total = (long long)r.M * (d->N / 8);
-        const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        EGOMI_LAUNCH(splitk_reduce_swiglu_bwd_kernel, dim3(grid), dim3(256), 0, s, r);
-        return egomi_launch_status();
-    }
-    if (tp.rows && !g.tickets) {
-        FastArgs r = g;
-        const long long row0 = (long long)g.full_tm * 256;
-        const int esz = d->c_dtype == EGOMI_BF16 ? 2 : 4;
-        r.M = d->M - (int)row0; r.splitk = tp.s;
-        r.C = (char*)g.C + row0 * g.ldc * esz;
-        if (g.residual) r.residual = (const char*)g.residual + row0 * g.ldr * esz;
-        const long long total = (long long)r.M * ((d->N + 3) / 4);
-        const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, r);
-        else EGOMI_LAUNCH(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, r);
+        EGOMI_LAUNCH(splitk_reduce_swiglu_bwd_kernel, dim3(combine_grid((long long)r.M * (d->N / 8))), dim3(256), 0, s, r);
+    } else if (!g.tickets) {
+        launch_combine(r, d->c_dtype, s);
         if (g.epi == 1) {                                              // K-sliced tail rows: gate|up just combined, SwiGLU on those rows only
             const int rc = egomi_swiglu_il_fwd(r.C, (char*)g.C2 + row0 * g.ldc2 * 2, r.M, d->N / 2, g.ldc, g.ldc2, EGOMI_BF16, (egomi_stream_t)s);
             if (rc != EGOMI_OK) return rc;
@@ -2016,37 +1970,7 @@ static int launch_8phase(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s, i
     return egomi_launch_status();
 }
 
-// ---- column split: the 352x256 form on the first Na columns (whole rounds), the 256x256 form on the rest.  Products whose tiles fit neither
-// form in whole rounds: gate|up at M = 5536 (N = 22016: 1892 tiles of 256x256 = 7.39 rounds; 16 x 86 tall tiles = 5.375) runs as 16 x 64 tall tiles
-// (4 rounds) + 22 x 22 tiles of 256x256 (1.89 rounds), the down_proj data gradient (N = 11008: 3.70 / 2.69 rounds) as 16 x 32 tall (2 rounds) +
-// 22 x 11 (0.95 rounds).  Same round model as tall_form(); both parts carry the product's epilogue (plain, SwiGLU, SwiGLU backward); the second
-// part plans its own K-sliced tail.  Na is a multiple of 256 columns, so interleaved-32 gate|up groups and 64-column wave strips stay whole.
-static double c256_model(long long tiles, bool ws) {
-    const int ncu = p8_cus();                                            // CUs of this device (256 on MI355X in SPX mode)
-    const int rem = (int)(tiles % ncu);
-    return (double)(tiles / ncu) + (rem ? (rem * 2 <= ncu && ws ? 0.28 + 0.85 * rem / ncu : 1.0) : 0.0);
-}
-static int split_cols(const egomi_gemm_desc* d) {
-    if (g_tall_mode < 0) { const char* e = getenv("EGOMI_GEMM_TALL"); g_tall_mode = e ? atoi(e) : 1; if (g_tall_mode < 0 || g_tall_mode > 2) g_tall_mode = 1; }
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("EGOMI_GEMM_SPLIT"); on = e ? atoi(e) : 1; }
-    if (g_tall_mode != 1 || !on) return 0;                             // (mode 2 = "the tall form wherever it applies" is the whole-product A/B arm)
-    if (d->epilogue != EGOMI_EPI_NONE && d->epilogue != EGOMI_EPI_SWIGLU && d->epilogue != EGOMI_EPI_SWIGLU_BWD) return 0;
-    if ((d->M & 7) || (d->N & 255) || d->M < TL_BM || d->K < 2048 || d->split_k > 0 || d->bias) return 0;
-    if ((long long)d->M * d->lda >= (1ll << 31) || (long long)d->N * d->ldb >= (1ll << 31)) return 0;
-    if (d->c_dtype != EGOMI_BF16 && d->c_dtype != EGOMI_F32) return 0;
-    const int ncu = p8_cus();                                            // CUs of this device (256 on MI355X in SPX mode)
-    const long long tn = d->N / 256, tm256 = (d->M + 255) / 256, tm352 = (d->M + TL_BM - 1) / TL_BM;
-    const double c0 = c256_model(tm256 * tn, d->workspace != nullptr);
-    double best = 0.97 * c0;
-    int ja_best = 0;
-    for (long long ja = 1; ja < tn; ++ja) {
-        if ((tm352 * ja) % ncu) continue;                                // the tall part: whole rounds only
-        const double c = 1.31 * (double)(tm352 * ja / ncu) + c256_model(tm256 * (tn - ja), d->workspace != nullptr) + 0.03;
-        if (c < best) { best = c; ja_best = (int)ja; }
-    }
-    return ja_best * 256;
-}
+// the column split (split_cols): both parts carry the product's epilogue
 static int launch_split(const egomi_gemm_desc* d, const FastArgs& g, int Na, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
     const int esz = d->c_dtype == EGOMI_BF16 ? 2 : 4;
     egomi_gemm_desc d1 = *d;
@@ -2064,94 +1988,150 @@ static int launch_split(const egomi_gemm_desc* d, const FastArgs& g, int Na, hip
     if (d->residual) d2.residual = g2.residual = (const char*)d->residual + (long long)Na * esz;
     if (d->epilogue == EGOMI_EPI_SWIGLU) d2.C2 = g2.C2 = (char*)d->C2 + (long long)(Na / 2) * 2;   // act [M, N/2]
     if (d->epilogue == EGOMI_EPI_SWIGLU_BWD) d2.C2 = g2.C2 = (char*)d->C2 + 2ll * Na * 2;          // gate|up [M, 2N]
-    rc = launch_8phase(&d2, g2, s, nullptr, nullptr, t1);
-    egomi_route_[0] = 9; egomi_route_[4] = Na;                           // (the second part's tail plan stays in the record)
+    rc = launch_8phase(&d2, g2, tail_plan_for(&d2), s, nullptr, nullptr, t1);
+    egomi_route_[0] = FORM_SPLIT; egomi_route_[4] = Na;                  // (the second part's tail plan stays in the record)
     return rc;
 }
 
-// returns 0 on success, <0 on error, 1 when the tuned kernel does not apply
-// EGOMI_EPI_SLABS (include/egomi.h): plain product only — everything an epilogue could do is the consumer kernel's job
-static bool slabs_form_ok(const egomi_gemm_desc* d) {
-    return !d->bias && !d->residual && !d->accumulate && d->act == 0 && d->alpha == 1.0f && d->workspace && d->M <= 512 && (d->N & 3) == 0;
+template <int BM, int BN, int STAGES>
+static void run_tiles(FastArgs& g, bool bf16, hipStream_t s) {
+    g.tiles_m = (g.M + BM - 1) / BM; g.tiles_n = (g.N + BN - 1) / BN;
+    const dim3 grid(g.tiles_m * g.tiles_n, g.splitk), block((BM / 64) * (BN / 64) * 64);
+    if (bf16) EGOMI_LAUNCH((gemm_nt_bf16_kernel<bf16_t, BM, BN, STAGES>), grid, block, 0, s, g);
+    else EGOMI_LAUNCH((gemm_nt_bf16_kernel<float, BM, BN, STAGES>), grid, block, 0, s, g);
+}
+// one frame for the forms that cut K over blockIdx.y into `splitk` fp32 slabs: the form's launch, then the combine pass unless the slabs are the
+// result (EGOMI_EPI_SLABS: the caller's next kernel sums them; gemm_route has seen to it that there are at least two)
+static int launch_sliced(const egomi_gemm_desc* d, FastArgs& g, int form, int splitk, hipStream_t s) {
+    if (d->c_dtype != EGOMI_BF16 && d->c_dtype != EGOMI_F32) return EGOMI_E_UNSUPPORTED;
+    static const int pf = egomi_env_int("EGOMI_GEMM_PF", 1);             // 0: one LDS stage in the 128x128 kernel (A/B switch)
+    const bool bf16 = d->c_dtype == EGOMI_BF16;
+    g.ws = (float*)d->workspace; g.splitk = splitk;
+    if (form == FORM_GEMV) run_gemv(g, bf16, s);
+    else if (form == FORM_M256) run_m256(g, bf16, s);
+    else if (form == FORM_128 && pf) run_tiles<128, 128, 2>(g, bf16, s);
+    else if (form == FORM_128) run_tiles<128, 128, 1>(g, bf16, s);
+    else run_tiles<256, 128, 1>(g, bf16, s);
+    if (splitk > 1 && d->epilogue != EGOMI_EPI_SLABS) launch_combine(g, d->c_dtype, s);
+    egomi_route_set(form, splitk, d->M, 0, 0);
+    return egomi_launch_status();
+}
+
+// ---- the route of a product: the form that runs it and that form's numbers.  egomi_gemm_fast_try launches what gemm_route() returns, and
+// egomi_gemm_kernel_id, egomi_gemm_slab_count and egomi_gemm_tail_plan report from the same call, so a query cannot disagree with the launch.
+// The forms that launch carry their egomi_gemm_last_route ids.
+struct GemmRoute {
+    int form;
+    egomi_gemm_desc d;      // the descriptor as the launch carries it: workspace / workspace_bytes are the slab area behind the ticket words
+    int kernel_id;          // egomi_gemm_kernel_id: 2 = the tile choice is the 256-row forms, 1 = the others (whatever the epilogue rules then say)
+    int splitk;             // gemv, m256, 128x128, 256x128: K slices over blockIdx.y
+    int slabs;              // egomi_gemm_slab_count: the slabs those forms leave under EGOMI_EPI_SLABS; 0 = such a launch is refused
+    TailPlan tail;          // 256x256 per tile: the K-sliced tail rows
+    int* tickets;           //   ... non-null: combined inside the launch where the slabs fit
+    int Na;                 // column split: the first Na columns in the 352x256 form
+    P8Sched sc;             // persistent
+};
+static GemmRoute gemm_route(const egomi_gemm_desc* d0) {
+    GemmRoute r = {};
+    r.d = *d0; r.splitk = 1; r.tail = {0, 1};
+    egomi_gemm_desc* d = &r.d;
+    if (d->force_generic || !fast_applicable(d)) return r;
+    const int tc = tile_choice(d), epi = d->epilogue;                    // (tile_choice sees the whole scratch: its few-tiles rule counts the ticket words itself)
+    r.kernel_id = tc == 8 ? 2 : 1;
+    const bool unfused = epi == EGOMI_EPI_NONE || epi == EGOMI_EPI_SLABS;
+    // an unfused product asks the round model of the 352x256 form before the ticket words come off the scratch, a fused one after: the two
+    // differ only for a scratch that is nothing but ticket words, where the model then does or does not count on K-sliced rows
+    const bool tall_early = tc == 8 && unfused && tall_form(d);
+    int* tickets; char* slabs; long long bytes;
+    egomi_scratch_slabs(d, &tickets, &slabs, &bytes);
+    d->workspace = slabs; d->workspace_bytes = bytes;
+    if (tc != 8 || (epi == EGOMI_EPI_NONE && !spans_fit_31(d))) {        // (EGOMI_GEMM_TILE=8 on spans too long: a plain product goes to the 128x128 forms)
+        if (tc != 2 && gemv_form(d)) { r.form = FORM_GEMV; r.splitk = gemv_splitk(d); }
+        else if (tc != 2 && m256_form(d)) { r.form = FORM_M256; r.splitk = m256_splitk(d); }
+        else {
+            r.form = tc == 2 ? FORM_256x128 : FORM_128;
+            r.splitk = skinny_splitk(d, ((d->M + (tc == 2 ? 255 : 127)) / (tc == 2 ? 256 : 128)) * ((d->N + 127) / 128));
+        }
+        if (plain_slabs(d, false) && tc == 1 && r.splitk >= 2) r.slabs = r.splitk;
+        // slabs need two slices to be slabs; the fused epilogues live in the 256-row forms only
+        if (epi == EGOMI_EPI_SLABS ? !r.slabs : epi != EGOMI_EPI_NONE) r.form = FORM_UNSUPPORTED;
+        return r;
+    }
+    if (epi == EGOMI_EPI_SLABS) {
+        // large products: only the K-sliced TAIL rows are left as slabs (egomi_gemm_tail_plan tells which); whole tiles get the
+        // normal epilogue, residual included
+        if (!plain_slabs(d, true) || !spans_fit_31(d)) { r.form = FORM_UNSUPPORTED; return r; }
+    } else if (epi != EGOMI_EPI_NONE) {
+        // fused epilogues live in the 256-row kernels' plain-bf16 store path only: whole interleaved groups per wave
+        // (N % 256 == 0), 16-B aligned rows, nothing else in the epilogue
+        const bool common = d->c_dtype == EGOMI_BF16 && d->C2 && !d->bias && !d->residual && !d->accumulate && d->act == 0 && d->alpha == 1.0f &&
+                            d->ldc % 8 == 0 && d->ldc2 % 8 == 0 && (((uintptr_t)d->C | (uintptr_t)d->C2) & 15) == 0 && spans_fit_31(d);
+        const bool ok = common && ((epi == EGOMI_EPI_SWIGLU && d->N % 256 == 0 && d->ldc2 >= d->N / 2) ||
+                                   (epi == EGOMI_EPI_SWIGLU_BWD && d->N % 64 == 0 && d->ldc >= 2 * d->N && d->ldc2 >= 2 * d->N));
+        if (!ok) { r.form = FORM_UNSUPPORTED; return r; }
+    }
+    if (unfused ? tall_early : tall_form(d)) r.form = FORM_TALL;         // one round of 352x256 tiles: no K-sliced rows
+    else if (epi == EGOMI_EPI_NONE && p8_applicable(d, tickets, r.sc)) r.form = FORM_P8;
+    else if ((r.Na = split_cols(d)) != 0) r.form = FORM_SPLIT;
+    else {
+        r.form = FORM_8PHASE;
+        r.tail = tail_plan_for(d);
+        // In-launch combine of the K-sliced tail tiles (last-arriver tickets) is built and tested but NOT the default.  Measured in the
+        // training step on one box, arms alternated: with agent-scope release/acquire fences around the slabs 139.1 ms/step vs 136.6
+        // with the separate combine launch; with sc1 slab stores/loads and no fence (the present form) 136.4 vs 136.15 — the fences
+        // (whole-L2 write-back / invalidate in mid-launch) were the 2.3 ms, what remains is the last arriver summing S x 256 KB
+        // alone at the very end of the launch, where splitk_reduce_kernel spreads the same bytes over every CU.  EGOMI_GEMM_FOLD=1
+        // selects it.  The ticket words are used by this and the persistent form only.
+        static const int fold = egomi_env_int("EGOMI_GEMM_FOLD", 0);
+        if (epi == EGOMI_EPI_NONE && (fold || d->ws_tickets_zeroed == 2)) r.tickets = tickets;
+    }
+    return r;
 }
 
 extern thread_local hipEvent_t egomi_time_start_, egomi_time_stop_;     // api.hip (egomi_gemm_time_next)
 
+// returns 0 on success, <0 on error, 1 when the tuned kernels do not apply
 int egomi_gemm_fast_try(const egomi_gemm_desc* d0, hipStream_t s) {
     const hipEvent_t t0 = egomi_time_start_, t1 = egomi_time_stop_;       // one-shot request: consumed by this call whatever path it takes
     egomi_time_start_ = egomi_time_stop_ = nullptr;
-    if (!fast_applicable(d0)) return 1;
-    egomi_gemm_desc dl = *d0;
-    const egomi_gemm_desc* d = &dl;
+    const GemmRoute r = gemm_route(d0);
+    if (r.form == FORM_NA) return 1;
+    if (r.form == FORM_UNSUPPORTED) return EGOMI_E_UNSUPPORTED;
+    const egomi_gemm_desc* d = &r.d;
     FastArgs g;
     g.A = (const bf16_t*)d->A; g.B = (const bf16_t*)d->B; g.C = d->C; g.bias = (const bf16_t*)d->bias; g.residual = d->residual;
     g.M = d->M; g.N = d->N; g.K = d->K; g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc; g.ldr = d->ldr;
     g.alpha = d->alpha; g.accumulate = d->accumulate; g.act = d->act; g.tickets = nullptr;
-    g.epi = d->epilogue; g.C2 = d->C2; g.ldc2 = d->ldc2;
-    const int tc = tile_choice(d);
-    if (tc == 8 && (d->epilogue == EGOMI_EPI_NONE || d->epilogue == EGOMI_EPI_SLABS) && tall_form(d)) {
-        if (d->epilogue == EGOMI_EPI_SLABS && (d->bias || d->accumulate || d->act != 0 || d->alpha != 1.0f || d->c_dtype != EGOMI_BF16)) return EGOMI_E_UNSUPPORTED;
-        return launch_tall(d, g, s, t0, t1);
+    g.epi = d->epilogue == EGOMI_EPI_SLABS ? 0 : d->epilogue;            // (slabs are the host's business: the kernels run a plain epilogue)
+    g.C2 = d->C2; g.ldc2 = d->ldc2;
+    switch (r.form) {
+    case FORM_P8: return launch_p8(d, g, r.sc, s);
+    case FORM_TALL: return launch_tall(d, g, s, t0, t1);
+    case FORM_SPLIT: return launch_split(d, g, r.Na, s, t0, t1);
+    case FORM_8PHASE: return launch_8phase(d, g, r.tail, s, r.tickets, t0, t1, d->epilogue == EGOMI_EPI_SLABS);
+    default: return launch_sliced(d, g, r.form, r.splitk, s);
     }
-    if (d->epilogue == EGOMI_EPI_SLABS && tc == 8) {
-        // large products: only the K-sliced TAIL rows are left as slabs (egomi_gemm_tail_plan tells which); whole tiles get the
-        // normal epilogue, residual included
-        if (d->bias || d->accumulate || d->act != 0 || d->alpha != 1.0f || d->c_dtype != EGOMI_BF16 || (d->N & 7) ||
-            (long long)d->M * d->lda >= (1ll << 31) || (long long)d->N * d->ldb >= (1ll << 31)) return EGOMI_E_UNSUPPORTED;
-        if (dl.ws_tickets_zeroed && dl.workspace) {
-            if (dl.workspace_bytes > 4096) { dl.workspace = (char*)dl.workspace + 4096; dl.workspace_bytes -= 4096; }
-            else { dl.workspace = nullptr; dl.workspace_bytes = 0; }
-        }
-        g.epi = 0;
-        return launch_8phase(d, g, s, nullptr, t0, t1, true);
-    }
-    if (d->epilogue == EGOMI_EPI_SLABS) {
-        if (!slabs_form_ok(d) || tc != 1) return EGOMI_E_UNSUPPORTED;
-        if (dl.ws_tickets_zeroed && dl.workspace) {                     // same scratch convention as below: slabs start behind the ticket words
-            if (dl.workspace_bytes > 4096) { dl.workspace = (char*)dl.workspace + 4096; dl.workspace_bytes -= 4096; }
-            else return EGOMI_E_UNSUPPORTED;
-        }
-        g.epi = 0;
-        return launch_fast<128, 128>(d, g, s);
-    }
-    if (d->epilogue != EGOMI_EPI_NONE) {
-        // fused epilogues live in the 256x256 per-tile kernel's plain-bf16 store path only: whole interleaved groups per wave
-        // (N % 256 == 0), 16-B aligned rows, nothing else in the epilogue
-        const bool common = tc == 8 && d->c_dtype == EGOMI_BF16 && d->C2 && !d->bias && !d->residual &&
-                            !d->accumulate && d->act == 0 && d->alpha == 1.0f && d->ldc % 8 == 0 && d->ldc2 % 8 == 0 &&
-                            (((uintptr_t)d->C | (uintptr_t)d->C2) & 15) == 0 && (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31);
-        const bool ok = common && ((d->epilogue == EGOMI_EPI_SWIGLU && d->N % 256 == 0 && d->ldc2 >= d->N / 2) ||
-                                   (d->epilogue == EGOMI_EPI_SWIGLU_BWD && d->N % 64 == 0 && d->ldc >= 2 * d->N && d->ldc2 >= 2 * d->N));
-        if (!ok) return EGOMI_E_UNSUPPORTED;
-        if (dl.ws_tickets_zeroed && dl.workspace) {
-            if (dl.workspace_bytes > 4096) { dl.workspace = (char*)dl.workspace + 4096; dl.workspace_bytes -= 4096; }
-            else { dl.workspace = nullptr; dl.workspace_bytes = 0; }
-        }
-        if (tall_form(d)) return launch_tall(d, g, s, t0, t1);              // the fused epilogues live in both forms
-        if (const int Na = split_cols(d)) return launch_split(d, g, Na, s, t0, t1);
-        return launch_8phase(d, g, s, nullptr, t0, t1);
-    }
-    if (tc == 8 && (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) {
-        P8Sched sc;
-        if (p8_applicable(d, sc)) return launch_p8(d, g, sc, s);
-    }
-    int* tickets = nullptr;
-    if (dl.ws_tickets_zeroed && dl.workspace) {                       // the ticket words are used by the in-launch combines only: every other
-        if (dl.workspace_bytes > 4096) { tickets = (int*)dl.workspace; dl.workspace = (char*)dl.workspace + 4096; dl.workspace_bytes -= 4096; }   // scratch starts behind them
-        else { dl.workspace = nullptr; dl.workspace_bytes = 0; }
-    }
-    // In-launch combine of the K-sliced tail tiles (last-arriver tickets) is built and tested but NOT the default.  Measured in the
-    // training step on one box, arms alternated: with agent-scope release/acquire fences around the slabs 139.1 ms/step vs 136.6
-    // with the separate combine launch; with sc1 slab stores/loads and no fence (the present form) 136.4 vs 136.15 — the fences
-    // (whole-L2 write-back / invalidate in mid-launch) were the 2.3 ms, what remains is the last arriver summing S x 256 KB
-    // alone at the very end of the launch, where splitk_reduce_kernel spreads the same bytes over every CU.  EGOMI_GEMM_FOLD=1
-    // selects it.
-    static int fold = -1;
-    if (fold < 0) { const char* e = getenv("EGOMI_GEMM_FOLD"); fold = e ? atoi(e) : 0; }
-    if (!fold && dl.ws_tickets_zeroed != 2) tickets = nullptr;
-    if (tc == 8 && (long long)d->M * d->lda < (1ll << 31) && (long long)d->N * d->ldb < (1ll << 31)) {
-        if (const int Na = split_cols(d)) return launch_split(d, g, Na, s, t0, t1);
-        return launch_8phase(d, g, s, tickets, t0, t1);
-    }
-    return tc == 2 ? launch_fast<256, 128>(d, g, s) : launch_fast<128, 128>(d, g, s);
+}
+
+extern "C" int egomi_gemm_tn_kernel_id(const egomi_gemm_desc* d);      // gemm_tn.hip: 3 when the k-major 8-phase kernel takes the product
+extern "C" int egomi_gemm_kernel_id(const egomi_gemm_desc* d) {
+    if (!d) return EGOMI_E_BADARG;
+    const GemmRoute r = gemm_route(d);
+    return r.form == FORM_NA ? egomi_gemm_tn_kernel_id(d) : r.kernel_id;
+}
+extern "C" int egomi_gemm_slab_count(const egomi_gemm_desc* d) { return d ? gemm_route(d).slabs : EGOMI_E_BADARG; }
+// EGOMI_EPI_SLABS on a product that takes a 256-row form: rows >= *row0 are left as *slices fp32 slabs [slices][M - row0][N]
+// at the start of the slab area (workspace + 4096 when ws_tickets_zeroed); *slices = 0: every row gets the normal epilogue
+extern "C" int egomi_gemm_tail_plan(const egomi_gemm_desc* d0, int* row0, int* slices) {
+    if (!d0 || !row0 || !slices) return EGOMI_E_BADARG;
+    *row0 = d0->M; *slices = 0;
+    // the plan is asked BEFORE the caller sets epilogue = EGOMI_EPI_SLABS; the launch that follows carries it, and tile_choice looks at
+    // the epilogue (its few-tiles / long-K rule wants a plain one): route the descriptor the launch will see, so that plan and launch
+    // agree for every M (M in [1024, 1792] at K >= 8192 used to plan the 256x256 kernel and launch the 128x128 one)
+    egomi_gemm_desc dl = *d0;
+    dl.epilogue = EGOMI_EPI_SLABS;
+    const GemmRoute r = gemm_route(&dl);
+    if (r.form != FORM_TALL && r.form != FORM_8PHASE) return EGOMI_E_UNSUPPORTED;
+    if (r.tail.rows) { *row0 = ((dl.M + 255) / 256 - r.tail.rows) * 256; *slices = r.tail.s; }
+    return EGOMI_OK;
 }

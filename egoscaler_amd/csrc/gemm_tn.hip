@@ -326,14 +326,15 @@ void gemm_bf16_8phase_t_kernel(TnArgs g) {
 int egomi_gemm_tn_rest(const egomi_gemm_desc* d, hipStream_t s);
 int egomi_tall_kmajor_try(const egomi_gemm_desc* d, hipStream_t s, bool query);    // data gradients: the 352x256 form where whole rounds pay (0 = taken)
 void egomi_plan_tail_rows(int M, int N, int K, long long ws_bytes, int* rows, int* slices);
-int egomi_splitk_reduce_rows(void* C, int c_dtype, long long ldc, int rows, int N, const float* ws, int slices, int accumulate, hipStream_t s);
+int egomi_splitk_reduce_rows(void* C, int c_dtype, long long ldc, int M, int row0, int N, const float* ws, int slices, int accumulate, hipStream_t s);   // combine pass over rows >= row0
+bool egomi_scratch_slabs(const egomi_gemm_desc* d, int** tickets, char** slabs, long long* bytes);    // the slab area behind the ticket words
+int egomi_gemm_no_tail();                                                          // EGOMI_GEMM_NO_TAIL
 
 // kernel id reported by egomi_gemm_kernel_id for this kernel
 #define TN_KERNEL_ID 3
 
 static bool tn_applicable(const egomi_gemm_desc* d) {
-    static int on = -1;                                                            // EGOMI_GEMM_TN=0: k-major operands go back to the generic kernel (A/B runs)
-    if (on < 0) { const char* e = getenv("EGOMI_GEMM_TN"); on = e ? atoi(e) : 1; }
+    static const int on = egomi_env_int("EGOMI_GEMM_TN", 1);                       // 0: k-major operands go back to the generic kernel (A/B runs)
     if (!on || d->force_generic) return false;
     if (d->ab_dtype != EGOMI_BF16 || d->batch > 1 || d->b_layout != 1) return false;      // (a_layout, b_layout) = (1, 1) or (0, 1)
     if (d->bias || d->residual || d->act != 0 || d->alpha != 1.0f || d->epilogue != EGOMI_EPI_NONE) return false;
@@ -360,13 +361,8 @@ static bool tn_applicable(const egomi_gemm_desc* d) {
 // the ticket words of the caller's scratch).  rows = 0: every tile whole.
 static void tn_tail(const egomi_gemm_desc* d, int* rows, int* slices, float** slabs) {
     *rows = 0; *slices = 1; *slabs = nullptr;
-    static int no_tail = -1;
-    if (no_tail < 0) { const char* e = getenv("EGOMI_GEMM_NO_TAIL"); no_tail = e ? atoi(e) : 0; }
-    if (!d->workspace || no_tail) return;
-    char* wsp = (char*)d->workspace;
-    long long wsb = d->workspace_bytes;
-    if (d->ws_tickets_zeroed) { wsp += 4096; wsb -= 4096; }
-    if (wsb <= 0 || (((uintptr_t)wsp) & 15)) return;
+    int* tickets; char* wsp; long long wsb;
+    if (egomi_gemm_no_tail() || !egomi_scratch_slabs(d, &tickets, &wsp, &wsb) || wsb <= 0 || (((uintptr_t)wsp) & 15)) return;
     int r = 0, sl = 1;
     egomi_plan_tail_rows(d->M, d->N, d->K, wsb, &r, &sl);
     const int nt = (d->K + TN_BK - 1) / TN_BK;
@@ -417,10 +413,6 @@ int egomi_gemm_tn_rest(const egomi_gemm_desc* d, hipStream_t s) {
         else EGOMI_LAUNCH((gemm_bf16_8phase_t_kernel<bf16_t, false, true>), grid, block, 0, s, g);
     }
     egomi_route_set(10, 1, rows > 0 ? g.full_tm * 256 : d->M, rows > 0 ? slices : 0, 0);
-    if (rows > 0) {
-        const long long row0 = (long long)g.full_tm * 256;
-        const int esz = f32 ? 4 : 2;
-        return egomi_splitk_reduce_rows((char*)d->C + row0 * d->ldc * esz, d->c_dtype, d->ldc, d->M - (int)row0, d->N, g.ws, slices, d->accumulate, s);
-    }
+    if (rows > 0) return egomi_splitk_reduce_rows(d->C, d->c_dtype, d->ldc, d->M, g.full_tm * 256, d->N, g.ws, slices, d->accumulate, s);
     return egomi_launch_status();
 }

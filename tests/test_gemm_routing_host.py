@@ -88,3 +88,76 @@ def test_k_major_products_slice_the_ragged_last_round():
     assert L.egomi_gemm_tn_tail_plan(ctypes.byref(d), ctypes.byref(row0), ctypes.byref(sl)) == 0 and sl.value == 0
     d = tn_desc(300, 200, 512, 1)                                          # not a product of that kernel
     assert L.egomi_gemm_tn_tail_plan(ctypes.byref(d), ctypes.byref(row0), ctypes.byref(sl)) != 0
+
+
+FULL = 4096 + 256 * 2 * 262144
+SWEEP_M = sorted(set(range(8, 8192 + 1, 8)) | {692, 1224, 1384, 2768, 5536})
+SWEEP_NK = [(12288, 4096), (4096, 4096), (22016, 4096), (11008, 4096), (4096, 11008), (4096, 12288), (4096, 22016), (32262, 4096)]
+SWEEP_WS = [0, 2048, 4096, 4096 + (1 << 20), 4096 + (16 << 20), FULL]
+EPI_SLABS = 2
+
+
+def sweep_desc(M, N, K, ws_bytes, tickets):
+    d = desc(M, N, K, ws_bytes)
+    d.ws_tickets_zeroed = tickets
+    if not ws_bytes:
+        d.workspace = None
+    return d
+
+
+def plan_of(L, d):
+    row0, sl = ctypes.c_int(0), ctypes.c_int(0)
+    rc = L.egomi_gemm_tail_plan(ctypes.byref(d), ctypes.byref(row0), ctypes.byref(sl))
+    return rc, row0.value, sl.value
+
+
+@pytest.mark.parametrize("N,K", SWEEP_NK)
+def test_what_the_queries_promise_the_launch_can_keep(N, K):
+    """Every answer of egomi_gemm_tail_plan and egomi_gemm_slab_count names a kernel that takes slabs and a slab area that holds them,
+    for every M, scratch size and ticket setting: no exception is allowed."""
+    L = _lib.lib()
+    bad = []
+    for ws in SWEEP_WS:
+        for tickets in (0, 1, 2):
+            room = ws - (4096 if tickets else 0)
+            for M in SWEEP_M:
+                d = sweep_desc(M, N, K, ws, tickets)
+                rc, row0, sl = plan_of(L, d)
+                d.epilogue = EPI_SLABS                        # what ops.gemm_raw sets before egomi_gemm
+                kid = L.egomi_gemm_kernel_id(ctypes.byref(d))
+                if rc == 0 and sl >= 2:
+                    if not (kid == 2 and row0 % 256 == 0 and 0 <= row0 < M and (M - row0) * N * 4 * sl <= room and ws > 4096):
+                        bad.append(("plan", M, ws, tickets, row0, sl, kid))
+                n = L.egomi_gemm_slab_count(ctypes.byref(d))
+                if n and not (n >= 2 and M <= 512 and kid == 1 and n * M * N * 4 <= room):
+                    bad.append(("slabs", M, ws, tickets, n, kid))
+    assert not bad, bad[:8]
+
+
+def test_tail_plan_does_not_depend_on_the_scratch_sizes_asked_before():
+    """plan_tail's cache is keyed by the scratch size: a 16-MiB scratch holds no slabs for this shape, the full one holds 4 slices of the last
+    104 rows, whichever is asked first."""
+    L = _lib.lib()
+    assert plan_of(L, desc(1384, 22016, 4096, 4096 + (16 << 20)))[2] < 2
+    assert plan_of(L, desc(1384, 22016, 4096, FULL)) == (0, 1280, 4)
+
+
+# the workload's shapes at the full scratch, ticket words present, bf16: kernel id, slab count under EGOMI_EPI_SLABS, tail plan (None: refused)
+PINNED = [
+    (8, 12288, 4096, 1, 4, None), (8, 22016, 4096, 1, 2, None), (8, 4096, 11008, 1, 10, None), (8, 32262, 4096, 1, 0, None),
+    (256, 12288, 4096, 1, 2, None), (256, 4096, 4096, 1, 4, None), (256, 22016, 4096, 1, 0, None), (256, 4096, 11008, 1, 8, None),
+    (512, 22016, 4096, 2, 0, (0, 512, 0)), (1384, 22016, 4096, 2, 0, (0, 1280, 4)), (1384, 11008, 4096, 2, 0, (0, 1280, 4)),
+    (1384, 4096, 11008, 2, 0, None), (5536, 4096, 4096, 2, 0, (0, 5536, 0)), (5536, 4096, 11008, 2, 0, (0, 5536, 0)),
+    (5536, 22016, 4096, 2, 0, (0, 5536, 0)), (5536, 32262, 4096, 2, 0, None),
+]
+
+
+@pytest.mark.parametrize("M,N,K,kernel_id,slabs,plan", PINNED)
+def test_routes_of_the_workload_shapes(M, N, K, kernel_id, slabs, plan):
+    L = _lib.lib()
+    d = desc(M, N, K)
+    assert L.egomi_gemm_kernel_id(ctypes.byref(d)) == kernel_id
+    got = plan_of(L, d)
+    assert (got == plan) if plan is not None else (got[0] != 0)
+    d.epilogue = EPI_SLABS
+    assert L.egomi_gemm_slab_count(ctypes.byref(d)) == slabs
