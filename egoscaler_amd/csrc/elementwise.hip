@@ -4,6 +4,7 @@
 // All compute in fp32; I/O in T (float or bf16).  16-byte vector accesses where the shape allows.
 #include "common.h"
 #include "row_pieces.h"
+#include "lp_row.h"
 #include <math.h>
 
 static inline int ew_grid(long long total) { long long g = (total + 255) / 256; return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }
@@ -867,6 +868,98 @@ extern "C" int egomi_ce_fwd_bwd(const void* logits, int64_t ld, const int64_t* t
     EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH(ce_fwd_bwd_kernel<T>, dim3(R), dim3(1024), 0, (hipStream_t)stream,
                                                    (const T*)logits, ld, targets, V, ignore, count, row_loss, (T*)dlogits, ldd, grad_scale));
     EGOMI_LAUNCH(ordered_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)row_loss, R, loss_sum);
+    return egomi_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// A12 (soft)  the same loss against a bin-aware target.  reference: train.py:174-181 (its F.cross_entropy is the one-hot case)
+// A row whose target t is one of the nb bin ids p0 .. p0 + nb - 1 is scored against q = a discrete Gaussian of width sigma (in bins) around
+// t, cut at `radius` bins and at the ends of the bin window and renormalised there: no mass leaves [p0, p0 + nb).  Every other kept row keeps
+// the one-hot, ignored rows give 0 and a zero gradient row.  row_loss = sum_j q_j (lse - x_j), row_nll = lse - x_t, dlogits = (p - q) sc.
+// m and s come from lp_row_max_sumexp (csrc/lp_row.h), so a row's bits do not depend on its address, its slot or R; lse is never formed in
+// fp32: p = expf((x - m) - logf(s)), and the loss terms are (double)m - (double)x_j + log((double)s).  The at most 65 weights, their sum and
+// the dot product are float64 in ascending j: threads < n compute one weight each, every thread adds them in the same order.
+// In place (dlogits == logits): the window's logits and x_t go to LDS before the barrier that follows the row pass; after it a thread
+// re-reads only the elements it alone then writes (element c belongs to thread c % 1024), and nothing outside [row, row + V) is written.
+// ------------------------------------------------------------------------------------------------
+#define CE_SOFT_MAXR 32
+#define CE_SOFT_MAXW (2 * CE_SOFT_MAXR + 1)
+#define CE_SOFT_MAXSIGMA 16.0f
+
+template <typename T, bool REG>
+__global__ __launch_bounds__(LPB_THREADS) void ce_soft_fwd_bwd_kernel(const T* logits, long long ld, const int64_t* tg, int V, int64_t ignore,
+                                                                      const int32_t* count, int p0, int nb, float sigma, int radius,
+                                                                      float* row_loss, float* row_nll, T* dlogits, long long ldd, float grad_scale) {
+    __shared__ float red[16];
+    __shared__ double wq[CE_SOFT_MAXW];                                  // w_j of the ids c0 .. c0 + n - 1, the only ones with q > 0
+    __shared__ float wx[CE_SOFT_MAXW + 1];                               // their logits, then x_t
+    const long long row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const T* lr = logits + row * ld;
+    const int64_t t = tg[row];
+    if ((t == ignore) || t < 0 || t >= V) {
+        if (tid == 0) { row_loss[row] = 0.f; row_nll[row] = 0.f; }
+        if (dlogits) for (int c = tid; c < V; c += LPB_THREADS) Cvt<T>::st(dlogits + row * ldd + c, 0.f);
+        return;
+    }
+    const bool bin = t >= p0 && t < (int64_t)p0 + nb;
+    const int ti = (int)t, i = ti - p0;
+    const int c0 = bin ? p0 + max(0, i - radius) : ti;
+    const int n = bin ? p0 + min(nb - 1, i + radius) - c0 + 1 : 1;
+    float m, s;
+    lp_row_max_sumexp<T, REG>(lr, V, red, m, s);
+    if (tid < n) {
+        const double d = (double)(c0 + tid - ti), sg = (double)sigma;
+        wq[tid] = exp(-(d * d) / (2.0 * sg * sg));
+        wx[tid] = Cvt<T>::ld(lr + c0 + tid);
+    }
+    if (tid == n) wx[n] = Cvt<T>::ld(lr + ti);
+    __syncthreads();                                                     // every read of the row that is not element-owned lies before this
+    double Z = 0.0;
+    for (int j = 0; j < n; ++j) Z += wq[j];
+    if (tid == 0) {
+        const double ls = log((double)s);
+        double acc = 0.0;
+        for (int j = 0; j < n; ++j) {
+            const double q = wq[j] / Z;
+            if (q > 0.0) acc += q * ((double)m - (double)wx[j] + ls);    // (a weight that underflowed to 0 does not meet a -inf logit)
+        }
+        row_loss[row] = (float)acc;
+        row_nll[row] = (float)((double)m - (double)wx[n] + ls);
+    }
+    if (dlogits) {
+        // p is the only fp32 quantity: q, the difference and the scale stay in float64, so the stored value is rounded once
+        const double sc = (double)grad_scale / (double)(*count);
+        const float lgs = logf(s);
+        T* dr = dlogits + row * ldd;
+        for (int c = tid; c < V; c += LPB_THREADS) {
+            const float p = expf((Cvt<T>::ld(lr + c) - m) - lgs);
+            const int j = c - c0;
+            const double q = (j >= 0 && j < n) ? wq[j] / Z : 0.0;
+            Cvt<T>::st(dr + c, (float)(((double)p - q) * sc));
+        }
+    }
+}
+
+extern "C" int egomi_ce_soft_fwd_bwd(const void* logits, int64_t ld, const int64_t* targets, int R, int V, int64_t ignore,
+                                     const int32_t* count, int p0, int nb, float sigma, int radius,
+                                     float* loss_sum, float* nll_sum, float* row_loss, float* row_nll,
+                                     void* dlogits, int64_t ldd, float grad_scale, int dtype, egomi_stream_t stream) {
+    if (!logits || !targets || !count || !loss_sum || !nll_sum || !row_loss || !row_nll) return EGOMI_E_BADARG;
+    if (dtype != EGOMI_F32 && dtype != EGOMI_BF16) return EGOMI_E_BADARG;
+    if (R <= 0 || V <= 0 || ld < V || (dlogits && ldd < V)) return EGOMI_E_SHAPE;
+    if (p0 < 0 || nb < 1 || (long long)p0 + nb > V || radius < 1 || radius > CE_SOFT_MAXR) return EGOMI_E_SHAPE;
+    if (!(sigma > 0.f && sigma <= CE_SOFT_MAXSIGMA)) return EGOMI_E_SHAPE;                     // (refuses NaN as well)
+    const uintptr_t el = dtype == EGOMI_F32 ? 4 : 2;                                           // elements must be naturally aligned
+    if (((uintptr_t)logits) % el || ((uintptr_t)dlogits) % el) return EGOMI_E_UNSUPPORTED;
+    if (V <= LPB_THREADS * LPB_NPT)
+        EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((ce_soft_fwd_bwd_kernel<T, true>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, (const T*)logits,
+                                                       ld, targets, V, ignore, count, p0, nb, sigma, radius, row_loss, row_nll, (T*)dlogits, ldd, grad_scale));
+    else
+        EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((ce_soft_fwd_bwd_kernel<T, false>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, (const T*)logits,
+                                                       ld, targets, V, ignore, count, p0, nb, sigma, radius, row_loss, row_nll, (T*)dlogits, ldd, grad_scale));
+    EGOMI_LAUNCH(ordered_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)row_loss, R, loss_sum);
+    EGOMI_LAUNCH(ordered_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)row_nll, R, nll_sum);
     return egomi_launch_status();
 }
 

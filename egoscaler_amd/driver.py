@@ -545,6 +545,8 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
     sync = GradSync(wire_dtype=torch.bfloat16 if model.engine.dtype == torch.bfloat16 else None, resident=True) if world > 1 else None     # EgoAdamW reads the wire
     if sync is None and model.engine.dtype == torch.bfloat16 and model.engine.any_layer_trainable and model.engine.device.type == "cuda":
         sync = GradSync(wire_dtype=torch.bfloat16, resident=True, local=True)      # one rank, --unfreeze_language_model: bf16 weight gradients in per-layer wire buffers (dp.py), nothing exchanged
+    bin_sigma = float(getattr(args, "bin_sigma", 0) or 0)                             # 0: the reference's one-hot loss, nothing below changes
+    soft = T.soft_target_spec(model.dims.tok, bin_sigma, getattr(args, "bin_radius", None)) if bin_sigma > 0 else None
     start_epoch, global_step, best_ade = 0, 0, float("inf")
     os.makedirs(args.out_dir, exist_ok=True)
     latest = os.path.join(args.out_dir, "latest_model.pt")
@@ -570,6 +572,7 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
         g = np.random.Generator(np.random.Philox(key=np.array([1234, epoch], dtype=np.uint64)))   # same order on every rank
         order = g.permutation(len(train_data))
         run = torch.zeros((), device=device)
+        run_nll = torch.zeros((), device=device) if soft is not None else None
         for it in range(steps_per_epoch):
             # the epoch's last optimizer step may be short (no drop_last, see above).  Its samples are dealt over the micro-batches in the
             # usual order; a micro-batch that does not divide over the ranks is filled up by wrapping around to the start of the epoch's
@@ -593,8 +596,11 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
                 if last and (sync is None or sync.local):                           # one rank: trainable decoder layers are updated under this backward pass
                     opt.arm(grad_scale=1.0 / (n_mb * world), lr=linear_warmup_lr(float(args.lr_llm), global_step, total_steps))
                 loss = model.loss_and_backward(batch["tokens"], batch["attention_masks"], batch["pcrgbs"], batch["prompts"].shape[1],
-                                               model.dims.tok.pad, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device))
+                                               model.dims.tok.pad, fps_start=torch.zeros(len(idx), dtype=torch.int32, device=device),
+                                               **({} if soft is None else {"bin_soft": soft}))
                 run += loss / n_mb
+                if soft is not None:
+                    run_nll += model.last_nll / n_mb
             model.accumulate_grads = False
             if sync is not None:
                 sync.finish()
@@ -605,10 +611,14 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
                 entry = {"epoch": epoch, "step": global_step, "learning_rate": lr_now, "loss": float(loss) if n_mb == 1 else None}
                 if clip > 0:
                     entry["grad_norm"] = float(opt.last_grad_norm)
+                if soft is not None:                                                    # "loss" is the soft loss, "nll" the hard one of the same rows
+                    entry["nll"] = float(model.last_nll) if n_mb == 1 else None
                 step_log(entry)
             global_step += 1
         rec = {"epoch": epoch, "train_loss": float(run) / max(1, steps_per_epoch), "global_step": global_step,
                "learning_rate": linear_warmup_lr(float(args.lr_llm), global_step, total_steps)}
+        if soft is not None:                                                           # train_loss is the soft loss; train_nll stays comparable with the reference's
+            rec.update({"train_nll": float(run_nll) / max(1, steps_per_epoch), "bin_sigma": soft.sigma, "bin_radius": soft.radius})
         if clip > 0:                                                                   # one read of the device-side statistics per epoch
             gs = opt.grad_stats(reset=True)
             rec.update({k: gs[k] for k in ("grad_norm_mean", "grad_norm_max", "clipped_steps", "nonfinite_steps")})
@@ -619,9 +629,11 @@ def train(args, model, train_data, val_data=None, device="cuda", log=print, step
             m, _ = run_validation(model, val_data, args, device, max_batches=getattr(args, "val_batches", None))
             rec.update(m)
         if world > 1:
-            t = torch.tensor([rec["train_loss"]], device=device)
+            t = torch.tensor([rec["train_loss"]] + ([rec["train_nll"]] if soft is not None else []), device=device)
             dist.all_reduce(t)
-            rec["train_loss"] = float(t) / world
+            rec["train_loss"] = float(t[0]) / world
+            if soft is not None:
+                rec["train_nll"] = float(t[1]) / world
         history.append(rec)
         if rank == 0:
             log(json.dumps(rec))
@@ -712,6 +724,12 @@ def parse_args(argv=None):
                     help="train: clip the global gradient norm of every optimizer step to this value on the device (HF Trainer's "
                          "max_grad_norm / DeepSpeed's gradient_clipping); 'inf' only measures it; adds grad_norm_mean / grad_norm_max / "
                          "clipped_steps / nonfinite_steps to the epoch record and grad_norm to the step log (0: off, the reference does not clip)")
+    ap.add_argument("--bin_sigma", type=float, default=0.0,
+                    help="train with the bin-aware loss: a target that is a bin token becomes a discrete Gaussian of this width (in bins, at most 16) "
+                         "over the neighbouring bins, renormalised at the ends of the bin range; train_loss is then the soft loss and the epoch "
+                         "record gains train_nll (the reference's hard loss), bin_sigma and bin_radius, the step log nll (0: off, the reference's loss)")
+    ap.add_argument("--bin_radius", type=int, default=None,
+                    help="with --bin_sigma: cut the Gaussian this many bins from the target, 1 .. 32 (default min(32, ceil(3 * bin_sigma)))")
     ap.add_argument("--num_bins", type=int, default=256)
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", 0)))
@@ -772,6 +790,12 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if not a.max_grad_norm >= 0:
         ap.error("--max_grad_norm must be >= 0 (0: off)")
+    if not 0 <= a.bin_sigma <= 16:                                       # (refuses NaN and inf as well)
+        ap.error("--bin_sigma must be a finite width in bins, 0 <= bin_sigma <= 16 (0: off)")
+    if a.bin_radius is not None and not 1 <= a.bin_radius <= 32:
+        ap.error("--bin_radius must be between 1 and 32")
+    if a.bin_radius is not None and not a.bin_sigma > 0:
+        ap.error("--bin_radius goes with --bin_sigma")
     try:
         check_val_options(int(a.num_samples or 1), a.num_beams, a.val_sample, a.select, a.rescore, a.num_modes, a.mode_radius, a.soft_decode,
                           decoding_rules=False, constrain=a.constrain_traj)

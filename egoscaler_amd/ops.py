@@ -565,6 +565,21 @@ def cross_entropy(logits, targets, ignore_index, dlogits=None, grad_scale=1.0):
     return ls, cnt
 
 
+def cross_entropy_soft(logits, targets, ignore_index, spec, dlogits=None, grad_scale=1.0):
+    """The same loss against the bin-aware target `spec` = (p0, nb, sigma, radius) (traj.soft_target_spec; include/egomi.h,
+    egomi_ce_soft_fwd_bwd).  Returns (loss_sum fp32 [1], nll_sum fp32 [1], count i32 [1]): mean soft loss = loss_sum / count, mean hard
+    loss (what cross_entropy returns for the same rows) = nll_sum / count."""
+    R, V = logits.shape
+    p0, nb, sigma, radius = spec
+    cnt = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    sums = torch.zeros(2, dtype=torch.float32, device=logits.device)
+    rows = torch.empty(2, R, dtype=torch.float32, device=logits.device)
+    call("egomi_ce_count", targets, R, ignore_index, cnt, S())
+    call("egomi_ce_soft_fwd_bwd", logits, _ld(logits), targets, R, V, ignore_index, cnt, p0, nb, sigma, radius, sums[0:1], sums[1:2], rows[0], rows[1],
+         dlogits, _ld(dlogits) if dlogits is not None else 0, grad_scale, dt(logits.dtype), S())
+    return sums[0:1], sums[1:2], cnt
+
+
 def adamw(master, model_copy, grad, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, grad_scale_dev=None):
     """grad_scale_dev (a device fp32 scalar, clip_scale's out[2:3]): the scale is read on the device and `grad_scale` is not used."""
     if grad.dtype not in (torch.float32, torch.bfloat16) or not grad.is_contiguous() or grad.numel() != master.numel():

@@ -555,11 +555,18 @@ class TrajPointLLMForCausalLM(nn.Module):
         out = CausalLMOutput(logits=logits)
         return out if (return_dict is None or return_dict) else (logits,)
 
+    last_nll = None           # loss_and_backward(bin_soft=spec): the mean hard loss of the step's rows, a device fp32 scalar
+
     def loss_and_backward(self, input_ids, attention_mask, point_clouds, prompt_len, pad_token_id, fps_start=None,
-                          backward=True, grad_scale=1.0):
+                          backward=True, grad_scale=1.0, bin_soft=None):
         """Fused training step of train.py:166-183: forward, lm_head restricted to the trajectory span
         [Lp-1, S-1), cross-entropy with ignore_index=pad (mean), and the full backward, without
-        materialising [B,S,V] logits.  Returns the loss (fp32 scalar tensor)."""
+        materialising [B,S,V] logits.  Returns the loss (fp32 scalar tensor).
+
+        bin_soft=traj.soft_target_spec(tok, sigma, radius): the bin-aware loss.  Rows whose target is a bin token are scored against a
+        truncated discrete Gaussian over the neighbouring bins instead of the one-hot (ops.cross_entropy_soft, egomi_ce_soft_fwd_bwd); the
+        returned loss and the gradients are those of that soft loss, and self.last_nll holds the mean hard loss of the same rows (what the
+        call without bin_soft returns for these logits) as a device fp32 scalar, without a host sync.  None: the reference's loss."""
         eng = self.engine
         dev = eng.device
         input_ids = input_ids.to(dev)
@@ -578,7 +585,11 @@ class TrajPointLLMForCausalLM(nn.Module):
             hs = hn.view(B, S, d)[:, Lp - 1:S - 1].reshape(-1, d)
         tg = input_ids[:, Lp:].reshape(-1).contiguous()
         lg = eng.logits(hs, padded=backward)
-        ls, cnt = ops.cross_entropy(lg, tg, pad_token_id, dlogits=lg if backward else None, grad_scale=grad_scale)
+        if bin_soft is None:
+            ls, cnt = ops.cross_entropy(lg, tg, pad_token_id, dlogits=lg if backward else None, grad_scale=grad_scale)
+        else:
+            ls, nll, cnt = ops.cross_entropy_soft(lg, tg, pad_token_id, bin_soft, dlogits=lg if backward else None, grad_scale=grad_scale)
+            self.last_nll = (nll / cnt.float())[0]
         loss = ls / cnt.float()
         if backward:
             self._begin_backward(explicit=True)

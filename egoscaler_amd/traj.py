@@ -72,6 +72,31 @@ def grammar_spec(tok, min_steps: int, max_steps: int) -> GrammarSpec:
     return GrammarSpec(int(tok.p0), int(tok.num_bins), int(tok.ts), int(tok.tsep), int(tok.te), int(tok.eos), mn, mx)
 
 
+SoftTargetSpec = collections.namedtuple("SoftTargetSpec", "p0 nb sigma radius")
+
+
+def soft_target_spec(tok, sigma: float, radius=None) -> SoftTargetSpec:
+    """The bin-aware training target of loss_and_backward(bin_soft=...) for the tokenizer ids `tok`: a row whose target is one of the bin ids
+    tok.p0 .. tok.p0 + tok.num_bins - 1 is scored against a discrete Gaussian of width `sigma` (in bins, 0 < sigma <= 16) around that bin,
+    cut at `radius` bins (1 .. 32; default min(32, ceil(3 sigma))) and at the ends of the bin window and renormalised there; every other
+    target keeps its one-hot (include/egomi.h, egomi_ce_soft_fwd_bwd)."""
+    try:
+        s = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"soft_target_spec: sigma must be a number, not {sigma!r}") from None
+    if not 0.0 < s <= 16.0:                                                          # (refuses NaN as well)
+        raise ValueError(f"soft_target_spec: 0 < sigma <= 16 (bins) does not hold for {sigma!r}")
+    if radius is None:
+        w = min(32, int(np.ceil(3.0 * s)))
+    else:
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)):
+            raise ValueError(f"soft_target_spec: radius must be an integer, not {radius!r}")
+        w = int(radius)
+    if not 1 <= w <= 32:
+        raise ValueError(f"soft_target_spec: 1 <= radius <= 32 does not hold for {radius!r}")
+    return SoftTargetSpec(int(tok.p0), int(tok.num_bins), s, w)
+
+
 def detokenize_soft(ids: torch.Tensor, tok, max_steps: int, bin_mean, bin_std, bin_mass=None):
     """detokenize_batch with the per-token statistics of generate(output_bin_stats=True) / egomi_bin_stats in place of the bin centres
     (egomi_traj_detokenize_soft): the same scan of the same ids, and a step parsed from ids hit .. hit+5 takes

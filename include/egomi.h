@@ -749,6 +749,18 @@ int egomi_ce_count(const int64_t* targets, int64_t n, int64_t ignore, int32_t* c
 int egomi_ce_fwd_bwd(const void* logits, int64_t ld, const int64_t* targets, int R, int V, int64_t ignore, const int32_t* count,
                      float* loss_sum, float* row_loss, void* dlogits, int64_t ldd, float grad_scale, int dtype, egomi_stream_t stream);
 
+/* A12 (soft)  the same loss against a bin-aware target (label-distribution learning for the binned regression head); the reference's
+ * F.cross_entropy at models/pointllm/train.py:174-181 is its one-hot case.  count as above (zeroed, then ce_count).  A kept row whose target t
+ * is one of the nb contiguous bin ids p0 .. p0 + nb - 1 is scored against q[p0 + j] = w_j / Z, w_j = exp(-(j - i)^2 / (2 sigma^2)) for
+ * max(0, i - radius) <= j <= min(nb - 1, i + radius), i = t - p0, Z = sum w_j (float64, j ascending): truncation renormalises, no mass leaves
+ * the bin window, nb = 1 is the one-hot.  Every other kept target keeps the one-hot; ignored rows (t == ignore, t < 0, t >= V) give 0 and a
+ * zero gradient row.  row_loss[R] = sum_j q_j (lse - x_j), row_nll[R] = lse - x_t (the hard loss, comparable with ce_fwd_bwd's); loss_sum and
+ * nll_sum (fp32, zeroed by caller) += their sums in a fixed order (no atomics: the same bits every run).  dlogits (may alias logits, may be
+ * NULL) = (softmax - q) * grad_scale / count; nothing outside [row, row + V) is written.  sigma in bins, 0 < sigma <= 16; 1 <= radius <= 32. */
+int egomi_ce_soft_fwd_bwd(const void* logits, int64_t ld, const int64_t* targets, int R, int V, int64_t ignore, const int32_t* count,
+                          int p0, int nb, float sigma, int radius, float* loss_sum, float* nll_sum, float* row_loss, float* row_nll,
+                          void* dlogits, int64_t ldd, float grad_scale, int dtype, egomi_stream_t stream);
+
 /* AdamW step (torch.optim.AdamW semantics; reference optimizer models/pointllm/train.py:107-111).
  * fp32 master/moments/grad; model_copy (copy_dtype, may be NULL) receives the updated value. */
 int egomi_adamw(float* master, void* model_copy, const float* grad, float* m, float* v, int64_t n, float lr, float beta1,
