@@ -40,6 +40,7 @@ struct FastArgs {
                                          // epi 3 (EGOMI_EPI_SWIGLU_BWD): the product is d(act) [M, N]; C2 = gate|up [M, 2N] (read), C = d(gate|up) [M, 2N]
     int* tickets;                    // non-null: the K-slices of a tail tile are summed INSIDE the launch by the slice block that arrives last
                                      // (one ticket word per tail tile, zero on entry, returned to zero); ws then holds register-major slabs
+    int l2pf;                        // 352x256 and 256x256 per-tile kernels: tile step t touches the cache lines of K-tile min(t + l2pf, last) (l2pf_slot); 0 = off
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -47,6 +48,72 @@ typedef __attribute__((address_space(1))) const void gbl_void;
 
 __device__ __forceinline__ void glds16(const bf16_t* g, bf16_t* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((gbl_void*)g, (lds_void*)lds_wave_base, 16, 0, 0);
+}
+
+// ---- L2 touch (FastArgs::l2pf) of the 352x256 and the 256x256 per-tile kernels: in tile step t every wave reads 4 bytes of cache lines of K-tile
+// min(t + l2pf, last) — by LDS-DMA into a 256-B corner of LDS that nobody reads, so no register carries the data — and the ring's DMA of that tile, l2pf - 2
+// steps later, finds its lines in the XCD's L2 instead of waiting for HBM or the Infinity Cache.  Results cannot change: the data is never read.
+// OFF BY DEFAULT (l2pf_rule below returns 0): measured, the touches cost more than L2-hot sources give back (profiles/gemm_l2_prefetch.txt).
+// A block's K-tile is 128-B lines, one per A row and per B row (k-major B: 64 k-rows x 4 lines).  One touch instruction = one SLOT = 64 lanes on 64
+// consecutive rows of ONE operand, so everything but the lane index is scalar.  l2pf_slot is the one rule: the kernels feed its numbers to the instruction
+// (l2pf_touch) and egomi_gemm_l2pf_span walks l2pf_addr, the same numbers in the same 32-bit arithmetic, on the host (tests/test_gemm_l2pf_host.py):
+//   lane l reads the 4 bytes at  operand + base_off + (uint32)(min(row0 + l, rmax) * ld2)
+//   352x256 form, 16 slots (2 per wave): 0-5 A rows 64 s .. (the tile has 352: the last slot's upper half repeats row 351), 6-9 B rows, 10-15 idle
+//   256x256 form,  8 slots (1 per wave): 0-3 A rows, 4-7 B rows
+//   k-major B: slot 6 + c = the 64 k-rows of the K-tile (row stride ldb) at column 64 c of the tile: rows 0-63 relative to base_off
+//   an idle slot repeats the first line of slot s - 10 on all its lanes: every wave issues the same number of touches, which the vmcnt counts need
+// rmax clamps to the tile and to M - 1 / N - 1, the K-tile to [0, K / 64 - 1]: the 4 bytes lie inside [0, ((M - 1) lda + K) 2) of A, [0, ((N - 1) ldb + K) 2)
+// of B, [0, ((K - 1) ldb + N) 2) of a k-major B.  The 32-bit product cannot wrap: the 256-row forms' spans fit 31 bits of elements, 64 k-rows of a k-major B 32 bits of bytes.
+#define L2PF_TALL 0
+#define L2PF_TALL_KMAJOR 1
+#define L2PF_P8 2
+#define L2PF_TALL_ROWS 352
+#define L2PF_MAX 8
+struct L2pfSlot { int op; uint32_t row0, rmax, ld2; long long base_off; };
+__host__ __device__ __forceinline__ L2pfSlot l2pf_slot(int form, int slot, int m0, int n0, int M, int N, int K, int kt, long long lda, long long ldb) {
+    const int a_slots = form == L2PF_P8 ? 4 : 6, bm = form == L2PF_P8 ? 256 : L2PF_TALL_ROWS;
+    const bool idle = slot >= a_slots + 4;
+    const int s = idle ? slot - (a_slots + 4) : slot;
+    const int last = K / FT_BK - 1;
+    kt = kt < last ? kt : last;
+    kt = kt > 0 ? kt : 0;
+    L2pfSlot r;
+    int row0, rmax;
+    if (s < a_slots) {
+        r.op = 0; r.ld2 = (uint32_t)lda * 2u; r.base_off = (long long)kt * (FT_BK * 2);
+        row0 = m0 + 64 * s; rmax = m0 + bm - 1 < M - 1 ? m0 + bm - 1 : M - 1;
+    } else if (form == L2PF_TALL_KMAJOR) {
+        int c = n0 + 64 * (s - a_slots); c = c < N - 2 ? c : N - 2;
+        r.op = 1; r.ld2 = (uint32_t)ldb * 2u; r.base_off = ((long long)kt * FT_BK * ldb + c) * 2;
+        row0 = 0; rmax = FT_BK - 1;
+    } else {
+        r.op = 1; r.ld2 = (uint32_t)ldb * 2u; r.base_off = (long long)kt * (FT_BK * 2);
+        row0 = n0 + 64 * (s - a_slots); rmax = n0 + 255 < N - 1 ? n0 + 255 : N - 1;
+    }
+    if (row0 > rmax) row0 = rmax;
+    if (idle) rmax = row0;
+    r.row0 = (uint32_t)row0; r.rmax = (uint32_t)rmax;
+    return r;
+}
+// -> operand (0 A, 1 B) and the byte offset from its base of the 4 bytes lane `lane` of slot `slot` reads
+__host__ __device__ __forceinline__ int l2pf_addr(int form, int slot, int lane, int m0, int n0, int M, int N, int K, int kt, long long lda, long long ldb, long long* off) {
+    const L2pfSlot r = l2pf_slot(form, slot, m0, n0, M, N, K, kt, lda, ldb);
+    const uint32_t row = r.row0 + (uint32_t)lane < r.rmax ? r.row0 + (uint32_t)lane : r.rmax;
+    *off = r.base_off + (long long)(uint32_t)(row * r.ld2);
+    return r.op;
+}
+// one touch instruction, one statement on ONE VGPR that dies in it (the 256x256 kernel has none to spare; a C++ address, hoisted out of the K loop, would be
+// a register neither kernel has): lane index, + row0, min rmax, * ld2, load.  `lds_corner`: LDS byte address of 256 B nobody reads.
+__device__ __forceinline__ void l2pf_touch(const FastArgs& g, int form, int slot, int m0, int n0, int kt, uint32_t lds_corner) {
+    const L2pfSlot r = l2pf_slot(form, slot, m0, n0, g.M, g.N, g.K, kt, g.lda, g.ldb);
+    const uint64_t b = (uint64_t)(uintptr_t)(r.op ? g.B : g.A) + (uint64_t)r.base_off;
+    const uint64_t bs = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+    uint32_t v, m0_saved;                                               // m0 is the compiler's (the 256x256 kernel's DMAs are builtins): handed back as it was
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_add_u32 %0, %2, %0\n\tv_min_u32 %0, %3, %0\n\tv_mul_lo_u32 %0, %0, %4\n\t"
+                 "s_mov_b32 %1, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dword %0, %5\n\ts_mov_b32 m0, %1"
+                 : "=&v"(v), "=&s"(m0_saved)
+                 : "s"(__builtin_amdgcn_readfirstlane(r.row0)), "s"(__builtin_amdgcn_readfirstlane(r.rmax)), "s"(__builtin_amdgcn_readfirstlane(r.ld2)), "s"(bs), "s"(lds_corner)
+                 : "memory");
 }
 
 // ---- interior fast path of the epilogue: whole sub-tile in bounds, alpha = 1, no bias / activation, 4-aligned leading
@@ -494,6 +561,10 @@ void gemm_nt_bf16_m256_kernel(FastArgs g) {
 //                       ph2 reads B-h1         MFMA (A0,B1)   DMA B-h0(t+2) -> b   (B-h0 reads retired by lgkmcnt(8) in ph1)
 //                       ph3 reads A-h1         MFMA (A1,B1)   DMA A-h0(t+2) -> b
 //                       ph4 (B0 kept in regs)  MFMA (A1,B0)   DMA B-h1(t+2) -> b ; vmcnt(6): tile t+1 has landed
+//   L2 touch (FastArgs::l2pf = D > 0, l2pf_slot above; off by default): ph4, the stage without ds_reads, issues ONE more load per wave and tile after its DMA — 8 waves x 64
+//   lanes = the 256 + 256 lines of K-tile min(t + D, t_last), t_last being the block's own (a K-slice block re-touches its slice's last tile, as the tail's
+//   DMAs re-load it).  Loads return in order, so the wait becomes vmcnt(7): the 6 DMAs of tile t+2 plus the touch may be outstanding, A-h1(t+1) and all
+//   before it have landed.  The prologue issues no touch and keeps vmcnt(6): K-tiles 2 .. D-1 are fetched as before.  D = 0 runs the code as it was.
 //   rows beyond M / N clamp on load, mask on store; DMAs past the last K-tile re-load the last tile into
 //   buffers nobody reads any more, which keeps the vmcnt arithmetic constant.
 // =================================================================================================
@@ -518,7 +589,7 @@ extern "C" int egomi_gemm_stamp_reset() { unsigned long long z[16] = {0}; return
 template <typename TC>
 __global__ __launch_bounds__(512, 2)
 void gemm_nt_bf16_8phase_kernel(FastArgs g) {
-    __shared__ __attribute__((aligned(16))) bf16_t smem[2 * 4 * P8_HT];
+    __shared__ __attribute__((aligned(16))) bf16_t smem[2 * 4 * P8_HT + 128];                // (+ 256 B: where the L2 touches drop their data)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 2, wc = wave & 3;
@@ -607,8 +678,13 @@ void gemm_nt_bf16_8phase_kernel(FastArgs g) {
         asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory"); P8_BAR P8_MMA(0, fb0, 0) P8_BAR \
         /* ph2 */ P8_LDB(fb1, b, 1) P8_PF(b, 2, pB2, offB[0]) P8_BAR P8_MMA(0, fb1, 1) P8_BAR \
         /* ph3 */ P8_LDA(b, 1) P8_PF(b, 0, pA2, offA[0]) P8_BAR P8_MMA(1, fb1, 1) P8_BAR \
-        /* ph4 */ P8_PF(b, 3, pB2, offB[1]) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); P8_BAR P8_MMA(1, fb0, 0) P8_BAR \
+        /* ph4 */ P8_PF(b, 3, pB2, offB[1]) \
+        if (pfd) { l2pf_touch(g, L2PF_P8, wave, m0, n0, (tt) + pfd < t_last ? (tt) + pfd : t_last, pf_lds); asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); } \
+        else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); \
+        P8_BAR P8_MMA(1, fb0, 0) P8_BAR \
     }
+    const int pfd = g.l2pf;                                           // L2 touch distance in K-tiles, 0 = off (block-uniform)
+    const uint32_t pf_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((lds_void*)smem) + 2 * 4 * P8_HT * 2);
 
     // ---- prologue: tile t_begin complete, three half-tiles of the next one in flight
     {
@@ -841,11 +917,17 @@ void gemm_nt_bf16_8phase_kernel(FastArgs g) {
 //          own parity, so the swizzled source offset inside a group is the same VGPR for all of them; the group's row offset
 //          is scalar.  Needs M % 8 == 0 and N % 8 == 0 (a ragged tile clamps whole 8-row groups), M, N >= 8.
 //   88 MFMAs per K-tile and wave on 30 ds_read_b128 (0.34 per MFMA; the 256x256 form: 0.375), 10 (9) DMA instructions.
+//   L2 touch (FastArgs::l2pf = D > 0, l2pf_slot above; off by default): ph1, the one stage without a DMA, issues TWO more loads per wave and tile step after its 8 ds_reads —
+//          16 x 64 lanes over the 352 + 256 lines of K-tile min(t + D, t_last); every wave issues both in every step, also when the target is clamped.
+//          Loads return in order, so ph4 then waits vmcnt(8): B-h1, A-c0, B-h0 of tile t+2 (6) and the step's 2 touches may be outstanding, A-c2(t+1) from
+//          the step before and everything older has landed.  A touch is therefore waited for one whole tile step after its issue, like a DMA.  The
+//          prologue issues no touch and keeps vmcnt(8): K-tiles 2 .. D-1 are fetched as before.  D = 0 runs the code as it was (vmcnt(6)).
 // =================================================================================================
 #define TL_NB 11
 #define TL_BM (32 * TL_NB)
 #define TL_AB (TL_BM * 128)                       // bytes of the A image of one buffer
 #define TL_BUFB (TL_AB + 256 * 128)               // bytes per buffer
+static_assert(TL_BM == L2PF_TALL_ROWS, "l2pf_addr deals the 352x256 form's lines");
 __device__ __forceinline__ void tl_dma(const char* gbase, uint32_t voff, uint32_t lds_base) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(gbase), "s"(lds_base) : "memory");
 }
@@ -858,7 +940,7 @@ typedef __attribute__((address_space(3))) tl_bf16x4 tl_lds_bf16x4;
 template <typename TC, bool TBK>
 __global__ __launch_bounds__(512, 2)
 void gemm_nt_bf16_tall_kernel(FastArgs g) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * TL_BUFB];
+    __shared__ __attribute__((aligned(16))) char smem[2 * TL_BUFB + 256];                       // (+ 256 B: where the L2 touches drop their data)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 2, wc = wave & 3;
@@ -971,7 +1053,8 @@ void gemm_nt_bf16_tall_kernel(FastArgs g) {
         __builtin_amdgcn_s_setprio(0);
 #define TL_BAR __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0);
 
-    // (TL_ABL: timing-only ablation builds of tools/debug/tall_ablate.py — 1 no fragment reads, 2 no DMA, 4 one barrier per phase, 8 no MFMA, 16 every DMA reads K-tile 0; results are garbage)
+    // (TL_ABL: timing-only ablation builds of tools/debug/tall_ablate.py — 1 no fragment reads, 2 no DMA, 4 one barrier per phase, 8 no MFMA, 16 every DMA reads K-tile 0,
+    //  32 L2 touches at distance 4 whatever the launch says (34 = the touch loads alone); results are garbage)
 #ifndef TL_ABL
 #define TL_ABL 0
 #endif
@@ -982,6 +1065,8 @@ void gemm_nt_bf16_tall_kernel(FastArgs g) {
 #define TL_MMA_(c, n, fbv, X) if (!(TL_ABL & 8)) { TL_MMA(c, n, fbv, X) }
 #define TL_BAR2 if (!(TL_ABL & 4)) { TL_BAR }
 
+    const int pfd = (TL_ABL & 32) ? 4 : g.l2pf;                       // L2 touch distance in K-tiles, 0 = off (block-uniform)
+    const uint32_t pf_lds = __builtin_amdgcn_readfirstlane(lds0 + 2 * TL_BUFB);
     // ---- prologue: tile 0 complete, all but A-c2 of tile 1 in flight; B-h0 of tile 0 in registers
     {
         const int t1 = 1 < t_last ? 1 : t_last;
@@ -1002,10 +1087,17 @@ void gemm_nt_bf16_tall_kernel(FastArgs g) {
         const char* pA1 = Ab + (long long)t1 * 128;
         const char* pA2 = Ab + (long long)t2 * 128;
         const char* pB2 = Bb + (long long)t2 * strideB;
-        /* ph1 */ TL_LDA_(0, 4) TL_BAR TL_MMA_(0, 4, fb0, 0) TL_BAR2
+        /* ph1 */ TL_LDA_(0, 4)
+        if (pfd) {
+            const int tp = t + pfd < t_last ? t + pfd : t_last;
+            l2pf_touch(g, TBK ? L2PF_TALL_KMAJOR : L2PF_TALL, wave * 2, m0, n0, tp, pf_lds);
+            l2pf_touch(g, TBK ? L2PF_TALL_KMAJOR : L2PF_TALL, wave * 2 + 1, m0, n0, tp, pf_lds);
+        }
+        TL_BAR TL_MMA_(0, 4, fb0, 0) TL_BAR2
         /* ph2 */ TL_LDB_(fb1, 1) TL_PFB_(bo, 0, pB2) TL_BAR TL_MMA_(0, 4, fb1, 1) TL_BAR2
         /* ph3 */ TL_LDA_(1, 4) TL_PFA_(bo, 0, pA2) TL_BAR TL_MMA_(1, 4, fb1, 1) TL_BAR2
-        /* ph4 */ TL_PFB_(bo, 1, pB2) if (!(TL_ABL & 2)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        /* ph4 */ TL_PFB_(bo, 1, pB2)
+        if (!(TL_ABL & 2)) { if (pfd) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
         TL_BAR TL_MMA_(1, 4, fb0, 0) TL_BAR2
         /* ph5 */ TL_LDA_(2, 3) TL_PFA_(bo, 1, pA2) TL_BAR TL_MMA_(2, 3, fb0, 0) TL_BAR2
         /* ph6 */
@@ -1586,8 +1678,11 @@ static bool plain_slabs(const egomi_gemm_desc* d, bool tail_rows) {
 }
 
 // tile choice: 8 = 256x256 8-phase kernel, 2 = 256x128, 1 = 128x128.  EGOMI_GEMM_TILE=1|2|8 overrides (A/B runs).
+static int g_tile_forced = -1;                                           // -1: EGOMI_GEMM_TILE is (re)read at the next use
+extern "C" int egomi_gemm_set_tile(int tile) { g_tile_forced = tile < 0 ? -1 : tile; return EGOMI_OK; }
 static int tile_choice(const egomi_gemm_desc* d) {
-    static const int forced = egomi_env_int("EGOMI_GEMM_TILE", 0);
+    if (g_tile_forced < 0) { g_tile_forced = egomi_env_int("EGOMI_GEMM_TILE", 0); if (g_tile_forced < 0) g_tile_forced = 0; }
+    const int forced = g_tile_forced;
     if (forced == 1 || forced == 2 || forced == 8) return forced;
     // measured (tools/gemm_bench.py, M=5536): 256x128 wins only where N is wide enough to keep every CU at
     // 2 resident blocks to the end (N=11008: 1168 vs 1084 TFLOP/s); at N=4096 its 704 tiles quantise worse
@@ -1842,9 +1937,26 @@ static bool tall_form(const egomi_gemm_desc* d) {
     return c352 < 0.98 * c256_model(t256, d->workspace != nullptr);
 }
 
+// ---- L2 touch distance (FastArgs::l2pf, l2pf_slot at the top of the file) of a launch: decided here, after the route, and no part of it.
+// EGOMI_GEMM_L2PF / egomi_gemm_set_l2_prefetch: -1 the rule below (default), 0 off, 1..8 that distance in every launch of the two kernels (A/B runs, tests).
+static int g_l2pf_mode = -2;                                             // -2: EGOMI_GEMM_L2PF is (re)read at the next use
+extern "C" int egomi_gemm_set_l2_prefetch(int d) { g_l2pf_mode = d < 0 ? -2 : (d > L2PF_MAX ? L2PF_MAX : d); return EGOMI_OK; }
+static int l2pf_rule(int form, int K, long long blocks);
+static int l2pf_distance(int form, int K, long long blocks) {
+    if (g_l2pf_mode == -2) { g_l2pf_mode = egomi_env_int("EGOMI_GEMM_L2PF", -1); if (g_l2pf_mode < -1 || g_l2pf_mode > L2PF_MAX) g_l2pf_mode = -1; }
+    return g_l2pf_mode >= 0 ? g_l2pf_mode : l2pf_rule(form, K, blocks);
+}
+// the rule: per form, K and round count (blocks over CUs).  0 for every launch: at every distance, shape and form measured the touches cost more than
+// the L2-hot sources give back (profiles/gemm_l2_prefetch.txt), so the kernels run the code they ran before.  The path stays as a measured A/B switch.
+static int l2pf_rule(int form, int K, long long blocks) {
+    (void)form; (void)K; (void)blocks;
+    return 0;
+}
+
 static int launch_tall(const egomi_gemm_desc* d, FastArgs& g, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
     g.tiles_m = (d->M + TL_BM - 1) / TL_BM; g.tiles_n = (d->N + 255) / 256;
     g.splitk = 1; g.ws = nullptr; g.tickets = nullptr;
+    g.l2pf = l2pf_distance(L2PF_TALL, d->K, (long long)g.tiles_m * g.tiles_n);
     static const int group = egomi_env_int("EGOMI_TALL_GROUP", 8);
     g.full_tm = group < 1 ? 8 : group;
     const int nwg = g.tiles_m * g.tiles_n;
@@ -1905,6 +2017,7 @@ int egomi_tall_kmajor_try(const egomi_gemm_desc* d, hipStream_t s, bool query) {
     g.M = d->M; g.N = Na; g.K = d->K; g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc; g.alpha = 1.0f;
     g.tiles_m = (d->M + TL_BM - 1) / TL_BM; g.tiles_n = Na / 256;
     g.splitk = 1; g.full_tm = 8;
+    g.l2pf = l2pf_distance(L2PF_TALL_KMAJOR, d->K, (long long)g.tiles_m * g.tiles_n);
     EGOMI_LAUNCH((gemm_nt_bf16_tall_kernel<bf16_t, true>), dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
     if (Na == d->N) { egomi_route_set(11, 1, d->M, 0, 0); return egomi_launch_status(); }
     egomi_gemm_desc d2 = *d;                                             // the rest on gemm_tn.hip's 256x256 tiles (its own tail plan)
@@ -1947,6 +2060,7 @@ static int launch_8phase(const egomi_gemm_desc* d, FastArgs& g, const TailPlan t
     g.tickets = nullptr;
     if (tp.rows && tickets && tp.rows * g.tiles_n <= 1024 && (long long)tp.rows * g.tiles_n * tp.s * 262144 <= d->workspace_bytes) g.tickets = tickets;
     const int nwg = g.full_tiles + tp.rows * g.tiles_n * tp.s;
+    g.l2pf = l2pf_distance(L2PF_P8, d->K, nwg);
     if (d->c_dtype != EGOMI_BF16 && d->c_dtype != EGOMI_F32) return EGOMI_E_UNSUPPORTED;
     if (t0) (void)hipEventRecord(t0, s);                                 // egomi_gemm_time_next: this kernel alone
     if (d->c_dtype == EGOMI_BF16) EGOMI_LAUNCH(gemm_nt_bf16_8phase_kernel<bf16_t>, dim3(nwg, 1), dim3(512), 0, s, g);
@@ -2101,7 +2215,7 @@ int egomi_gemm_fast_try(const egomi_gemm_desc* d0, hipStream_t s) {
     FastArgs g;
     g.A = (const bf16_t*)d->A; g.B = (const bf16_t*)d->B; g.C = d->C; g.bias = (const bf16_t*)d->bias; g.residual = d->residual;
     g.M = d->M; g.N = d->N; g.K = d->K; g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc; g.ldr = d->ldr;
-    g.alpha = d->alpha; g.accumulate = d->accumulate; g.act = d->act; g.tickets = nullptr;
+    g.alpha = d->alpha; g.accumulate = d->accumulate; g.act = d->act; g.tickets = nullptr; g.l2pf = 0;
     g.epi = d->epilogue == EGOMI_EPI_SLABS ? 0 : d->epilogue;            // (slabs are the host's business: the kernels run a plain epilogue)
     g.C2 = d->C2; g.ldc2 = d->ldc2;
     switch (r.form) {
@@ -2133,5 +2247,34 @@ extern "C" int egomi_gemm_tail_plan(const egomi_gemm_desc* d0, int* row0, int* s
     const GemmRoute r = gemm_route(&dl);
     if (r.form != FORM_TALL && r.form != FORM_8PHASE) return EGOMI_E_UNSUPPORTED;
     if (r.tail.rows) { *row0 = ((dl.M + 255) / 256 - r.tail.rows) * 256; *slices = r.tail.s; }
+    return EGOMI_OK;
+}
+// What the L2 touches of a launch would read (host only, launches nothing): l2pf_addr walked over every tile, touch slot, lane and target K-tile of
+// the descriptor's product in the 352x256 form (tall != 0; b_layout 1 = its k-major B instantiation, N % 256 == 0) or the 256x256 per-tile form
+// (tall == 0, b_layout 0) at distance `dist`.  out4 = {min, max byte offset into A, min, max into B} of the first of the 4 bytes a lane reads,
+// -1 where nothing is touched (dist = 0).  Whole tiles touch K-tiles min(dist, last) .. last; a K-slice block of the 256x256 form clamps to its own
+// slice's last tile, which may be any: that form is walked from K-tile 0.
+extern "C" int egomi_gemm_l2pf_span(const egomi_gemm_desc* d, int tall, int dist, int64_t* out4) {
+    if (!d || !out4 || d->M < 1 || d->N < 2 || d->K < FT_BK || (d->K % FT_BK) || dist < 0) return EGOMI_E_BADARG;
+    if (d->b_layout != 0 && (!tall || (d->N & 255))) return EGOMI_E_UNSUPPORTED;
+    out4[0] = out4[1] = out4[2] = out4[3] = -1;
+    if (!dist) return EGOMI_OK;
+    if (dist > L2PF_MAX) dist = L2PF_MAX;
+    const int form = !tall ? L2PF_P8 : (d->b_layout ? L2PF_TALL_KMAJOR : L2PF_TALL);
+    const int bm = tall ? TL_BM : 256, slots = tall ? 16 : 8, last = d->K / FT_BK - 1;
+    const int kts[2] = {tall ? (dist < last ? dist : last) : 0, last};   // (offsets grow with the K-tile: the ends of the range give the extremes)
+    bool seen[2] = {false, false};
+    for (int m0 = 0; m0 < d->M; m0 += bm)
+        for (int n0 = 0; n0 < d->N; n0 += 256)
+            for (int slot = 0; slot < slots; ++slot)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 2; ++e) {
+                        long long off;
+                        const int op = l2pf_addr(form, slot, lane, m0, n0, d->M, d->N, d->K, kts[e], d->lda, d->ldb, &off);
+                        int64_t* o = out4 + 2 * op;
+                        if (!seen[op] || off < o[0]) o[0] = off;
+                        if (!seen[op] || off > o[1]) o[1] = off;
+                        seen[op] = true;
+                    }
     return EGOMI_OK;
 }

@@ -184,6 +184,19 @@ int egomi_gemm_kernel_id(const egomi_gemm_desc* desc);
  * Whole tiles are bit-identical to the 256x256 form's (same K order per element), fused epilogues included.
  * Process-wide, not thread-safe: measurement and tests only.  No reference counterpart (torch.nn.Linear's GEMM is the vendor library's). */
 int egomi_gemm_set_tall(int mode);
+/* The tile choice of the bf16 NT kernels, as EGOMI_GEMM_TILE sets it for a whole process: 1 = 128x128, 2 = 256x128, 8 = the 256-row forms whatever the
+ * product's size (tests reach those kernels at shapes of a few tiles with it), 0 = the library's rule, -1 = back to EGOMI_GEMM_TILE / the rule.
+ * Process-wide, not thread-safe: measurement and tests only.  No reference counterpart. */
+int egomi_gemm_set_tile(int tile);
+/* L2 touch of the 352x256 and the 256x256 per-tile kernels: in tile step t a block reads 4 bytes of each 128-B line of K-tile min(t + d, last) of its
+ * A and B panels and throws them away, so that the LDS-DMA of that tile hits in L2.  Decided per launch AFTER the route and no part of it; results are
+ * bit for bit the same at every d.  d = -1: back to EGOMI_GEMM_L2PF / the library's rule (default), 0 = off (the kernels run as without the feature),
+ * 1..8 = that distance in every launch.  Process-wide, not thread-safe: measurement and tests only.  No reference counterpart. */
+int egomi_gemm_set_l2_prefetch(int d);
+/* Host-only query, launches nothing: the byte offsets those touches would read for this descriptor's M, N, K, lda, ldb and b_layout in the 352x256 form
+ * (tall != 0; b_layout 1 = k-major B, N % 256 == 0) or the 256x256 per-tile form (tall == 0, b_layout 0) at distance dist, over every tile, wave, lane and
+ * tile step.  out4 = {min, max offset into A, min, max into B} of the first of the 4 bytes a lane reads; -1 where nothing is touched (dist = 0). */
+int egomi_gemm_l2pf_span(const egomi_gemm_desc* desc, int tall, int dist, int64_t* out4);
 int egomi_gemm_slab_count(const egomi_gemm_desc* desc);   /* EGOMI_EPI_SLABS: slices egomi_gemm will leave for this descriptor, 0 = none */
 /* EGOMI_EPI_SLABS on a LARGE product (egomi_gemm_kernel_id == 2): whole 256-row tiles get the normal epilogue (residual
  * included); the K-sliced tail rows [row0, M) are left as `slices` fp32 slabs [slices][M - row0][N] at the start of the slab

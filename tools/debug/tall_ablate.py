@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Timing-only ablations of gemm_nt_bf16_tall_kernel (csrc/gemm_fast.hip, -DTL_ABL=mask: 1 no fragment reads, 2 no LDS-DMA, 4 one barrier per phase,
-8 no MFMA, 16 every DMA re-reads K-tile 0 (L2-hot operands); results are garbage, only the launch time means anything).  `python tools/debug/tall_ablate.py build` (anywhere hipcc is), then on the GPU box
+8 no MFMA, 16 every DMA re-reads K-tile 0 (L2-hot operands), 32 L2 touches at distance 4 whatever the launch says — 34 = the touch loads alone, 32 = the kernel with them; results are garbage, only the launch time means anything).  `python tools/debug/tall_ablate.py build` (anywhere hipcc is), then on the GPU box
 `python tools/debug/tall_ablate.py` runs every variant in a process of its own on two shapes."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 LIBDIR = os.path.join(ROOT, "egoscaler_amd", "lib")
-MASKS = (0, 2, 16, 24)
+MASKS = (0, 2, 16, 24, 32, 34)
 if len(sys.argv) > 1 and sys.argv[1] == "build":
     from egoscaler_amd import build
     build.build()
