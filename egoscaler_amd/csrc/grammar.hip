@@ -43,6 +43,20 @@
 //      written, and no byte outside [row, row + V * sizeof) is: the ld - V padding columns and the neighbouring rows stay as they are.
 //   No atomics; rem and col are launch constants.  m, s and Z come from loads whose order depends on V only, and the stored bits from the
 //   element index only: a row's bits depend on its values, its state and (V, spec, dtype), not on R, its slot, ld or its alignment.
+//
+// Motion limits (egomi_traj_grammar_init_limits / egomi_traj_grammar_step_limits): the same two kernels with one template flag.  Per row a
+//   table lim int32 [18] = lo[6] | hi[6] | dmax[6] in bins and a pose int32 [12] = prev[6] | cur[6]: prev = the bins of the last CLOSED step
+//   (-1: unknown), cur = the bins of the open step seen so far.  The pose moves with gr_advance's transitions and adds none: a
+//   bin taken at phase p sets cur[p]; <tsep> taken at phase 6 copies cur to prev; <ts> taken at phase 9 sets prev to -1; a token that does
+//   not move the phase leaves the pose alone.  (The step never clears cur: cur[p] is meaningful below the phase only.  The init kernel
+//   writes -1 there.)  Where the state allows bins at phase p, dimension d = p and q = prev[d], the window of bin indices is (gr_window)
+//       q < 0:  [lo, hi]           else  a = max(lo, q - dmax), b = min(hi, q + dmax)
+//       a > b (q lies farther than dmax outside the box): the cap wins, a = b = min(max(e, q - dmax), q + dmax) with e = q < lo ? lo : hi
+//   never empty, always inside [0, nb - 1]; lo, hi, dmax and q are clamped into range on load, so a bad table cannot move the window out of
+//   the bin ids.  Everything else -- need, rem >= 9, when <te> is allowed, the special ids -- is the grammar's.  mass keeps its meaning
+//   (what the grammar ALONE allows); limits_mass[r, col] is the same sum over the window: the second slot of the one block_sum2_f64 call,
+//   the same float64 terms in the same order, so a full-range table gives limits_mass bit-equal to mass.  Thread 0 stores the pose after
+//   the last barrier, like the state.  The init kernel commits prev at a <tsep> only when the run before it held six bins (else -1).
 #include "lp_row.h"                      // lp_row_max_sumexp, block_sum2_f64: shared with csrc/logprob.hip
 
 struct GrammarSpec {
@@ -94,23 +108,54 @@ __device__ __forceinline__ int gr_need(int phase, int steps, const GrammarSpec& 
     return (int)(n < never ? n : never);
 }
 
+__device__ __forceinline__ int gr_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the window [wa, wb] of bin indices for a dimension with limits (lo, hi, dmax) whose last closed step chose bin q (-1: unknown)
+__device__ __forceinline__ void gr_window(int lo, int hi, int dmax, int q, int nb, int& wa, int& wb) {
+    lo = gr_clamp(lo, 0, nb - 1);
+    hi = gr_clamp(hi, lo, nb - 1);
+    dmax = gr_clamp(dmax, 0, nb - 1);
+    q = gr_clamp(q, -1, nb - 1);
+    wa = lo; wb = hi;
+    if (q < 0) return;
+    wa = max(lo, q - dmax);
+    wb = min(hi, q + dmax);
+    if (wa > wb) wa = wb = min(max(q < lo ? lo : hi, q - dmax), q + dmax);
+}
+
+template <bool POSE>
 __global__ __launch_bounds__(64) void traj_grammar_init_kernel(const int64_t* ids, long long ld_ids, const uint8_t* mask, long long ld_mask, int R,
-                                                               int S0, GrammarSpec g, int32_t* state, int32_t* need) {
+                                                               int S0, GrammarSpec g, int32_t* state, int32_t* need, int32_t* pose) {
     const int r = blockIdx.x * 64 + threadIdx.x;
     if (r >= R) return;
     const int64_t* row = ids + (long long)r * ld_ids;
     const uint8_t* mk = mask ? mask + (long long)r * ld_mask : nullptr;
     bool seen = false;
     int steps = 0, run = 0;
+    int prev[6], cur[6];                                                 // POSE only
+    if (POSE)
+        for (int d = 0; d < 6; ++d) prev[d] = cur[d] = -1;
     for (int j = 0; j < S0; ++j) {
         if (mk && mk[j] == 0) continue;
         const long long t = row[j];
+        const bool bin = gr_is_bin(t, g);
+        if (POSE && seen) {
+#pragma unroll
+            for (int d = 0; d < 6; ++d) {
+                if (t == g.ts) prev[d] = -1;
+                else if (t == g.tsep) prev[d] = run == 6 ? cur[d] : -1;
+                if (bin && run == d) cur[d] = (int)(t - g.p0);
+                else if (!bin || t == g.ts) cur[d] = -1;                 // every token that ends a run
+            }
+        }
         if (t == g.ts) { seen = true; steps = 0; run = 0; }
         else if (!seen) continue;
         else if (t == g.tsep) { ++steps; run = 0; }
-        else if (gr_is_bin(t, g)) { if (run < 6) ++run; }
+        else if (bin) { if (run < 6) ++run; }
         else run = 0;
     }
+    if (POSE)
+        for (int d = 0; d < 6; ++d) { pose[12 * r + d] = prev[d]; pose[12 * r + 6 + d] = cur[d]; }
     const int phase = seen ? run : 9;
     if (!seen) steps = 0;
     state[2 * r] = phase;
@@ -123,6 +168,7 @@ struct GrammarStepArgs {
     const int64_t* tok_prev; int32_t* state;
     GrammarSpec g; int rem;
     float* mass; long long ld_mass; int col;
+    const int32_t* lim; int32_t* pose; float* limits_mass;              // the LIM kernels only
 };
 
 template <typename T> struct NegInf;
@@ -131,38 +177,71 @@ template <> struct NegInf<float> { static constexpr uint32_t word = 0xFF800000u;
 __device__ __forceinline__ void gr_store_ninf(bf16_t* p) { *p = NegInf<bf16_t>::one; }
 __device__ __forceinline__ void gr_store_ninf(float* p) { *p = -INFINITY; }
 
-template <typename T, bool REG>
+template <typename T, bool REG, bool LIM>
 __global__ __launch_bounds__(LPB_THREADS) void traj_grammar_step_kernel(GrammarStepArgs a) {
     __shared__ float red[16];
     __shared__ double red2[32];
     const int r = blockIdx.x, tid = threadIdx.x, V = a.V;
     int phase = a.state[2 * r], steps = a.state[2 * r + 1];             // read by every thread before the first barrier; stored after the last
+    // LIM: the row's whole table and pose, loaded here beside the state: their addresses depend on r alone, so they travel with the state's
+    // load and not, entry by entry, behind the phase it yields (three more dependent round trips in front of the row pass)
+    int lm[18], ps0[12];
+    if (LIM) {
+#pragma unroll
+        for (int i = 0; i < 18; ++i) lm[i] = a.lim[18 * (long long)r + i];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) ps0[i] = a.pose[12 * (long long)r + i];
+    }
+    const int phase0 = phase;
     if (a.tok_prev) gr_advance(phase, steps, a.tok_prev[r], a.g);
     bool bins;
     long long sp;
     gr_allowed(phase, steps, a.rem, a.g, bins, sp);
+    // LIM: what the token does to the pose (stored by thread 0 below), and the window [wa, wb] of bin indices under the moved pose
+    const bool moved = LIM && a.tok_prev && phase != phase0;
+    const bool set_cur = moved && phase0 >= 0 && phase0 <= 5 && phase == phase0 + 1;       // a bin taken at phase0
+    const bool commit = moved && phase0 == 6;                                                // <tsep>: prev = cur
+    const bool reset = moved && phase0 == 9;                                                 // <ts>: prev = -1
+    int wa = 0, wb = a.g.nb - 1;
+    if (LIM && bins) {
+#pragma unroll
+        for (int d = 0; d < 6; ++d)                                      // (selects: the arrays stay in registers)
+            if (d == phase) gr_window(lm[d], lm[6 + d], lm[12 + d], reset ? -1 : (commit ? ps0[6 + d] : ps0[d]), a.g.nb, wa, wb);
+    }
     T* lg = (T*)a.logits + (long long)r * a.ld;
     float m, s;
     lp_row_max_sumexp<T, REG>(lg, V, red, m, s);
-    double Z = 0.0, unused = 0.0;
+    double Z = 0.0, Zw = 0.0;                                            // Zw: the same terms over the window (LIM; else unused)
     if (bins && tid < a.g.nb) {
         const float xi = Cvt<T>::ld(lg + a.g.p0 + tid);
         Z = (double)(xi == -INFINITY ? 0.f : expf(xi - m));
+        if (LIM && tid >= wa && tid <= wb) Zw = Z;
     }
-    block_sum2_f64(Z, unused, red2);                                     // (after its barriers every load of the row pass has completed)
+    block_sum2_f64(Z, Zw, red2);                                         // (after its barriers every load of the row pass has completed)
     if (tid == 0) {
         if (sp >= 0) {
             const float xs = Cvt<T>::ld(lg + sp);
-            Z += (double)(xs == -INFINITY ? 0.f : expf(xs - m));
+            const double zs = (double)(xs == -INFINITY ? 0.f : expf(xs - m));
+            Z += zs;
+            Zw += zs;
         }
         a.mass[(long long)r * a.ld_mass + a.col] = (float)Z / s;
         if (a.tok_prev) { a.state[2 * r] = phase; a.state[2 * r + 1] = steps; }
+        if (LIM) {
+            a.limits_mass[(long long)r * a.ld_mass + a.col] = (float)Zw / s;
+            int32_t* ps = a.pose + 12 * (long long)r;
+            if (set_cur) ps[6 + phase0] = (int32_t)(a.tok_prev[r] - a.g.p0);
+            if (commit || reset) {
+#pragma unroll
+                for (int d = 0; d < 6; ++d) ps[d] = commit ? ps0[6 + d] : -1;
+            }
+        }
     }
     // the mask: 16-byte aligned blocks of the row's bytes, block k at base + 16 k
     constexpr int EPB = 16 / (int)sizeof(T);
     const uintptr_t row = (uintptr_t)lg, row_end = row + (uintptr_t)V * sizeof(T), base = row & ~(uintptr_t)15;
     const long long nblk = (long long)((row_end - base + 15) >> 4);
-    const long long a0 = bins ? a.g.p0 : 0, a1 = bins ? a.g.p0 + a.g.nb : 0;     // the allowed window [a0, a1)
+    const long long a0 = bins ? a.g.p0 + (LIM ? wa : 0) : 0, a1 = bins ? a.g.p0 + (LIM ? wb + 1 : a.g.nb) : 0;     // the allowed window [a0, a1)
     const u32x4 ninf4 = {NegInf<T>::word, NegInf<T>::word, NegInf<T>::word, NegInf<T>::word};
     for (long long k = tid; k < nblk; k += LPB_THREADS) {
         const uintptr_t blk = base + (uintptr_t)k * 16;
@@ -192,23 +271,36 @@ static int gr_check_spec(int64_t p0, int nb, int64_t ts, int64_t tsep, int64_t t
     return EGOMI_OK;
 }
 
-extern "C" int egomi_traj_grammar_init(const int64_t* ids, int64_t ld_ids, const uint8_t* mask, int64_t ld_mask, int R, int S0, int64_t p0, int nb,
-                                       int64_t ts, int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int32_t* state,
-                                       int32_t* need, egomi_stream_t stream) {
-    if (!ids || !state || !need) return EGOMI_E_BADARG;
+template <bool POSE>
+static int gr_init(const int64_t* ids, int64_t ld_ids, const uint8_t* mask, int64_t ld_mask, int R, int S0, int64_t p0, int nb, int64_t ts, int64_t tsep,
+                   int64_t te, int64_t eos, int min_steps, int max_steps, int32_t* state, int32_t* need, int32_t* pose, egomi_stream_t stream) {
+    if (!ids || !state || !need || (POSE && !pose)) return EGOMI_E_BADARG;
     if (R <= 0 || S0 <= 0 || ld_ids < S0 || (mask && ld_mask < S0)) return EGOMI_E_SHAPE;
     GrammarSpec g;
     const int rc = gr_check_spec(p0, nb, ts, tsep, te, eos, min_steps, max_steps, g);
     if (rc != EGOMI_OK) return rc;
-    EGOMI_LAUNCH(traj_grammar_init_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, ids, (long long)ld_ids, mask, (long long)ld_mask, R,
-                 S0, g, state, need);
+    EGOMI_LAUNCH(traj_grammar_init_kernel<POSE>, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, ids, (long long)ld_ids, mask,
+                 (long long)ld_mask, R, S0, g, state, need, pose);
     return egomi_launch_status();
 }
 
-extern "C" int egomi_traj_grammar_step(void* logits, int64_t ld, int R, int V, const int64_t* tok_prev, int32_t* state, int64_t p0, int nb, int64_t ts,
-                                       int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int rem, float* mass, int64_t ld_mass,
-                                       int col, int dtype, egomi_stream_t stream) {
-    if (!logits || !state || !mass) return EGOMI_E_BADARG;
+extern "C" int egomi_traj_grammar_init(const int64_t* ids, int64_t ld_ids, const uint8_t* mask, int64_t ld_mask, int R, int S0, int64_t p0, int nb,
+                                       int64_t ts, int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int32_t* state,
+                                       int32_t* need, egomi_stream_t stream) {
+    return gr_init<false>(ids, ld_ids, mask, ld_mask, R, S0, p0, nb, ts, tsep, te, eos, min_steps, max_steps, state, need, nullptr, stream);
+}
+
+extern "C" int egomi_traj_grammar_init_limits(const int64_t* ids, int64_t ld_ids, const uint8_t* mask, int64_t ld_mask, int R, int S0, int64_t p0,
+                                              int nb, int64_t ts, int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps,
+                                              int32_t* state, int32_t* need, int32_t* pose, egomi_stream_t stream) {
+    return gr_init<true>(ids, ld_ids, mask, ld_mask, R, S0, p0, nb, ts, tsep, te, eos, min_steps, max_steps, state, need, pose, stream);
+}
+
+template <bool LIM>
+static int gr_step(void* logits, int64_t ld, int R, int V, const int64_t* tok_prev, int32_t* state, int64_t p0, int nb, int64_t ts, int64_t tsep,
+                   int64_t te, int64_t eos, int min_steps, int max_steps, int rem, float* mass, int64_t ld_mass, int col, const int32_t* lim,
+                   int32_t* pose, float* limits_mass, int dtype, egomi_stream_t stream) {
+    if (!logits || !state || !mass || (LIM && (!lim || !pose || !limits_mass))) return EGOMI_E_BADARG;
     if (dtype != EGOMI_F32 && dtype != EGOMI_BF16) return EGOMI_E_BADARG;
     if (R <= 0 || V <= 0 || ld < V || rem < 1 || col < 0 || ld_mass <= col) return EGOMI_E_SHAPE;
     GrammarStepArgs a;
@@ -217,7 +309,23 @@ extern "C" int egomi_traj_grammar_step(void* logits, int64_t ld, int R, int V, c
     if (p0 + nb > V || ts >= V || tsep >= V || te >= V || eos >= V) return EGOMI_E_SHAPE;
     if (((uintptr_t)logits) % (dtype == EGOMI_F32 ? 4 : 2)) return EGOMI_E_UNSUPPORTED;      // elements must be naturally aligned
     a.logits = logits; a.ld = ld; a.V = V; a.tok_prev = tok_prev; a.state = state; a.rem = rem; a.mass = mass; a.ld_mass = ld_mass; a.col = col;
-    if (V <= LPB_THREADS * LPB_NPT) EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((traj_grammar_step_kernel<T, true>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
-    else EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((traj_grammar_step_kernel<T, false>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
+    a.lim = lim; a.pose = pose; a.limits_mass = limits_mass;
+    if (V <= LPB_THREADS * LPB_NPT) EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((traj_grammar_step_kernel<T, true, LIM>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
+    else EGOMI_DISPATCH_DTYPE(dtype, EGOMI_LAUNCH((traj_grammar_step_kernel<T, false, LIM>), dim3(R), dim3(LPB_THREADS), 0, (hipStream_t)stream, a));
     return egomi_launch_status();
+}
+
+extern "C" int egomi_traj_grammar_step(void* logits, int64_t ld, int R, int V, const int64_t* tok_prev, int32_t* state, int64_t p0, int nb, int64_t ts,
+                                       int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int rem, float* mass, int64_t ld_mass,
+                                       int col, int dtype, egomi_stream_t stream) {
+    return gr_step<false>(logits, ld, R, V, tok_prev, state, p0, nb, ts, tsep, te, eos, min_steps, max_steps, rem, mass, ld_mass, col, nullptr, nullptr,
+                          nullptr, dtype, stream);
+}
+
+extern "C" int egomi_traj_grammar_step_limits(void* logits, int64_t ld, int R, int V, const int64_t* tok_prev, int32_t* state, int64_t p0, int nb,
+                                              int64_t ts, int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int rem, float* mass,
+                                              int64_t ld_mass, int col, const int32_t* lim, int32_t* pose, float* limits_mass, int dtype,
+                                              egomi_stream_t stream) {
+    return gr_step<true>(logits, ld, R, V, tok_prev, state, p0, nb, ts, tsep, te, eos, min_steps, max_steps, rem, mass, ld_mass, col, lim, pose,
+                         limits_mass, dtype, stream);
 }

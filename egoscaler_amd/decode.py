@@ -197,6 +197,51 @@ def traj_grammar_step(logits, tok_prev, state, spec, rem, mass, col):
          col, dt(logits.dtype), S())
 
 
+def traj_limits_check(lim, nb, rows):
+    """The motion-limits table of sample() / greedy() / generate(traj_limits=...) (traj.motion_limits), checked on the host before any
+    launch: `lim` is a CPU integer tensor or array [rows, 18] = lo[6] | hi[6] | dmax[6] in bins with 0 <= lo <= hi <= nb - 1 and
+    0 <= dmax <= nb - 1 (include/egomi.h egomi_traj_grammar_step_limits).  -> the table as a contiguous CPU int32 tensor.  It reads no
+    device memory: a table that lives on a device is refused, not fetched."""
+    if isinstance(lim, torch.Tensor):
+        if lim.is_cuda:
+            raise ValueError("traj_limits: the table is checked on the host; pass a CPU tensor or array, not a device tensor")
+        if lim.is_floating_point() or lim.dtype == torch.bool:
+            raise ValueError(f"traj_limits: an integer table of bins, not {lim.dtype}")
+        t = lim.detach().to(torch.int64)
+    else:
+        import numpy as np
+        a = np.asarray(lim)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"traj_limits: an integer table of bins, not {a.dtype}")
+        t = torch.from_numpy(a.astype(np.int64))
+    if t.dim() != 2 or tuple(t.shape) != (int(rows), 18):
+        raise ValueError(f"traj_limits: the table is [{int(rows)}, 18] = lo[6] | hi[6] | dmax[6] per row, not {list(t.shape)}")
+    if bool(((t < 0) | (t > nb - 1)).any()):
+        raise ValueError(f"traj_limits: every entry is a number of bins in [0, {nb - 1}]")
+    if bool((t[:, 0:6] > t[:, 6:12]).any()):
+        raise ValueError("traj_limits: lo <= hi does not hold in every row and dimension")
+    return t.to(torch.int32).contiguous()
+
+
+def traj_grammar_init_limits(ids, mask, spec, state, need, pose):
+    """traj_grammar_init, and pose int32 [R, 12] = prev[6] | cur[6] from the prompt (include/egomi.h egomi_traj_grammar_init_limits)."""
+    R, S0 = ids.shape
+    p0, nb, ts, tsep, te, eos, mn, mx = spec
+    call("egomi_traj_grammar_init_limits", ids, ids.stride(0), mask, mask.stride(0) if mask is not None else 0, R, S0, p0, nb, ts, tsep, te, eos,
+         mn, mx, state, need, pose, S())
+
+
+def traj_grammar_step_limits(logits, tok_prev, state, spec, rem, mass, col, lim, pose, limits_mass):
+    """traj_grammar_step under the motion limits lim int32 [R, 18] (include/egomi.h egomi_traj_grammar_step_limits): the bin window of a
+    row narrows to its limits around pose's last closed step, the pose moves with the state, and limits_mass[:, col] = the raw
+    probability of what is allowed under the limits (mass[:, col] stays what the grammar alone allows).  limits_mass has mass's stride."""
+    R, V = logits.shape
+    p0, nb, ts, tsep, te, eos, mn, mx = spec
+    assert lim.is_contiguous() and pose.is_contiguous() and limits_mass.stride(0) == mass.stride(0)
+    call("egomi_traj_grammar_step_limits", logits, logits.stride(0), R, V, tok_prev, state, p0, nb, ts, tsep, te, eos, mn, mx, rem, mass,
+         mass.stride(0), col, lim, pose, limits_mass, dt(logits.dtype), S())
+
+
 def seq_rank(sum_lp, n_tok, B, K, length_penalty=1.0):
     """Per clip, the K rows b * K + j by descending sum_lp / n_tok ** length_penalty (include/egomi.h egomi_seq_rank):
     -> (score fp32 [B, K], order int32 [B, K])."""
@@ -453,6 +498,7 @@ class Decoder:
         self.bs_mass = self.bs_mean = self.bs_std = self.bs_ent = None   # sample() / greedy() / score() with bin_stats=(p0, nb) (_bs_buffers)
         self._bs_values = {}
         self.gr_state = self.gr_need = self.gr_mass = None               # sample() / greedy() with grammar=spec (_grammar)
+        self.gr_lim = self.gr_pose = self.gr_limits_mass = None          # ... and limits=table
         self._score_act = None                              # score(): the activations of a suffix pass, made on first use (_score_buffers)
         self.kv_row = None                                  # beam mode: [B, Smax] int32, physical cache row of every key of every logical row
         if self.nb > 1:
@@ -524,15 +570,21 @@ class Decoder:
             self._bs_values[nb] = bin_edges(nb, dev)
         return p0, nb, self._bs_values[nb], (self.bs_mass, self.bs_mean, self.bs_std, self.bs_ent)
 
-    def _grammar(self, grammar, T_new):
+    def _grammar(self, grammar, T_new, limits=None):
         """The trajectory grammar of sample() / greedy() with grammar=spec: its static buffers, made on first use -- gr_state int32 [B, 2]
         (phase, steps per row), gr_need int32 [B] (the tokens the prompt row needs to close: a row with gr_need <= T_new ends `<te> eos`
         inside the loop, any other may not; the caller checks), gr_mass fp32 [B, max_len] (column t = the raw probability of step t's allowed
         set) -- and -> (head, mask, key).  head() queues egomi_traj_grammar_init on the prompt in self.seq / self.mask: the token loop
         starts with it, inside the captured graph, so every replay starts from the state of the prompt that is in the static buffers then,
         not from where the last replay ended.  mask(t) queues step t's egomi_traj_grammar_step on self.lg, directly before the token
-        kernel.  key: what the grammar adds to a graph key (the spec with its step limits).  None: no launch, no buffer, () as key."""
+        kernel.  key: what the grammar adds to a graph key (the spec with its step limits).  None: no launch, no buffer, () as key.
+        limits=table (traj_limits_check; [B, 18] CPU integers): the motion limits.  Three more static buffers, made on first use -- gr_lim
+        int32 [B, 18], gr_pose int32 [B, 12], gr_limits_mass fp32 [B, max_len] -- and the two launches become egomi_traj_grammar_init_limits
+        / egomi_traj_grammar_step_limits.  The table is copied into gr_lim here, before the loop, on every call: the captured loop reads
+        it from there, so the key gains the constant "limits" only and a replay with another table needs no re-capture."""
         if grammar is None:
+            if limits is not None:
+                raise ValueError("motion limits narrow the trajectory grammar's bin window: `limits` needs `grammar`")
             return (lambda: None), (lambda t: None), ()
         if self.nb > 1:
             raise ValueError("a trajectory grammar is for num_beams == 1: the beams of an item share one prefill logits row at step 0")
@@ -543,6 +595,22 @@ class Decoder:
             self.gr_need = torch.zeros(self.B, dtype=torch.int32, device=dev)
             self.gr_mass = torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev)
         S0 = self.pos
+        if limits is not None:
+            table = traj_limits_check(limits, spec[1], self.B)
+            if self.gr_lim is None:
+                dev = self.eng.device
+                self.gr_lim = torch.zeros(self.B, 18, dtype=torch.int32, device=dev)
+                self.gr_pose = torch.zeros(self.B, 12, dtype=torch.int32, device=dev)
+                self.gr_limits_mass = torch.zeros(self.B, self.Smax, dtype=torch.float32, device=dev)
+            self.gr_lim.copy_(table)
+
+            def head_l():
+                traj_grammar_init_limits(self.seq_buf[:, :S0], self.mask_buf[:, :S0], spec, self.gr_state, self.gr_need, self.gr_pose)
+
+            def mask_l(t):
+                traj_grammar_step_limits(self.lg, None if t == 0 else self.tok.view(-1), self.gr_state, spec, T_new - t, self.gr_mass, t,
+                                         self.gr_lim, self.gr_pose, self.gr_limits_mass)
+            return head_l, mask_l, ("grammar",) + spec + ("limits",)
 
         def head():
             traj_grammar_init(self.seq_buf[:, :S0], self.mask_buf[:, :S0], spec, self.gr_state, self.gr_need)
@@ -754,7 +822,7 @@ class Decoder:
         return self._scores[T_new]
 
     def sample(self, T_new, do_sample=True, temperature=1.0, top_k=50, top_p=0.95, repetition_penalty=1.0, eos=None, pad=None, seed=None,
-               use_graph=True, logprobs=False, bin_stats=None, grammar=None):
+               use_graph=True, logprobs=False, bin_stats=None, grammar=None, limits=None):
         """After prefill(): T_new steps of HF generate's token loop (model_arch.py:82-108 -> GenerationMixin: logits processors, warpers,
         multinomial / arg-max, eos bookkeeping), every step one egomi_sample_rows launch + one cached decode step, all of them captured
         into ONE hipGraph (the draw counter and `pos` are launch constants, seed and done flags live in device memory).
@@ -772,9 +840,12 @@ class Decoder:
         of the constrained distribution, and logprobs / bin_stats describe that same renormalised distribution -- the one the token was
         drawn from, a proper distribution over valid trajectories; the raw signal survives in gr_mass alone.  A row with
         self.gr_need <= T_new ends `<te> eos` with min_steps <= n <= max_steps.  A graph of its own (the spec and its limits are part of the
-        key); None: the loop has the launches it had."""
+        key); None: the loop has the launches it had.
+        limits=table (with grammar; traj.motion_limits, [B, 18] CPU integers): per-row, per-dimension motion limits on the bins
+        (_grammar): the same two launches in their *_limits form, self.gr_limits_mass[:, t] = the raw probability of what the limits
+        allow beside gr_mass[:, t].  The table lives in self.gr_lim: another table replays the same graph."""
         emit, readout_key = self._readouts(logprobs, bin_stats, eos)
-        gr_head, gr_mask, gr_key = self._grammar(grammar, T_new)
+        gr_head, gr_mask, gr_key = self._grammar(grammar, T_new, limits)
         S0, sc_buf = self.pos, self._score_buf(T_new)
         self._seed(seed)
         self.done_buf.zero_()
@@ -795,14 +866,15 @@ class Decoder:
         self.pos = S0 + T_new
         return self.seq, sc_buf
 
-    def greedy(self, T_new, use_graph=True, keep_scores=True, logprobs=False, bin_stats=None, grammar=None):
+    def greedy(self, T_new, use_graph=True, keep_scores=True, logprobs=False, bin_stats=None, grammar=None, limits=None):
         """After prefill(): T_new greedy tokens.  Returns (sequences [B,S0+T], scores list or None).  logprobs=True: one egomi_token_logprob
         launch per step after the arg-max, into self.lp_tok / lp_sum / lp_n as in sample() (no eos here: every row counts every step).
         bin_stats=(p0, nb): one egomi_bin_stats launch per step after those, into self.bs_mass / bs_mean / bs_std / bs_ent as in sample().
         grammar=spec: as in sample(): the init launch before the loop and one egomi_traj_grammar_step launch per step before the scores
-        are kept and the arg-max runs, so scores, logprobs and bin_stats are those of the constrained row; self.gr_mass / gr_need as there."""
+        are kept and the arg-max runs, so scores, logprobs and bin_stats are those of the constrained row; self.gr_mass / gr_need as there.
+        limits=table: as in sample()."""
         emit, _ = self._readouts(logprobs, bin_stats, None)
-        gr_head, gr_mask, _ = self._grammar(grammar, T_new)
+        gr_head, gr_mask, _ = self._grammar(grammar, T_new, limits)
         S0 = self.pos
         scores = None                                       # eager: fp32 clones; captured: views of one buffer the graph writes
         if keep_scores:
@@ -931,13 +1003,15 @@ class Decoder:
         self._cands = {}
 
     def beam(self, T_new, num_return_sequences=1, length_penalty=1.0, early_stopping=False, do_sample=False, temperature=1.0, top_k=50,
-             top_p=1.0, repetition_penalty=1.0, eos=None, pad=None, seed=None, use_graph=True, grammar=None):
+             top_p=1.0, repetition_penalty=1.0, eos=None, pad=None, seed=None, use_graph=True, grammar=None, limits=None):
         """After prefill(nb=self.nb): HF _beam_search (generation/utils.py:3208-3560) for T_new steps, every step one egomi_beam_rows + one
         egomi_beam_update launch + one cached decode step over the B * nb logical beams, all captured into ONE hipGraph (no host sync per
         step: the loop-open flag lives in device memory and closes the remaining steps when HF would have left its loop).
         Returns (sequences [B*nrs, S0 + Lgen], sequences_scores [B*nrs], scores [iterations, B*nb, V] fp32, beam_indices [B*nrs, Lgen])."""
         if grammar is not None:
             raise ValueError("beam() takes no trajectory grammar: the beams of an item share one prefill logits row at step 0")
+        if limits is not None:
+            raise ValueError("beam() takes no motion limits: they narrow the trajectory grammar's bin window, and beam() takes no grammar")
         nb, R, S0, dev = self.nb, self.B, self.pos, self.eng.device
         Bi, V = R // nb, self.lg.shape[1]
         n_eos = 0 if eos is None else 1

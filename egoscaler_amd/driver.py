@@ -185,6 +185,7 @@ BASE_SUMS = ("ADE", "FDE", "ADE_as_called", "GD", "n")
 BEST_SUMS = ("minADE", "minFDE", "n_min")
 SEL_SUMS = ("ADE_sel", "FDE_sel", "n_sel")
 MODE_SUMS = ("minADE_M", "minFDE_M", "brierADE_M", "n_M", "modes", "clips_M")      # n_M: clips with a mode; modes over clips_M clips
+LIMIT_SUMS = ("n_limit_viol", "lmass_min", "n_lmass")                             # violating bin tokens (all rows); per clip the smallest limits mass
 GRAMMAR_SUMS = ("gmass_mean", "gmass_min", "n_gmass")                             # per clip: mean and smallest per-step mass of the allowed set
 SOFT_SUMS = ("ADE_soft", "FDE_soft", "n_soft", "std", "n_std", "mass_min")        # std over n_std coordinates; the smallest masses
 FULL_SUMS = ("IDE", "DTW", "GD_dev", "n_full", "minIDE", "minGD", "minDTW", "n_fmin", "GD_sel", "DTW_sel", "n_fsel", "minGD_M", "minDTW_M", "n_fM")
@@ -225,6 +226,39 @@ def parse_trajectories(ids, tok, num_steps, Tn, norm, max_abs, device):
     return gen, torch.from_numpy(np.ascontiguousarray(gen, dtype=np.float32)).to(device), n_h
 
 
+def _six(text, name, n=6):
+    """`a,b,...` -> n floats; an empty field or `none` = no limit there (NaN)."""
+    parts = [v.strip() for v in str(text).split(",")]
+    if len(parts) != n:
+        raise ValueError(f"{name} takes {n} comma-separated numbers, not {text!r}")
+    try:
+        return [float("nan") if v.lower() in ("", "none") else float(v) for v in parts]
+    except ValueError:
+        raise ValueError(f"{name} takes {n} comma-separated numbers, not {text!r}") from None
+
+
+def traj_limit_options(args, constrain):
+    """--traj_workspace / --traj_max_step resolved: None with both off, else (lo [6], hi [6], max_step [6]) in the units of the
+    de-normalised trajectories, NaN = no limit (the workspace bounds x, y, z only).  Both need --constrain_traj; raises ValueError."""
+    ws, ms = getattr(args, "traj_workspace", None), getattr(args, "traj_max_step", None)
+    if ws is None and ms is None:
+        return None
+    if not constrain:
+        raise ValueError("--traj_workspace / --traj_max_step narrow the bin window of constrained decoding: they need --constrain_traj")
+    nan = float("nan")
+    lo, hi, step = [nan] * 6, [nan] * 6, [nan] * 6
+    if ws is not None:
+        w = _six(ws, "--traj_workspace")
+        lo[:3], hi[:3] = w[0::2], w[1::2]
+        if any(a > b for a, b in zip(lo[:3], hi[:3])):
+            raise ValueError(f"--traj_workspace is x0,x1,y0,y1,z0,z1 with x0 <= x1, y0 <= y1, z0 <= z1, not {ws!r}")
+    if ms is not None:
+        step = _six(ms, "--traj_max_step")
+        if any(v < 0 for v in step):
+            raise ValueError(f"--traj_max_step is six distances >= 0, not {ms!r}")
+    return lo, hi, step
+
+
 def generate_kwargs(o, args, tok):
     """generate()'s keyword arguments for the decoding mode: K samples on a shared prompt, beams, or neither; the bin statistics."""
     kw = {"output_bin_stats": True, "bin_token_ids": (tok.p0, tok.num_bins)} if o.soft else {}
@@ -243,17 +277,21 @@ def generate_batch(model, data, args, device, o, idx, norm):
     batch = data.batch(idx, device, args.max_traj_token)
     prompts, gt = batch["prompts"], batch["trajectories"]
     fps0 = torch.zeros(len(idx), dtype=torch.int32, device=device)
+    lim = None
+    if o.limits is not None:                                 # physical limits -> bins, per clip (its own max_abs under --do_standard)
+        lim = T.motion_limits(tok, norm, *o.limits, max_abs=batch["max_abs"].cpu().numpy())
     out = model.generate(input_ids=prompts, attention_mask=batch["prompt_masks"], point_clouds=batch["pcrgbs"],
                          max_length=batch["tokens"].shape[1] - prompts.shape[1], do_sample=o.sample, fps_start=fps0,
                          kv_cache_dtype=getattr(args, "kv_cache_dtype", None),
-                         decode_weight_dtype=getattr(args, "decode_weight_dtype", None), **generate_kwargs(o, args, tok))
+                         decode_weight_dtype=getattr(args, "decode_weight_dtype", None), **generate_kwargs(o, args, tok),
+                         **({} if lim is None else {"traj_limits": lim}))
     all_ids = out.sequences[:, prompts.shape[1]:]
     head = prompts[:, -7:]                                   # the prompt holds the first step; with its <tsep> it is parsed like the rest
     mabs = batch["max_abs"].cpu().numpy()
     gen, gen_d, n_h = parse_trajectories(torch.cat([head.repeat_interleave(o.K, 0), all_ids], 1), tok, args.num_steps, gt.shape[1], norm,
                                          np.repeat(mabs, o.K, axis=0), device)
     return types.SimpleNamespace(batch=batch, prompts=prompts, head=head, gt=gt, gt_h=gt.cpu().numpy(), mabs=mabs, fps0=fps0, out=out,
-                                 all_ids=all_ids, ids_h=batch["image_ids"].cpu().numpy(), gen=gen, gen_d=gen_d, n_h=n_h,
+                                 all_ids=all_ids, ids_h=batch["image_ids"].cpu().numpy(), gen=gen, gen_d=gen_d, n_h=n_h, lim=lim,
                                  gen_k=gen_d.view(len(idx), o.K, gt.shape[1], -1),
                                  n_k=torch.from_numpy((n_h > 0).astype(np.int32) * gt.shape[1]).to(device).view(len(idx), o.K))
 
@@ -340,6 +378,24 @@ def grammar_batch(o, b, tok, sums):
     mean = (mass * live).sum(1) / lens
     low = mass.masked_fill(~live, float("inf")).min(1).values
     _add(sums, gmass_mean=mean.sum(), gmass_min=low.sum(), n_gmass=len(mean))
+
+
+def limits_batch(o, b, tok, sums):
+    """Every row: the bin tokens it generated outside their window (T.limits_violations, the host restatement of the kernel's rule; the
+    prompt's own tokens only move the pose); sample 0 of every clip: the smallest raw probability a step left inside the limits."""
+    from .decode import candidate_lengths
+    S0 = b.prompts.shape[1]
+    viol = T.limits_violations(b.out.sequences.cpu(), tok, b.lim.repeat_interleave(o.K, 0), start=S0)
+    mass = b.out.limits_mass[::o.K].double()
+    lens = candidate_lengths(b.all_ids[::o.K], tok.eos).clamp(min=1)
+    live = torch.arange(mass.shape[1], device=mass.device)[None, :] < lens[:, None]
+    low = mass.masked_fill(~live, float("inf")).min(1).values
+    _add(sums, n_limit_viol=int(viol.sum()), lmass_min=low.sum(), n_lmass=len(low))
+
+
+def limits_record(o, args, sums):
+    return {"n_limit_viol": int(sums["n_limit_viol"]), "limits_mass_min": _mean(sums, "lmass_min", "n_lmass"),
+            "traj_workspace": getattr(args, "traj_workspace", None), "traj_max_step": getattr(args, "traj_max_step", None)}
 
 
 def grammar_record(o, sums):
@@ -477,11 +533,18 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
     every generated row is a well-formed trajectory of exactly args.num_steps steps, the prompt's first step included (the state is read
     from the prompt).  The record gains 'grammar_mass_mean' and 'grammar_mass_min': the mean over the clips (sample 0) of the mean, and of
     the smallest, raw probability that a step gave the ids the grammar allowed -- how much of the model's own mass the constraint kept.
-    Off, every record, dump and bit is what it is without it."""
+    Off, every record, dump and bit is what it is without it.
+
+    args.traj_workspace "x0,x1,y0,y1,z0,z1" / args.traj_max_step "dx,dy,dz,rx,ry,rz" (both optional, both need constrain_traj; units of the
+    de-normalised trajectories; an empty field = no limit there): generate(traj_limits=T.motion_limits(...)), the limits converted to bins
+    per clip with conservative rounding and enforced on the device at every bin token.  The record gains 'n_limit_viol' (bin tokens outside
+    their window over all rows, counted by T.limits_violations on the host: it must be 0), 'limits_mass_min' (as 'grammar_mass_min', of the
+    probability the limits left allowed) and the two settings.  Off, every record, dump, launch and bit is what it is without them."""
     o = val_options(args, num_beams, num_samples, select, num_modes, mode_radius, soft_decode, full_metrics, constrain_traj)
+    o.limits = traj_limit_options(args, o.constrain)
     rank, world = _rank_world()
     norm = getattr(data, "norm", None) or T.TargetNorm()
-    sums = dict.fromkeys(BASE_SUMS + BEST_SUMS + SEL_SUMS + MODE_SUMS + SOFT_SUMS + FULL_SUMS + GRAMMAR_SUMS, 0.0)
+    sums = dict.fromkeys(BASE_SUMS + BEST_SUMS + SEL_SUMS + MODE_SUMS + SOFT_SUMS + FULL_SUMS + GRAMMAR_SUMS + LIMIT_SUMS, 0.0)
     dump, picked, mode_dump, soft_dump, full_dump = {}, {}, {}, {}, {}
     model.eval()
     for idx in rank_batches(len(data), micro_batch_per_rank(args.bs, 1, world), rank, world, max_batches):
@@ -489,6 +552,8 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
         base_batch(o, b, sums, dump)
         if o.constrain:
             grammar_batch(o, b, model.dims.tok, sums)
+        if o.limits is not None:
+            limits_batch(o, b, model.dims.tok, sums)
         if o.soft:
             soft_batch(o, b, model.dims.tok, args.num_steps, norm, sums, soft_dump)
         if o.K > 1:
@@ -520,6 +585,8 @@ def run_validation(model, data, args, device, max_batches=None, num_beams=1, num
         dump["full"] = full_dump
     if o.constrain:
         rec.update(grammar_record(o, sums))
+    if o.limits is not None:
+        rec.update(limits_record(o, args, sums))
     return rec, dump
 
 
@@ -787,7 +854,18 @@ def parse_args(argv=None):
                     help="validation / eval with --num_beams 1: constrained decoding, every generated row is a well-formed trajectory of exactly "
                          "--num_steps steps (the prompt's first step included), by one grammar launch per step on the device; adds "
                          "grammar_mass_mean / grammar_mass_min (the raw probability the model gave the allowed ids) to the record")
+    ap.add_argument("--traj_workspace", default=None, metavar="x0,x1,y0,y1,z0,z1",
+                    help="with --constrain_traj: every generated waypoint stays inside this box (units of the de-normalised trajectories; an "
+                         "empty field = no bound; write --traj_workspace=-2,2,... when it starts with a minus sign), enforced on the device at "
+                         "every bin token; adds n_limit_viol (must be 0) and limits_mass_min to the record")
+    ap.add_argument("--traj_max_step", default=None, metavar="dx,dy,dz,rx,ry,rz",
+                    help="with --constrain_traj: no waypoint moves farther than this from the one before it, per dimension (same units; an "
+                         "empty field = no cap), the prompt's step included; record keys as --traj_workspace")
     a = ap.parse_args(argv)
+    try:
+        traj_limit_options(a, a.constrain_traj)
+    except ValueError as e:
+        ap.error(str(e))
     if not a.max_grad_norm >= 0:
         ap.error("--max_grad_norm must be >= 0 (0: off)")
     if not 0 <= a.bin_sigma <= 16:                                       # (refuses NaN and inf as well)

@@ -155,6 +155,8 @@ class GenerateOutput:
     bin_entropy: Optional[torch.Tensor] = None          # its entropy in nats
     # generate(traj_grammar=spec) only: fp32 [rows, T'], column t = the raw probability of the ids the grammar allowed at step t; 0 after a row's eos
     grammar_mass: Optional[torch.Tensor] = None
+    # generate(traj_limits=table) only: fp32 [rows, T'], column t = the raw probability of the ids allowed under the motion limits at step t; 0 after a row's eos
+    limits_mass: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -608,7 +610,7 @@ class TrajPointLLMForCausalLM(nn.Module):
                  top_p=0.95, repetition_penalty=1.0, do_sample=True, num_return_sequences=1, fps_start=None,
                  eos_token_id="config", pad_token_id=None, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False, kv_cache_dtype=None,
                  decode_weight_dtype=None, share_prompt=False, kv_cache_layout=None, output_logprobs=False, rank_length_penalty=1.0, output_bin_stats=False,
-                 bin_token_ids=None, traj_grammar=None, **kwargs):
+                 bin_token_ids=None, traj_grammar=None, traj_limits=None, **kwargs):
         """model_arch.py:77-108: `max_length` means max_new_tokens; returns .sequences [B,S0+T'] and .scores (T' x [B,V], the PROCESSED
         scores, as HF returns them with output_scores=True).  Prefill runs encoder + splice and fills the KV cache; every later step
         feeds one token (the behaviour pointllm.py:112,255-275 intends; see DESIGN.md on the reference's cache bug).
@@ -686,7 +688,22 @@ class TrajPointLLMForCausalLM(nn.Module):
         was drawn from, a proper distribution over valid trajectories.  What the model itself thought of the grammar survives in
         grammar_mass fp32 [rows, T']: column t = the raw probability of the ids allowed at step t (0 after a row's eos).  eos_token_id must
         be the spec's eos.  Works with every cache and weight dtype, share_prompt and LoRA; num_beams > 1 raises ValueError.  None: every
-        graph, launch and output is what it is without the option."""
+        graph, launch and output is what it is without the option.
+
+        traj_limits=table (with traj_grammar; traj.motion_limits / motion_limits_bins): per-prompt, per-dimension motion limits on the
+        waypoints, enforced on the device at every bin token.  The table is [B, 18] CPU integers in bins, one row per prompt (expanded
+        to the K rows of num_return_sequences, with or without share_prompt): lo[6] | hi[6] = the inclusive box of every trajectory
+        dimension, dmax[6] = the largest allowed |bin_t - bin_(t-1)| between consecutive waypoints, the prompt's last complete step
+        included (csrc/grammar.hip states the rule; a waypoint farther than dmax outside the box moves toward it by dmax per step).  The
+        two grammar launches run in their *_limits form and nothing is added to the loop; when a trajectory may end does not change.
+        limits_mass fp32 [rows, T'] holds, beside grammar_mass, the raw probability of what the limits left allowed:
+        limits_mass / grammar_mass is how much the model wanted to break them.  The table lives in a device buffer the captured loop
+        reads, so a call with another table replays the same graph.  Needs traj_grammar; num_beams > 1 raises ValueError.  None: every
+        graph, launch and output is what generate(traj_grammar=...) gives without it."""
+        if traj_limits is not None and traj_grammar is None:
+            raise ValueError("traj_limits narrows the bin window of the trajectory grammar: it needs traj_grammar")
+        if traj_limits is not None and int(num_beams) > 1:
+            raise ValueError("traj_limits is for num_beams == 1, like traj_grammar")
         if traj_grammar is not None and int(num_beams) > 1:
             raise ValueError("traj_grammar is for num_beams == 1: the beams of an item share one prefill logits row at step 0")
         if output_logprobs and int(num_beams) > 1:
@@ -729,6 +746,11 @@ class TrajPointLLMForCausalLM(nn.Module):
         dev = self.engine.device
         ids, fps_start = self._decode_inputs(input_ids, point_clouds, fps_start)
         n_ret = int(num_return_sequences)
+        limits = None
+        if traj_limits is not None:                        # checked per prompt, then one row per decoder row (row b * K + j = sample j of prompt b)
+            from ..decode import grammar_check, traj_limits_check
+            limits = traj_limits_check(traj_limits, grammar_check(traj_grammar, self.dims.lm.vocab_size)[1], ids.shape[0])
+            limits = limits.repeat_interleave(max(n_ret, 1), 0)
         nb = int(num_beams)
         if nb < 1:
             raise ValueError(f"`num_beams` has to be a strictly positive integer, but is {num_beams}")
@@ -769,7 +791,7 @@ class TrajPointLLMForCausalLM(nn.Module):
             temperature, top_k, top_p = 1.0, 0, 1.0
         seq, sc = dec.sample(T, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                              eos=eos_token_id, pad=pad_token_id, seed=seed, use_graph=kwargs.get("use_graph", True),
-                             logprobs=bool(output_logprobs), bin_stats=bins, grammar=grammar)
+                             logprobs=bool(output_logprobs), bin_stats=bins, grammar=grammar, limits=limits)
         stop = T
         if eos_token_id is not None and T > 0:             # HF leaves the loop after the step at which the last unfinished row emitted eos
             hit = seq[:, S0:] == eos_token_id
@@ -786,6 +808,8 @@ class TrajPointLLMForCausalLM(nn.Module):
             _fill_bin_stats(out, dec, stop, past=past)
         if grammar is not None:
             out.grammar_mass = dec.gr_mass[:, :stop].masked_fill(past, 0.0)
+        if limits is not None:
+            out.limits_mass = dec.gr_limits_mass[:, :stop].masked_fill(past, 0.0)
         return out
 
     def _grammar_ready(self, traj_grammar, ids, attention_mask, eos_token_id, T):

@@ -72,6 +72,104 @@ def grammar_spec(tok, min_steps: int, max_steps: int) -> GrammarSpec:
     return GrammarSpec(int(tok.p0), int(tok.num_bins), int(tok.ts), int(tok.tsep), int(tok.te), int(tok.eos), mn, mx)
 
 
+def motion_limits_bins(lo=None, hi=None, dmax=None, nb=256, rows=1):
+    """The motion-limits table of generate(traj_limits=...) from limits already in bins: lo, hi, dmax are None (full range: 0, nb - 1, no
+    cap = nb - 1), one integer, six of them (one per trajectory dimension x, y, z, rx, ry, rz) or [rows, 6] -> int32 [rows, 18] =
+    lo | hi | dmax.  lo[d] <= bin <= hi[d] is the box, inclusive; dmax[d] the largest |bin_t[d] - bin_(t-1)[d]|.  Ranges are checked as
+    decode.traj_limits_check checks them."""
+    from .decode import traj_limits_check
+    nb, rows = int(nb), int(rows)
+    cols = []
+    for v, full in ((lo, 0), (hi, nb - 1), (dmax, nb - 1)):
+        a = np.full((rows, 6), full, dtype=np.int64) if v is None else np.asarray(v)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"motion_limits_bins: limits in bins are integers, not {a.dtype}")
+        cols.append(np.broadcast_to(a.astype(np.int64), (rows, 6)))
+    return traj_limits_check(np.concatenate(cols, axis=1), nb, rows)
+
+
+def motion_limits(tok, norm, lo=None, hi=None, max_step=None, max_abs=None):
+    """The motion-limits table of generate(traj_limits=...) from limits in the data's physical units (what TargetNorm.denorm returns:
+    metres and rotation vectors): lo / hi [6] or [B, 6] = the box per dimension, max_step [6] or [B, 6] = the largest move per step and
+    dimension, each None (or NaN / +-inf entries) for no limit; max_abs [B, 6] = the per-sample scale of `--do_standard` (None: one row
+    with max_abs = 1).  -> int32 [B, 18] = lo | hi | dmax in bins, one row per sample.
+    Bin i has the normalised value c_i = linspace(-1, 1, nb)[i] (bin_edges) and de-normalises through TargetNorm.denorm, which is affine per
+    dimension: v -> offset + scale * c with scale = norm.denorm_scale(max_abs) > 0.  Rounding is conservative: lo rounds up to the first
+    bin whose centre de-normalises >= lo, hi down to the last whose centre de-normalises <= hi, dmax down to the largest count of bins
+    whose centres lie no farther apart than max_step -- each verified with denorm itself on the neighbouring bins, not trusted to the
+    division.  A box that holds no bin centre raises ValueError."""
+    nb = int(tok.num_bins)
+    m = np.ones((1, 6)) if max_abs is None else np.asarray(max_abs, dtype=np.float64).reshape(-1, 6)
+    B = m.shape[0]
+    c = np.linspace(-1, 1, nb)
+    phys = norm.denorm(np.broadcast_to(c[None, :, None], (B, nb, 6)), m)            # [B, nb, 6]: every bin centre de-normalised
+    if bool((np.diff(phys, axis=1) <= 0).any()):
+        raise ValueError("motion_limits: the de-normalisation must increase with the bin in every dimension (std and max_abs > 0)")
+
+    def rows(v, fill):
+        a = np.full((B, 6), fill) if v is None else np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (B, 6)))
+        return np.where(np.isnan(a), fill, a)
+    plo, phi, pst = rows(lo, -np.inf), rows(hi, np.inf), rows(max_step, np.inf)
+    if bool((pst < 0).any()):
+        raise ValueError("motion_limits: max_step is a distance, >= 0")
+    blo = (phys < plo[:, None, :]).sum(1)                                           # the first bin with phys >= lo
+    bhi = nb - 1 - (phys > phi[:, None, :]).sum(1)                                  # the last bin with phys <= hi
+    if bool((blo > bhi).any()):
+        raise ValueError("motion_limits: no bin centre de-normalises inside [lo, hi] in some dimension")
+    dmax = np.zeros((B, 6), dtype=np.int64)
+    for k in range(1, nb):                                                          # the largest k with every pair of centres k apart <= max_step
+        ok = (phys[:, k:, :] - phys[:, :-k, :]).max(1) <= pst
+        dmax = np.where(ok & (dmax == k - 1), k, dmax)
+    from .decode import traj_limits_check
+    return traj_limits_check(np.concatenate([blo, bhi, dmax], axis=1), nb, B)
+
+
+def limits_window(lo, hi, dmax, q):
+    """The one window rule of the motion limits (csrc/grammar.hip gr_window) on the host: the inclusive window (a, b) of bin indices for a
+    dimension with limits (lo, hi, dmax) whose last closed step chose bin q (q < 0: unknown)."""
+    if q < 0:
+        return lo, hi
+    a, b = max(lo, q - dmax), min(hi, q + dmax)
+    if a > b:                                                                       # q lies farther than dmax outside the box: the cap wins
+        a = b = min(max(lo if q < lo else hi, q - dmax), q + dmax)
+    return a, b
+
+
+def limits_violations(ids, tok, lim, start=0):
+    """The validator of generate(traj_limits=...): ids [R, L] (whole sequences, prompt included: the last pose of the prompt limits the first
+    generated step), lim [R, 18] -> int64 numpy [R], the number of bin tokens per row that lie outside their window.  It walks every row
+    with the grammar's pose rule on the host in numpy: from the row's last <ts> (none: nothing is counted), a bin in a run of at most six
+    after <ts> / <tsep> is dimension = its place in the run and is held against limits_window(lo, hi, dmax, prev[dimension]); <tsep> after
+    six bins makes them prev, after fewer makes prev unknown; any other token ends the run.  Tokens after the first eos are not read.
+    start: only bin tokens at columns >= start are counted (the prompt length: what the prompt holds was not the decoder's choice); the
+    pose is followed from the row's beginning either way."""
+    ids = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids).astype(np.int64)
+    lim = np.asarray(lim.cpu() if isinstance(lim, torch.Tensor) else lim).astype(np.int64)
+    if ids.ndim != 2 or lim.shape != (ids.shape[0], 18):
+        raise ValueError(f"limits_violations: ids [R, L] and lim [R, 18], not {ids.shape} and {lim.shape}")
+    p0, nb = int(tok.p0), int(tok.num_bins)
+    out = np.zeros(ids.shape[0], dtype=np.int64)
+    for r, row in enumerate(ids.tolist()):
+        last = max((j for j, t in enumerate(row) if t == tok.ts), default=None)
+        if last is None:
+            continue
+        prev, cur, run = [-1] * 6, [-1] * 6, 0
+        for j, t in enumerate(row[last + 1:], last + 1):
+            if t == tok.eos:
+                break
+            if p0 <= t < p0 + nb:
+                if run < 6:
+                    a, b = limits_window(int(lim[r, run]), int(lim[r, 6 + run]), int(lim[r, 12 + run]), prev[run])
+                    out[r] += j >= start and not a <= t - p0 <= b
+                    cur[run] = t - p0
+                    run += 1
+                continue
+            if t == tok.tsep:
+                prev = list(cur) if run == 6 else [-1] * 6
+            run = 0
+    return out
+
+
 SoftTargetSpec = collections.namedtuple("SoftTargetSpec", "p0 nb sigma radius")
 
 

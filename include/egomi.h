@@ -384,6 +384,30 @@ int egomi_traj_grammar_init(const int64_t* ids, int64_t ld_ids, const uint8_t* m
 int egomi_traj_grammar_step(void* logits, int64_t ld, int R, int V, const int64_t* tok_prev, int32_t* state, int64_t p0, int nb, int64_t ts,
                             int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int rem, float* mass, int64_t ld_mass, int col,
                             int dtype, egomi_stream_t stream);
+/* Motion limits in constrained decoding: the two grammar kernels with a per-row table of limits and a per-row pose (csrc/grammar.hip states
+ * the one rule).  lim int32 [R, 18] = lo[6] | hi[6] | dmax[6] in bins: the inclusive box per trajectory dimension and the largest allowed
+ * |bin_t - bin_(t-1)|, nb - 1 = no cap.  pose int32 [R, 12] = prev[6] | cur[6]: the bins of the last CLOSED step (-1: unknown) and of the
+ * open step seen so far.  Both are contiguous.
+ *   grammar_init_limits: grammar_init, and pose[r] from the prompt: prev is committed at a <tsep> only when the run before it held six
+ *                bins (else -1), <ts> resets it, cur = the bins of the trailing run (-1 elsewhere).  No <ts>: all -1.
+ *   grammar_step_limits: grammar_step, where the state allows bins at phase p with the window of bin ids narrowed to dimension p's
+ *                [max(lo, q - dmax), min(hi, q + dmax)] around q = prev[p] ([lo, hi] when q < 0; when that is empty, q lies farther than
+ *                dmax outside the box and the one bin dmax nearer to the box is the window).  Never empty, always inside the bin ids:
+ *                lo, hi, dmax and q are clamped into range on load, so the kernel is safe on a table nobody checked (the launch cannot
+ *                read it; decode.traj_limits_check does on the host).  tok_prev moves the pose with the state: a bin taken at phase p
+ *                sets cur[p], <tsep> taken at phase 6 copies cur to prev, <ts> taken at phase 9 sets prev to -1, any token that does not
+ *                move the phase leaves it.  mass keeps grammar_step's meaning and bits (what the grammar ALONE allows);
+ *                limits_mass[r*ld_mass + col] = the same sum over the ids allowed under the limits, the same float64 terms in the same
+ *                order: with a full-range table it is bit-equal to mass, and so are the logits and the state to grammar_step's.  A
+ *                row's bits depend on its values, state, pose, limits and (V, spec, dtype) only.
+ * Errors as grammar_init / grammar_step; pose, lim and limits_mass NULL: BADARG. */
+int egomi_traj_grammar_init_limits(const int64_t* ids, int64_t ld_ids, const uint8_t* mask, int64_t ld_mask, int R, int S0, int64_t p0, int nb,
+                                   int64_t ts, int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int32_t* state,
+                                   int32_t* need, int32_t* pose, egomi_stream_t stream);
+int egomi_traj_grammar_step_limits(void* logits, int64_t ld, int R, int V, const int64_t* tok_prev, int32_t* state, int64_t p0, int nb,
+                                   int64_t ts, int64_t tsep, int64_t te, int64_t eos, int min_steps, int max_steps, int rem, float* mass,
+                                   int64_t ld_mass, int col, const int32_t* lim, int32_t* pose, float* limits_mass, int dtype,
+                                   egomi_stream_t stream);
 /* Beam search / beam sampling (num_beams > 1): HF GenerationMixin._beam_search, transformers 5.15 generation/utils.py:3208-3560.
  * Logical rows r = b * nb + j (item b, beam j), R = B * nb.  Every step is one beam_rows + one beam_update launch; ctl (int32 [6], device)
  * holds the loop-open flag [0] and the iteration count [1]: once a step closes the loop, both return at once, so T captured steps
